@@ -21,10 +21,18 @@ event pair would also count the time it waits for the previous frame's CUs), wit
 --pipeline 1 the mean event pair: the 1-spp cost pre-pass + LPT ordering (~1 % of the
 call at 256 spp) and the main kernel k_render_ps (the rocprof kernel trace under
 profiles/ lists them separately).  At N > 1 every rank reports the same figures for its
-own tiles (per_rank: launch ms, gather ms, roofline frac), rank 0 times the CPU baseline
-and runs the live PMC passes on its own GPU (a frame of the per-GPU workload alone).
+own tiles (per_rank: launch ms, gather ms, roofline frac).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene sponza|bunny|cornell]
+A plain run does what the headline figure needs and no more: scene upload, one instrumented
+counting pass, the warm-up steps, the K timed steps, the result line.  --full adds what takes
+runs of its own, after the timed region unless noted: the CPU baseline (rank 0), the live PMC
+passes on rank 0's GPU (a frame of the per-GPU workload alone), the isolated launch, further
+counting passes (--stats-reps) and, before timing at N > 1, the bit-exact check step; without
+it those fields of the line are null.  --dump-outputs DIR writes the frames the last timed
+step returned to its caller (rank 0's assembled rgba8 frames) as DIR/frame<id>_rgba8.npy.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene sponza|bunny|cornell] [--full]
+                  [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -99,7 +107,20 @@ def parse():
     p.add_argument("--check", default="auto", choices=["auto", "on", "off"],
                    help="one untimed step before timing whose gathered frames rank 0 compares bit for bit with "
                         "single-launch renders of the same seeds (auto: on when N > 1)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the live PMC passes, "
+                        "the isolated launch, --stats-reps counting passes and the N > 1 check step "
+                        "(--no-cpu-baseline, --pmc, --check and --stats-reps choose among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the frames the last timed step returned (rank 0) as "
+                        "DIR/frame<id>_rgba8.npy: float32 (H, W, 4), or a fixed seeded sample of their pixels "
+                        "where the frames together exceed DUMP_LIMIT_BYTES")
+    args = p.parse_args()
+    if not args.full and (args.pmc == "on" or args.check == "on"):
+        p.error("--pmc on and --check on need --full")
+    if args.dump_outputs and args.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",), ("TCC_HIT_sum", "TCC_MISS_sum"),
@@ -214,6 +235,25 @@ def live_pmc(args, kernel, grid_waves=None, local=0):
         f"live: {len(PMC_PASSES)} rocprofv3 --pmc passes of one frame of this workload alone, this run"
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # all files of --dump-outputs together
+
+
+def dump_outputs(d, frames):
+    """Write what a timed step returns to its caller, {frame id: (H, W, 4) rgba8 tensor}, as
+    d/frame<id>_rgba8.npy in float32 (exact for 8-bit values).  Frames that together exceed
+    DUMP_LIMIT_BYTES are cut to a sample of their pixels, (n, 4) rows in ascending row-major pixel
+    order, drawn without replacement by a generator seeded with the frame id: the same pixels in
+    every run of the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    per = DUMP_LIMIT_BYTES // (4 * max(len(frames), 1))  # float32 elements per frame
+    for fid, t in sorted(frames.items()):
+        a = t.cpu().numpy().astype(np.float32)
+        if a.size > per:
+            px = np.random.default_rng(fid).choice(a.shape[0] * a.shape[1], per // a.shape[2], replace=False)
+            a = a.reshape(-1, a.shape[2])[np.sort(px)]
+        np.save(os.path.join(d, f"frame{fid}_rgba8.npy"), a)
+
+
 def build_scene(w, kind):
     if kind == "cornell":
         L, Q, S = w.cornell_scene()
@@ -234,7 +274,7 @@ def cpu_baseline(args, scene, rank, world):
     """The oracle (CPU port, OpenMP) on a bounded row sample of the same workload,
     timed with its x86-64-v3 build (oracle/Makefile: liboracle_v3.so), which is first
     checked bit for bit against the reference build liboracle.so on a small tile."""
-    if rank != 0 or args.no_cpu_baseline:
+    if rank != 0 or args.no_cpu_baseline or not args.full:
         return None
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import pyoracle as po
@@ -323,8 +363,8 @@ def main():
 
     # instrumented passes (untimed): exact ray/sample counts for this rank's tiles.  The
     # node / triangle counts depend slightly on the schedule (which lanes run the
-    # speculative second leaf of a step), so the spread over the passes is reported
-    sts = [shard.stats() for _ in range(max(args.stats_reps, 1))]
+    # speculative second leaf of a step), so --full reports the spread over --stats-reps passes
+    sts = [shard.stats() for _ in range(max(args.stats_reps, 1) if args.full else 1)]
     st = sts[0]
 
     # real (non-NULL) streams: a step's launch, its events and its gather are ordered on
@@ -355,10 +395,10 @@ def main():
 
     for k in range(args.warmup):
         step(k, None)
-    # untimed check step (default with N > 1): the frames rank 0 gathered over the
+    # untimed check step (--full; default with N > 1): the frames rank 0 gathered over the
     # collective equal single-launch renders of the same seeds on rank 0's GPU
     check = None
-    if args.check == "on" or (args.check == "auto" and world > 1):
+    if args.full and (args.check == "on" or (args.check == "auto" and world > 1)):
         got = step(0, None)
         torch.cuda.synchronize()
         if rank == 0:
@@ -379,6 +419,8 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)  # views of the last step's output set: before any further launch
     # per-launch time: serial steps, the event pair around each launch; pipelined, the span
     # from the first launch's start (on an idle device: the region starts synchronised) to the
     # last launch's end over K launches.  An event pair would also count the time a launch
@@ -392,9 +434,9 @@ def main():
         kern_ms = evs[0][0].elapsed_time(evs[-1][1]) / args.steps
     else:
         kern_ms = float(np.mean(spans)) if args.steps else 0.0
-    # one more launch alone on an idle device (untimed): the single-frame latency
+    # --full: one more launch alone on an idle device (untimed): the single-frame latency
     iso = None
-    if P > 1:
+    if P > 1 and args.full:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(streams[0]):
@@ -464,9 +506,9 @@ def main():
                           "calibration": os.path.relpath(L2_CALIB_JSON, ROOT)}
         except (OSError, ValueError, KeyError):
             pass
-        # live PMC passes of this binary on this device (N = 1), in place of the profile entry
+        # --full: live PMC passes of this binary on this device (N = 1), in place of the profile entry
         traffic_source = "profile" if traffic is not None else None
-        if args.pmc == "on" or (args.pmc == "auto" and args.steps > 0):
+        if args.full and (args.pmc == "on" or (args.pmc == "auto" and args.steps > 0)):
             # the child renders one whole W x H frame at N = 1: its persistent grid is the device's
             # resident capacity or one wave per 8x8 pixel block, whichever is smaller
             res = int(info.get("ps_resident", 0))
@@ -502,6 +544,7 @@ def main():
             "ms_per_step": round(max_t / max(args.steps, 1) * 1e3, 3),
             "higher_is_better": True,
             "scaling": args.scaling,
+            "full": args.full,
             "vs_baseline": None,
             "dtype": "f32",
             "data": f"synthetic: procedural {args.scene} stand-in ({n_tris} tris) in the reference Cornell box"
@@ -520,7 +563,9 @@ def main():
                        "launch_ms_is": "event pair around each launch" if P == 1 or args.steps < 2 else
                        "span from the first launch's start to the last launch's end / K (HIP events; "
                        f"{P} frames in flight on the context's pipeline streams)",
-                       "isolated_launch_ms": round(iso, 3) if iso is not None else round(kern_ms, 3)},
+                       # serial steps: the event pair is a launch alone; pipelined: --full's extra launch
+                       "isolated_launch_ms": round(iso, 3) if iso is not None else
+                       round(kern_ms, 3) if P == 1 else None},
             "simt_utilisation": {k: round(v, 4) for k, v in simt.items()},
             "per_launch": {"traced_rays": int(mine[1]), "node_visits": int(mine[4]), "tri_tests": int(mine[5]),
                            "algorithmic_bytes": int(survey_bytes), "loaded_bytes": int(bytes_launch),
@@ -573,7 +618,8 @@ def main():
                                 "traced_rays": [int(x) for x in allv[:, 1]],
                                 "algorithmic_bytes": [int(x) for x in rk_bytes],"kernel_ms": [round(float(x), 3) for x in allv[:, 6]],
                                 "gather_ms": [round(float(x), 3) for x in allv[:, 7]],
-                                "isolated_launch_ms": [round(float(x), 3) for x in allv[:, 8]],
+                                "isolated_launch_ms": [round(float(x), 3) for x in allv[:, 8]]
+                                if args.full or P == 1 else None,
                                 "kernel_ms_min_max": [round(float(allv[:, 6].min()), 3),
                                                       round(float(allv[:, 6].max()), 3)],
                                 "gather_ms_min_max": [round(float(allv[:, 7].min()), 3),

@@ -8,7 +8,7 @@ TAG=${1:-prof}; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 BARGS="$@"
-echo "== bench"; timeout -k 10 600 python bench.py --steps 3 --warmup 1 $BARGS > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
+echo "== bench"; timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 $BARGS > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log
 echo "== kernel trace"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline $BARGS > $OUT/kt.log 2>&1 || { echo "kt failed"; tail -20 $OUT/kt.log; exit 1; }

@@ -18,7 +18,7 @@ for r in $(seq $R); do
     n=$(basename $so .so)
     for sc in ${SCENES:-sponza bunny}; do
       st=${STEPS:-12}; [ $sc = bunny ] && st=$((st + 8))
-      WGT_LIB_PATH=$PWD/$so timeout -k 10 400 python bench.py --scene $sc --steps $st --warmup 3 --pmc off \
+      WGT_LIB_PATH=$PWD/$so timeout -k 10 400 python bench.py --full --scene $sc --steps $st --warmup 3 --pmc off \
         --no-cpu-baseline --stats-reps 1 > $O/bench_${n}_${sc}_$r.log 2>&1 || { tail -20 $O/bench_${n}_${sc}_$r.log; exit 1; }
       echo "$n $sc r$r: $(tail -1 $O/bench_${n}_${sc}_$r.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['kernel_ms'], d['timing']['isolated_launch_ms'])")"
     done

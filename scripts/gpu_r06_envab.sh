@@ -15,7 +15,7 @@ for r in $(seq $R); do
     if [ $v = A ]; then E="$ENV_A"; else E="$ENV_B"; fi
     for sc in ${SCENES:-sponza bunny}; do
       st=${STEPS:-12}; [ $sc = bunny ] && st=$((st + 8))
-      env $E timeout -k 10 400 python bench.py --scene $sc --steps $st --warmup 3 --pmc off \
+      env $E timeout -k 10 400 python bench.py --full --scene $sc --steps $st --warmup 3 --pmc off \
         --no-cpu-baseline --stats-reps 1 > $O/bench_${v}_${sc}_$r.log 2>&1 || { tail -20 $O/bench_${v}_${sc}_$r.log; exit 1; }
       echo "$v($E) $sc r$r: $(tail -1 $O/bench_${v}_${sc}_$r.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['kernel_ms'], d['timing']['isolated_launch_ms'])")"
     done

@@ -61,3 +61,22 @@ def test_node_form_from_scene_info():
     """The node form comes from the library's scene_info (0 = 128-B nodes, 1 = 80-B compact)."""
     assert bench.node_form({"node_form": 1, "ps_waves": 6}) == 1
     assert bench.node_form({"node_form": 0, "ps_waves": 5}) == 0
+
+
+def test_bench_dump_sample_is_fixed(tmp_path, monkeypatch):
+    """Frames over the dump's size limit are cut to the same sorted pixel sample in every call
+    (bench.dump_outputs; no bench run): rows of the frame at those pixels, within the limit."""
+    import numpy as np
+    import torch
+
+    H, W = 48, 40
+    rng = np.random.default_rng(1)
+    frames = {f: torch.from_numpy(rng.integers(0, 256, (H, W, 4), dtype=np.uint8)) for f in (0, 1)}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4 * 4 * 500)  # 500 of each frame's 1920 pixels
+    bench.dump_outputs(str(tmp_path / "a"), frames)
+    bench.dump_outputs(str(tmp_path / "b"), frames)
+    for f in (0, 1):
+        a, b = np.load(tmp_path / "a" / f"frame{f}_rgba8.npy"), np.load(tmp_path / "b" / f"frame{f}_rgba8.npy")
+        assert a.dtype == np.float32 and a.shape == (500, 4) and np.array_equal(a, b)
+        px = np.sort(np.random.default_rng(f).choice(H * W, 500, replace=False))
+        assert np.array_equal(a, frames[f].numpy().reshape(-1, 4)[px].astype(np.float32))

@@ -257,7 +257,7 @@ def test_frames_launcher_two_ranks_union(tmp_path, wgt):
 
 
 def test_bench_two_ranks_self_checks(tmp_path):
-    """bench.py at N = 2 (torch.distributed.run, gloo, both ranks on cuda:0) runs its
+    """bench.py --full at N = 2 (torch.distributed.run, gloo, both ranks on cuda:0) runs its
     untimed check step without being asked: the line carries check_frames_bit_exact =
     true, i.e. the frames gathered over the collective equal single-launch renders."""
     import json
@@ -265,7 +265,7 @@ def test_bench_two_ranks_self_checks(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
            "--dist-backend", "gloo", "--scene", "bunny", "--width", "96", "--height", "64", "--spp", "4",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--stats-reps", "1"]
+           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--stats-reps", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -280,7 +280,7 @@ def test_bench_two_ranks_self_checks(tmp_path):
 
 
 def test_bench_four_ranks_full_line(tmp_path):
-    """bench.py at N = 4 (torch.distributed.run, gloo, all ranks on cuda:0) at 1080p with a reduced
+    """bench.py --full at N = 4 (torch.distributed.run, gloo, all ranks on cuda:0) at 1080p with a reduced
     spp: the line the driver's scaling run reads carries every field of the N = 1 line — the
     self-check (check_frames_bit_exact), the roofline with traffic from rank 0's live rocprofv3
     --pmc passes, the CPU baseline timed once on rank 0 — plus per_rank: each rank's launch and
@@ -291,7 +291,7 @@ def test_bench_four_ranks_full_line(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "4",
            "--dist-backend", "gloo", "--scene", "bunny", "--spp", "4", "--steps", "2", "--warmup", "1",
-           "--cpu-rows", "2", "--stats-reps", "1", "--pmc", "on"]
+           "--cpu-rows", "2", "--stats-reps", "1", "--pmc", "on", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -320,14 +320,14 @@ def test_bench_four_ranks_full_line(tmp_path):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py at N = 1 on a small workload prints one JSON line with every field of the driver's
+    """bench.py --full at N = 1 on a small workload prints one JSON line with every field of the driver's
     contract: throughput, timing, roofline (bound, achieved, peak, frac, traffic measured by the
     run's own rocprofv3 --pmc passes) and the CPU baseline (value, unit, cores, kind, sample),
     plus the build id."""
     import json
 
     cmd = [sys.executable, "bench.py", "--scene", "bunny", "--width", "96", "--height", "64", "--spp", "4",
-           "--steps", "2", "--warmup", "1", "--cpu-rows", "2", "--stats-reps", "1"]
+           "--steps", "2", "--warmup", "1", "--cpu-rows", "2", "--stats-reps", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -363,6 +363,39 @@ def test_bench_line_contract(tmp_path):
     assert rf["l2"]["requests_per_launch"] > 0 and 0.0 <= rf["l2"]["hit_rate"] <= 1.0
     cb = line["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] == "port" and cb["sample"]
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path, ctx, wgt):
+    """A plain bench.py run (no --full) times its steps and prints the headline fields, with what
+    takes runs of its own left null (CPU baseline, live traffic, isolated launch, check step);
+    --dump-outputs writes the last timed step's frame as float32, equal to a single render_tile of
+    the same scene, camera and seed (the inputs are the same in every run)."""
+    import json
+
+    W, H, spp = 96, 64, 4
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--scene", "bunny", "--width", str(W), "--height", str(H),
+           "--spp", str(spp), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] and line["unit"] == "Mrays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    # value = traced rays of the timed steps / their wall time (ms_per_step is rounded to 1 us)
+    assert line["value"] == pytest.approx(
+        line["per_launch"]["traced_rays"] / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3 + 6e-4 / line["ms_per_step"])
+    assert line["cpu_baseline"] is None and "check_frames_bit_exact" not in line
+    assert line["roofline"]["traffic_source"] is None and line["timing"]["isolated_launch_ms"] is None
+    assert line["roofline"]["count_spread"]["passes"] == 1
+    assert sorted(p.name for p in out.iterdir()) == ["frame0_rgba8.npy"]
+    got = np.load(out / "frame0_rgba8.npy")
+    assert got.dtype == np.float32 and got.shape == (H, W, 4)
+    ctx.upload_scene(*wgt.mesh_scene("bunny"))
+    ref = ctx.render_tile(wgt.camera_param(W / H, spp, 0), W, H, want=("u8",))["u8"]
+    assert np.array_equal(got, ref.astype(np.float32))
 
 
 _RCCL_ONE_RANK = r"""
