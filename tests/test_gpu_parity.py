@@ -411,6 +411,21 @@ def test_stack_overflow_spill_and_refill(ctx, wgt, oracle, bunny, cap, cnode, mo
     assert g["stats"]["stack_spills"] > 0 and g["stats"]["stack_refills"] > 0
 
 
+@pytest.mark.parametrize("env", [{}, {"WGT_PARK": "1"}, {"WGT_PS_WAVES": "5"}, {"WGT_PARK": "1", "WGT_PS_CAP": "8"}])
+def test_scene_info_agrees_with_bvh_build(ctx, wgt, bunny, env, monkeypatch):
+    """The host-only report (bvh_build) and the uploaded scene's (scene_info) state the same tree
+    and the same k_render_ps form (wgt_runtime.cpp ps_form_for, fill_bvh_info), under the knobs
+    that select each form."""
+    (L, Q, S, T), _ = bunny
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    ctx.upload_scene(L, Q, S, T)
+    up = ctx.scene_info()
+    host, _, _ = wgt.bvh_build(T)
+    for key in ("ps_waves", "ps_park", "ps_stack", "bvh_stack", "bvh_nodes", "bvh_width"):
+        assert up[key] == host[key], (key, up[key], host[key])
+
+
 def test_mesh_tiles_reassemble_full_frame(ctx, wgt, bunny):
     """Ragged tiles (not multiples of the 8x8 pixel blocks) through the persistent
     kernel reproduce the full frame bit for bit."""

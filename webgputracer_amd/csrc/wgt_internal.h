@@ -33,9 +33,59 @@ constexpr int kStackMax = 31;
 constexpr int kStackNarrow = 25;
 // k_render_ps on scenes without triangles (no traversal, no stack): its register budget
 constexpr int kPsWavesNoTris = 8;
-static_assert((kStackMax + 1) * kBlock * 4 * 5 * 4 <= 160 * 1024, "5 waves per SIMD");
-static_assert((kStackNarrow + 1) * kBlock * 4 * 6 * 4 <= 160 * 1024, "6 waves per SIMD");
-static_assert((kStackMax + 1) * kBlock * 3 * 6 * 4 <= 160 * 1024, "6 waves per SIMD, 3-byte entries");
+constexpr uint32_t kStack24Nodes = 1u << 16;  // 128-B node byte offsets < 2^23
+constexpr uint32_t kStack24Tris = 1u << 20;   // leaf refs ~(first << 3 | count - 1) >= -2^23
+// Parked traversal state per lane (wgt_device.h Park): 1/d (3), slab offsets (3), best t,
+// best index, node ref, stack top | global depth << 16, open leaf (offset | count)
+constexpr uint32_t kParkWords = 11;
+// The smallest LDS stack the parked kernel runs with: a node step needs 4 free entries
+// above the top (3 pushes and a parked leaf), and a ray's root step, which pushes at most
+// 4, must leave its top within that bound (top <= cap - 4), so a new ray never starts
+// past it
+constexpr uint32_t kMinPsCap = 8;
+
+// Dynamic LDS bytes of a traversal kernel launch (k_render, k_trace: 4-byte entries).
+constexpr size_t stack_lds_bytes(uint32_t stack) { return (size_t)stack * kBlock * sizeof(int); }
+
+// The launch form of k_render_ps for a scene (ps_form): with the frame's node form (node_form)
+// it names the instantiation (ps_kernel), and it alone fixes the launch's dynamic LDS (ps_lds).
+struct PsForm {
+  bool tris;       // the scene has triangles (else no traversal phase, at kPsWavesNoTris)
+  uint32_t waves;  // per SIMD (DevScene::ps_waves)
+  bool park;       // parked traversal state (DevScene::ps_park)
+  uint32_t cap;    // LDS stack entries per lane: DevScene::ps_cap when parked, else the whole stack
+  // the phase-threshold defaults (DevFrame::ps_to_trav, ps_to_service), swept per wave budget
+  // (profiles/sweeps/r01_sweep_compact_knobs.jsonl)
+  constexpr uint32_t to_trav() const { return waves >= 6 ? 16u : 18u; }
+  constexpr uint32_t to_service() const { return waves >= 6 ? 14u : 16u; }
+};
+// The dynamic LDS of one wave of k_render_ps, in bytes: f.cap stack entries per lane of `entry`
+// bytes (3 at 6 or more waves per SIMD, Stack24: the 16-bit array, then the high bytes at `hi`;
+// else 4, Stack32), then at `park` the lanes' kParkWords words when the form parks.  The launch,
+// the occupancy query (ps_resident_waves) and the kernel's carve-up all read this one statement.
+struct PsLds {
+  uint32_t entry, hi, park, total;
+};
+constexpr PsLds ps_lds(const PsForm& f) {
+  const uint32_t entry = f.waves >= 6 ? 3u : 4u, stack = f.cap * kBlock * entry;
+  return PsLds{entry, f.cap * kBlock * 2u, stack, stack + (f.park ? kParkWords * kBlock * 4u : 0u)};
+}
+constexpr size_t kLdsPerCu = 160 * 1024;
+static_assert(ps_lds({true, 5, false, kStackMax + 1}).total * 5 * 4 <= kLdsPerCu, "5 waves per SIMD");
+static_assert(stack_lds_bytes(kStackNarrow + 1) * 6 * 4 <= kLdsPerCu, "6 waves per SIMD");
+static_assert(ps_lds({true, 6, false, kStackMax + 1}).total * 6 * 4 <= kLdsPerCu, "6 waves per SIMD, 3-byte entries");
+// LDS entries the parked kernel can hold at its wave budget: the stack and the parked words
+// of 4 * waves one-wave workgroups per CU within kPsLdsPerCu.  Measured (profiles/r04/
+// lds_sweep_*.jsonl): 24 workgroups per CU run at full speed with 6,272 B each and lose 8-20 %
+// from 6,464 B on, although the occupancy API still reports 24 (and 160 KiB would hold 24 of
+// 6,656 B): the usable budget lies between 24 x 6,400 and 24 x 6,656 B, so 150 KiB is taken
+constexpr size_t kPsLdsPerCu = 150 * 1024;
+constexpr uint32_t ps_cap_max(uint32_t waves) {
+  const PsLds none = ps_lds({true, waves, true, 0});  // the parked words alone
+  return (uint32_t)((kPsLdsPerCu / (4 * waves) - none.total) / (kBlock * none.entry));
+}
+static_assert(ps_cap_max(6) == 18, "6 waves: 18 entries of 3 B beside the 11 parked words");
+static_assert(ps_cap_max(5) == 19, "5 waves: 19 entries of 4 B");
 
 struct DevScene {
   const float4* __restrict__ quads;   // n_lights + n_quads records
@@ -64,35 +114,8 @@ struct DevScene {
   // (DevFrame::ps_spill) in the service phase.  ps_park = 0: the whole stack in LDS.
   uint32_t ps_park, ps_cap;
 };
-constexpr uint32_t kStack24Nodes = 1u << 16;  // 128-B node byte offsets < 2^23
-constexpr uint32_t kStack24Tris = 1u << 20;   // leaf refs ~(first << 3 | count - 1) >= -2^23
-// Parked traversal state per lane (wgt_device.h Park): 1/d (3), slab offsets (3), best t,
-// best index, node ref, stack top | global depth << 16, open leaf (offset | count)
-constexpr uint32_t kParkWords = 11;
-// The smallest LDS stack the parked kernel runs with: a node step needs 4 free entries
-// above the top (3 pushes and a parked leaf), and a ray's root step, which pushes at most
-// 4, must leave its top within that bound (top <= cap - 4), so a new ray never starts
-// past it
-constexpr uint32_t kMinPsCap = 8;
-// Dynamic LDS bytes of a traversal kernel launch (4-byte entries).
-inline size_t stack_lds_bytes(const DevScene& sc) { return (size_t)sc.stack * kBlock * sizeof(int); }
-// ... of a k_render_ps launch: 3-byte entries at 6 waves per SIMD, ps_cap entries and
-// the parked state when ps_park
-inline size_t ps_stack_lds_bytes(const DevScene& sc) {
-  const size_t entry = sc.ps_waves >= 6 ? 3 : sizeof(int);
-  if (sc.ps_park) return (size_t)sc.ps_cap * kBlock * entry + (size_t)kParkWords * kBlock * 4;
-  return (size_t)sc.stack * kBlock * entry;
-}
-// LDS entries the parked kernel can hold at its wave budget: the stack and the parked words
-// of 4 * waves one-wave workgroups per CU within kPsLdsPerCu.  Measured (profiles/r04/
-// lds_sweep_*.jsonl): 24 workgroups per CU run at full speed with 6,272 B each and lose 8-20 %
-// from 6,464 B on, although the occupancy API still reports 24 (and 160 KiB would hold 24 of
-// 6,656 B): the usable budget lies between 24 x 6,400 and 24 x 6,656 B, so 150 KiB is taken
-// (6 waves: 18 entries of 3 B beside the 11 parked words; 5 waves: 19 of 4 B)
-constexpr size_t kPsLdsPerCu = 150 * 1024;
-inline uint32_t ps_cap_max(uint32_t waves) {
-  const size_t per_wave = kPsLdsPerCu / (4 * waves), entry = waves >= 6 ? 3 : 4;
-  return (uint32_t)((per_wave - (size_t)kParkWords * kBlock * 4) / (kBlock * entry));
+inline PsForm ps_form(const DevScene& sc) {
+  return PsForm{sc.n_tris > 0, sc.ps_waves, sc.ps_park != 0, sc.ps_park ? sc.ps_cap : sc.stack};
 }
 
 // 1 / spp when spp is a power of two (exact in fp32: end_sample multiplies), else 0

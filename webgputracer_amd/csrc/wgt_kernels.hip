@@ -120,9 +120,13 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
   // spill: the global stacks (PK, DevFrame::ps_spill), a kernel argument of its own: a
   // noalias pointer, so its stores do not clobber the scene for the compiler, whose
   // wave-uniform loads (quads, spheres, the root node) stay scalar loads
-  extern __shared__ int s_stack[];  // stack entries per lane (+ parked words), ps_stack_lds_bytes
+  extern __shared__ int s_stack[];  // stack entries per lane (+ parked words), ps_lds
+  // the layout's byte offsets per stack entry (it is linear in cap): the carve-up below scales
+  // them in typed pointer arithmetic (ps_lds's byte sums at a run-time cap compile to other
+  // code in the parked kernels)
+  constexpr PsLds row = ps_lds({TRIS, W, PK, 1});
   // 6 waves per SIMD: 3-byte entries (DevScene::ps_waves guarantees the refs fit)
-  using STK = typename std::conditional<W >= 6, Stack24, Stack32>::type;
+  using STK = typename std::conditional<row.entry == 3, Stack24, Stack32>::type;
   const uint32_t cap = PK ? sc.ps_cap : sc.stack;  // LDS stack entries per lane
   // PK: the highest stack top a node step may start from, cap - 4 (3 pushes and a parked
   // leaf above it); no bound when the LDS holds the builder's whole stack (cap = sc.stack),
@@ -130,13 +134,13 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
   const uint32_t top_max = PK && cap < sc.stack ? cap - 4u : 0xffffffffu;
   STK lds;
   Park P;
-  if constexpr (W >= 6) {
+  if constexpr (row.entry == 3) {
     lds.lo = (uint16_t*)s_stack + threadIdx.x;
-    lds.hi = (int8_t*)((uint16_t*)s_stack + cap * kBlock) + threadIdx.x;
-    P.p = (uint32_t*)((char*)s_stack + cap * kBlock * 3) + threadIdx.x;
+    lds.hi = (int8_t*)((uint16_t*)s_stack + cap * (row.hi / 2)) + threadIdx.x;
+    P.p = (uint32_t*)((char*)s_stack + cap * row.park) + threadIdx.x;
   } else {
     lds.p = s_stack + threadIdx.x;
-    P.p = (uint32_t*)(s_stack + cap * kBlock) + threadIdx.x;
+    P.p = (uint32_t*)(s_stack + cap * (row.park / 4)) + threadIdx.x;
   }
   const uint32_t lane = threadIdx.x;
   const Light L{xyz(sc.quads[0]), xyz(sc.quads[1]), xyz(sc.quads[2])};
@@ -553,32 +557,20 @@ hipError_t launch_selftest_math(uint32_t n, uint32_t seed, unsigned long long* d
   return hipGetLastError();
 }
 
-// k_render_ps at the scene's waves per SIMD (6 with 3-byte stack entries, else 5), the frame's node
-// form (node_form: 0 = 128-B nodes, 1 = 80-B compact records) and the scene's traversal state (parked
-// in LDS during service passes, or not: DevScene::ps_park).  Scenes without triangles run the
-// traversal-free instantiation.
-template <bool STATS, bool COST, int CN, int W>
-void ps_launch_w(const DevScene& sc, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const DevFrame& f,
-                 const wgt_tile* tiles, uchar4* out8, float4* out32, uint32_t* outhit, unsigned long long* counters,
-                 uint32_t* queue) {
-  if (sc.ps_park)
-    k_render_ps<STATS, COST, CN, W, true, true><<<grid, block, lds, stream>>>(sc, f, tiles, out8, out32, outhit, counters, queue, f.ps_spill);
-  else
-    k_render_ps<STATS, COST, CN, W, true, false><<<grid, block, lds, stream>>>(sc, f, tiles, out8, out32, outhit, counters, queue, f.ps_spill);
-}
+// The k_render_ps instantiation of a pass (STATS: counting, COST: the pre-pass) for the scene's
+// form and the frame's node form (node_form: 0 = 128-B nodes, 1 = 80-B compact records): the one
+// place that names them.  Scenes without triangles run the traversal-free instantiation.
+using PsKernel = void (*)(DevScene, DevFrame, const wgt_tile*, uchar4*, float4*, uint32_t*, unsigned long long*,
+                          uint32_t*, int*);
 template <bool STATS, bool COST>
-void ps_launch(const DevScene& sc, int cn, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const DevFrame& f,
-               const wgt_tile* tiles, uchar4* out8, float4* out32, uint32_t* outhit, unsigned long long* counters,
-               uint32_t* queue) {
-  if (sc.n_tris == 0) {
-    k_render_ps<STATS, COST, 0, kPsWavesNoTris, false><<<grid, block, lds, stream>>>(sc, f, tiles, out8, out32, outhit, counters, queue, f.ps_spill);
-  } else if (sc.ps_waves == 6) {
-    if (cn) ps_launch_w<STATS, COST, 1, 6>(sc, grid, block, lds, stream, f, tiles, out8, out32, outhit, counters, queue);
-    else ps_launch_w<STATS, COST, 0, 6>(sc, grid, block, lds, stream, f, tiles, out8, out32, outhit, counters, queue);
-  } else {
-    if (cn) ps_launch_w<STATS, COST, 1, 5>(sc, grid, block, lds, stream, f, tiles, out8, out32, outhit, counters, queue);
-    else ps_launch_w<STATS, COST, 0, 5>(sc, grid, block, lds, stream, f, tiles, out8, out32, outhit, counters, queue);
-  }
+PsKernel ps_kernel(const PsForm& f, int cn) {
+  if (!f.tris) return k_render_ps<STATS, COST, 0, kPsWavesNoTris, false>;
+  static constexpr PsKernel k[2][2][2] = {  // [6 waves][parked][compact]
+      {{k_render_ps<STATS, COST, 0, 5, true, false>, k_render_ps<STATS, COST, 1, 5, true, false>},
+       {k_render_ps<STATS, COST, 0, 5, true, true>, k_render_ps<STATS, COST, 1, 5, true, true>}},
+      {{k_render_ps<STATS, COST, 0, 6, true, false>, k_render_ps<STATS, COST, 1, 6, true, false>},
+       {k_render_ps<STATS, COST, 0, 6, true, true>, k_render_ps<STATS, COST, 1, 6, true, true>}}};
+  return k[f.waves == 6][f.park][cn != 0];
 }
 
 // The compact codes are exact for ray origins within their bound (the margin, wgt_geom.h):
@@ -618,10 +610,11 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
   fm.div_bx = 0xffffffffu / bx;
   fm.div_bpt = 0xffffffffu / (bx * by);
   const dim3 block(kBlock);
-  const size_t lds = stack_lds_bytes(sc);
+  const size_t lds = stack_lds_bytes(sc.stack);
   const bool tris = sc.n_tris > 0;
   if (fr.kernel == 2) {
-    const size_t plds = ps_stack_lds_bytes(sc);
+    const PsForm form = ps_form(sc);
+    const size_t plds = ps_lds(form).total;
     if (blocks * 64ull > 0xffffffffull || resident == 0) return hipErrorInvalidValue;
     if (!ws || ws_cap < render_ws_bytes(sc, fr, resident)) return hipErrorInvalidValue;
     const uint32_t nb = (uint32_t)blocks;
@@ -632,9 +625,8 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
     const int cn = node_form(sc, fr);
     uint32_t* q = (uint32_t*)ws;
     DevFrame f = fm;
-    // phase thresholds swept per wave budget (profiles/sweeps/r01_sweep_compact_knobs.jsonl)
-    if (f.ps_to_trav == 0) f.ps_to_trav = sc.ps_waves >= 6 ? 16u : 18u;
-    if (f.ps_to_service == 0) f.ps_to_service = sc.ps_waves >= 6 ? 14u : 16u;
+    if (f.ps_to_trav == 0) f.ps_to_trav = form.to_trav();
+    if (f.ps_to_service == 0) f.ps_to_service = form.to_service();
     if (f.pq_refill == 0) f.pq_refill = 2u;
     f.n_slots = nb * 64u;
     f.perm = nullptr;
@@ -655,14 +647,14 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
       fc.inv_fspp = pow2_recip(fc.sqrt_spp * fc.sqrt_spp);
       fc.cost = (uint32_t*)((char*)ws + 256);
       fc.n_slots = nb * (fr.pq_lpt_all ? 64u : 16u);  // by default a quarter of each block's pixels estimate its cost
-      ps_launch<false, true>(sc, cn, grid, block, plds, stream, fc, d_tiles, nullptr, nullptr, nullptr, nullptr, q);
+      ps_kernel<false, true>(form, cn)<<<grid, block, plds, stream>>>(sc, fc, d_tiles, nullptr, nullptr, nullptr, nullptr, q, fc.ps_spill);
       k_lpt_order<<<1, kLptThreads, 0, stream>>>(fc.cost, nb, fc.cost + nb, q);
       f.perm = fc.cost + nb;
       e = hipGetLastError();
     }
     if (e == hipSuccess) {
-      if (counters) ps_launch<true, false>(sc, cn, grid, block, plds, stream, f, d_tiles, out8, out32, outhit, counters, q + 1);
-      else ps_launch<false, false>(sc, cn, grid, block, plds, stream, f, d_tiles, out8, out32, outhit, nullptr, q + 1);
+      const PsKernel k = counters ? ps_kernel<true, false>(form, cn) : ps_kernel<false, false>(form, cn);
+      k<<<grid, block, plds, stream>>>(sc, f, d_tiles, out8, out32, outhit, counters, q + 1, f.ps_spill);
       e = hipGetLastError();
     }
     // after an LPT launch k_lpt_order has left the queues and nb costs zero for the next one
@@ -680,32 +672,17 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
   return hipGetLastError();
 }
 
-// k_render_ps<STATS = false, COST = false, CN, W, true, PK> of a launchable form
-template <int W, bool PK>
-const void* ps_kernel(int cn) {
-  return cn ? reinterpret_cast<const void*>(&k_render_ps<false, false, 1, W, true, PK>)
-            : reinterpret_cast<const void*>(&k_render_ps<false, false, 0, W, true, PK>);
-}
-
 // The persistent grid: the smaller resident capacity of the two node forms the scene's launches can
-// read (node_form), so that every wave of a launch is resident from its start.
+// read (node_form), at the launch's LDS bytes, so that every wave of a launch is resident from its start.
 hipError_t ps_resident_waves(const DevScene& sc, int device, uint32_t& waves) {
-  int per_cu = 0, cus = 0;
-  if (sc.n_tris == 0) {
+  const PsForm form = ps_form(sc);
+  int per_cu = 1 << 30, cus = 0;
+  for (int cn = 0; cn < 2; ++cn) {
+    int n = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, reinterpret_cast<const void*>(&k_render_ps<false, false, 0, kPsWavesNoTris, false>), kBlock,
-        stack_lds_bytes(sc));
+        &n, reinterpret_cast<const void*>(ps_kernel<false, false>(form, cn)), kBlock, ps_lds(form).total);
     if (e != hipSuccess) return e;
-  } else {
-    per_cu = 1 << 30;
-    for (int cn = 0; cn < 2; ++cn) {
-      const void* k = sc.ps_waves == 6 ? (sc.ps_park ? ps_kernel<6, true>(cn) : ps_kernel<6, false>(cn))
-                                       : (sc.ps_park ? ps_kernel<5, true>(cn) : ps_kernel<5, false>(cn));
-      int n = 0;
-      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kBlock, ps_stack_lds_bytes(sc));
-      if (e != hipSuccess) return e;
-      per_cu = n < per_cu ? n : per_cu;
-    }
+    per_cu = n < per_cu ? n : per_cu;
   }
   const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   if (e != hipSuccess) return e;
@@ -717,8 +694,8 @@ hipError_t launch_trace(const DevScene& sc, const float* d_rays, uint32_t n, uin
                         float* dist, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-  if (sc.n_tris > 0) k_trace<true><<<grid, block, stack_lds_bytes(sc), stream>>>(sc, d_rays, n, prim, dist);
-  else k_trace<false><<<grid, block, stack_lds_bytes(sc), stream>>>(sc, d_rays, n, prim, dist);
+  if (sc.n_tris > 0) k_trace<true><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, n, prim, dist);
+  else k_trace<false><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, n, prim, dist);
   return hipGetLastError();
 }
 

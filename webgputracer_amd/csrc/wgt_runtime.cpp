@@ -135,8 +135,6 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
   return (uint32_t)std::strtoul(v, nullptr, 10);
 }
 
-// setup_camera_ray's frame-invariant terms (path_tracer.wgsl:239-257), same fp32
-// operations as the WGSL per-invocation evaluation.
 // The builder's stack bound (WGT_STACK_LIMIT overrides kStackMax for sweeps).
 uint32_t stack_limit() { return std::min(env_u32("WGT_STACK_LIMIT", (uint32_t)kStackMax), (uint32_t)kStackMax); }
 // The narrow collapse (a 25-entry stack bound), off by default since 3-byte stack
@@ -145,31 +143,59 @@ uint32_t stack_limit() { return std::min(env_u32("WGT_STACK_LIMIT", (uint32_t)kS
 // enough (sweeps).
 uint32_t narrow_limit() { return env_u32("WGT_NARROW", 0) ? (uint32_t)kStackNarrow : 0u; }
 double narrow_ratio() { return env_u32("WGT_NARROW", 0) == 2 ? 1e30 : kNarrowNodeRatio; }
-// k_render_ps waves per SIMD (DevScene::ps_waves): 6 with 3-byte stack entries when
-// every ref fits them, else 5; WGT_PS_WAVES=5 forces 5 (sweeps).
-uint32_t ps_waves_for(const BvhOut& bvh, uint32_t n_tris) {
-  // no triangles: the kernel without traversal (4-byte stack bytes in the launch and
-  // the occupancy query alike, ps_stack_lds_bytes)
-  if (n_tris == 0) return (uint32_t)kPsWavesNoTris;
-  if (env_u32("WGT_PS_WAVES", 0) == 5) return 5u;
-  const bool fits24 = bvh.n_nodes < kStack24Nodes && n_tris < kStack24Tris;
-  return fits24 ? 6u : 5u;
+// The build with the project's knobs, for ray origins within kOriginBoundScale x `extent`
+// (scene_extent)
+constexpr double kOriginBoundScale = 4.0;
+bool build_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh, std::string& err) {
+  return BuildBvh(tris, n_tris, (uint32_t)kMaxBvhDepth, stack_limit(), narrow_limit(), narrow_ratio(),
+                  kOriginBoundScale * extent, bvh, err);
 }
+// The traversal stack of the built tree, entries per lane (DevScene::stack): + 1, the
+// speculative traversal parks a second leaf on the stack (wgt_device.h)
+uint32_t stack_entries(const BvhOut& bvh) { return std::max(bvh.stack_need, 1u) + 1u; }
 
-// Parked traversal state of k_render_ps (opt-in: WGT_PARK=1; it
+// The k_render_ps form of a scene (PsForm).  Waves per SIMD: 6 with 3-byte stack entries when
+// every ref fits them, else 5; WGT_PS_WAVES=5 forces 5 (sweeps); without triangles the kernel
+// without traversal at its own budget (3-byte entries in the launch and the occupancy query
+// alike, ps_lds).  Parked traversal state (opt-in: WGT_PARK=1; it
 // removes the service phase's scratch stores but measured 5 % slower, profiles/r04/): the LDS
-// stack holds what fits beside the parked words at the wave budget,
-// or the whole stack (`stack` entries) when that is smaller; WGT_PS_CAP lowers it, down to
-// kMinPsCap, for tests.
-void ps_park_cap(uint32_t n_tris, uint32_t stack, uint32_t waves, uint32_t& park, uint32_t& cap) {
-  park = n_tris > 0 && env_u32("WGT_PARK", 0) ? 1u : 0u;
-  cap = stack;
-  if (!park) return;
-  uint32_t c = std::min(stack, ps_cap_max(waves));
-  c = std::min(c, std::max(env_u32("WGT_PS_CAP", c), kMinPsCap));
-  cap = std::max(c, kMinPsCap);
+// stack holds what fits beside the parked words at the wave budget, or the whole stack when
+// that is smaller; WGT_PS_CAP lowers it, down to kMinPsCap, for tests.
+PsForm ps_form_for(const BvhOut& bvh, uint32_t n_tris) {
+  PsForm f{n_tris > 0, (uint32_t)kPsWavesNoTris, false, stack_entries(bvh)};
+  if (!f.tris) return f;
+  const bool fits24 = bvh.n_nodes < kStack24Nodes && n_tris < kStack24Tris;
+  f.waves = fits24 && env_u32("WGT_PS_WAVES", 0) != 5 ? 6u : 5u;
+  f.park = env_u32("WGT_PARK", 0) != 0;
+  if (f.park) {
+    const uint32_t c = std::min(f.cap, ps_cap_max(f.waves));
+    f.cap = std::max(std::min(c, std::max(env_u32("WGT_PS_CAP", c), kMinPsCap)), kMinPsCap);
+  }
+  return f;
 }
 
+// The BVH and kernel-form fields of the scene report, of wgt_bvh_build and of an upload alike
+// (a scene without triangles reports zeros)
+void fill_bvh_info(const BvhOut& bvh, uint32_t n_tris, const PsForm& f, wgt_scene_info& in) {
+  in.n_tris = n_tris;
+  in.bvh_nodes = bvh.n_nodes;
+  in.bvh_leaves = bvh.n_leaves;
+  in.bvh_max_depth = bvh.max_depth;
+  in.bvh_max_leaf = bvh.max_leaf;
+  in.sah_cost = bvh.sah_cost;
+  in.bvh_width = f.tris ? (uint32_t)kBvhWidth : 0u;
+  in.bvh_stack = f.tris ? std::max(bvh.stack_need, 1u) : 0u;
+  in.bvh2_nodes = bvh.n_nodes2;
+  in.bvh2_depth = bvh.depth2;
+  in.bvh_compact = (size_t)bvh.n_nodes * kNode4Floats * 4 > kCompactNodeBytes ? 1u : 0u;
+  in.bvh_compact_step = bvh.cstep;
+  in.ps_waves = f.tris ? f.waves : 0u;
+  in.ps_park = f.park;
+  in.ps_stack = f.tris ? f.cap : 0u;
+}
+
+// setup_camera_ray's frame-invariant terms (path_tracer.wgsl:239-257), same fp32
+// operations as the WGSL per-invocation evaluation.
 DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
   DevFrame fr{};
   const float theta = radians_w(cam.fovy);
@@ -201,7 +227,7 @@ DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
   fr.kernel = env_u32("WGT_KERNEL", 2);
   // swept on the persistent BVH4 kernel with compact nodes (DESIGN.md §4.2,
   // profiles/sweeps/r01_sweep_compact_knobs.jsonl)
-  // 0 = by the kernel's waves per SIMD: 18/16 at 5, 16/14 at 6 (launch_render)
+  // 0 = by the kernel's waves per SIMD: 18/16 at 5, 16/14 at 6 (PsForm::to_trav, to_service)
   fr.ps_to_trav = env_u32("WGT_PS_TO_TRAV", 0);
   fr.ps_to_service = env_u32("WGT_PS_TO_SERVICE", 0);
   fr.ps_svc_frac = env_u32("WGT_PS_SVC_FRAC", 16);  // sweep: profiles/sweeps/r01_ps_svc_frac.jsonl
@@ -217,6 +243,14 @@ DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
   // alone -0.6% against full paths, 3 rounds on one box (profiles/sweeps/r04_pq_depth.log)
   fr.pq_depth = std::min<uint32_t>(std::max<uint32_t>(env_u32("WGT_PQ_DEPTH", 6), 1u), (uint32_t)kRayDepth);
   fr.pq_lpt_all = env_u32("WGT_PQ_LPT_ALL", 1);  // sweep: all pixels -3% (sponza), -4% (bunny) at 256 spp
+  return fr;
+}
+// ... of a launch of n_tiles tiles of tw x th pixels
+DevFrame tile_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th, uint32_t n_tiles) {
+  DevFrame fr = make_frame(cam, W, H);
+  fr.tw = tw;
+  fr.th = th;
+  fr.n_tiles = n_tiles;
   return fr;
 }
 
@@ -286,7 +320,6 @@ double scene_extent(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint
     }
   return m;
 }
-constexpr double kOriginBoundScale = 4.0;
 
 int check_render_args(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H,
                       uint32_t tw, uint32_t th) {
@@ -347,11 +380,23 @@ void fill_stats(const unsigned long long* c, wgt_stats* s) {
   s->quad_ref_scans = c[CNT_QUAD_REF];
 }
 
-
 // Times of one frame's launch (profile runs only).
 struct FrameTiming {
   float total_ms = 0.0f;
 };
+void fill_timing(const FrameTiming& timing, wgt_stats* s) {
+  s->kernel_ms = timing.total_ms;
+  s->trace_ms = timing.total_ms;
+  s->iterations = 1;
+}
+// The stats of a synchronous render (wgt_render_frames, wgt_render_tile): the counters of a
+// second, instrumented pass over the context's tile list, and the time of the render itself
+int stats_of_render(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th,
+                    uint32_t n_tiles, const FrameTiming& timing, wgt_stats* stats) {
+  const int rc = wgt_render_tiles_stats(ctx, cam, W, H, tw, th, (const wgt_tile*)ctx->tiles.p, n_tiles, stats);
+  if (rc == WGT_OK) fill_timing(timing, stats);
+  return rc;
+}
 
 hipEvent_t pool_event(wgt_ctx* ctx, size_t i) {
   while (ctx->evpool.size() <= i) {
@@ -518,31 +563,16 @@ int wgt_bvh_build(const wgt_triangle* tris, uint32_t n_tris, float* nodes_out, u
   if (!tris || n_tris == 0 || !info) return fail(nullptr, WGT_E_INVALID, "null triangles or info");
   BvhOut bvh;
   std::string err;
-  if (!BuildBvh(tris, n_tris, (uint32_t)kMaxBvhDepth, stack_limit(), narrow_limit(), narrow_ratio(),
-                kOriginBoundScale * scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
+  if (!build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
     return fail(nullptr, WGT_E_INVALID, err);
   *info = wgt_scene_info{};
-  info->n_tris = n_tris;
-  info->bvh_nodes = bvh.n_nodes;
-  info->bvh_leaves = bvh.n_leaves;
-  info->bvh_max_depth = bvh.max_depth;
-  info->bvh_max_leaf = bvh.max_leaf;
+  fill_bvh_info(bvh, n_tris, ps_form_for(bvh, n_tris), *info);
   info->device_bytes = (bvh.nodes.size() + bvh.tris.size() + bvh.tshade.size()) * 4;
-  info->sah_cost = bvh.sah_cost;
-  info->bvh_width = (uint32_t)kBvhWidth;
-  info->bvh_stack = bvh.stack_need > 0 ? bvh.stack_need : 1u;
-  info->bvh2_nodes = bvh.n_nodes2;
-  info->bvh2_depth = bvh.depth2;
   if (nodes_out) {
     if (nodes_cap < bvh.n_nodes) return fail(nullptr, WGT_E_INVALID, "node capacity too small");
     std::memcpy(nodes_out, bvh.nodes.data(), bvh.nodes.size() * 4);
   }
   if (tris_out) std::memcpy(tris_out, bvh.tris.data(), bvh.tris.size() * 4);
-  info->bvh_compact = (size_t)bvh.n_nodes * kNode4Floats * 4 > kCompactNodeBytes ? 1u : 0u;
-  info->bvh_compact_step = bvh.cstep;
-  info->ps_waves = ps_waves_for(bvh, n_tris);
-  ps_park_cap(n_tris, (bvh.stack_need > 0 ? bvh.stack_need : 1u) + 1u, info->ps_waves, info->ps_park,
-              info->ps_stack);
   return WGT_OK;
 }
 
@@ -552,8 +582,7 @@ int wgt_bvh_build_compact(const wgt_triangle* tris, uint32_t n_tris, uint32_t* c
     return fail(nullptr, WGT_E_INVALID, "null triangles or outputs");
   BvhOut bvh;
   std::string err;
-  if (!BuildBvh(tris, n_tris, (uint32_t)kMaxBvhDepth, stack_limit(), narrow_limit(), narrow_ratio(),
-                kOriginBoundScale * scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
+  if (!build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
     return fail(nullptr, WGT_E_INVALID, err);
   if (nodes_cap < bvh.n_nodes) return fail(nullptr, WGT_E_INVALID, "node capacity too small");
   std::memcpy(cnodes_out, bvh.cnodes.data(), bvh.cnodes.size() * 4);
@@ -586,16 +615,8 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
     std::string err;
     const double ext = std::max({scene_extent(lights, n_lights, spheres, n_spheres, tris, n_tris),
                                  scene_extent(quads, n_quads, nullptr, 0, nullptr, 0)});
-    if (!BuildBvh(tris, n_tris, (uint32_t)kMaxBvhDepth, stack_limit(), narrow_limit(), narrow_ratio(),
-                  kOriginBoundScale * ext, bvh, err))
-      return fail(ctx, WGT_E_INVALID, err);
+    if (!build_bvh(tris, n_tris, ext, bvh, err)) return fail(ctx, WGT_E_INVALID, err);
   }
-  const uint32_t nlq = n_lights + n_quads;
-  const size_t b_quads = align256((size_t)nlq * 96);
-  const size_t b_sph = align256((size_t)n_spheres * 32);
-  // both node forms stay resident (the compact one is 63% of the 128-B one); the
-  // launch picks one per frame (DevFrame::cnode)
-  const size_t b_nodes = align256(bvh.nodes.size() * 4);
   // compact records: the 64-B node followed by its 16-B refs (wgt_geom.h)
   std::vector<uint32_t> crec((size_t)bvh.n_nodes * kCRecordFloat4s * 4);
   for (size_t i = 0; i < bvh.n_nodes; ++i) {
@@ -613,7 +634,6 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
       if (r128 >= 0) r128 *= (int32_t)(kNode4Floats * 4);
       std::memcpy(&bvh.nodes[i * kNode4Floats + 24 + k], &r128, 4);
     }
-  const size_t b_cnodes = align256(crec.size() * 4);
   // each node's level (root 0, saturating at 255): preorder refs point forward, so one pass
   std::vector<uint8_t> level(bvh.n_nodes, 0);
   for (size_t i = 0; i < bvh.n_nodes; ++i)
@@ -622,14 +642,20 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
       std::memcpy(&r, &bvh.crefs[i * 4 + k], 4);
       if (r >= 0 && (size_t)r < bvh.n_nodes) level[r] = (uint8_t)std::min(255, level[i] + 1);
     }
-  const size_t b_level = align256(level.size());
   // the device triangle records (wgt_geom.h kTriRecordBytes): the builder's 64-B records
   static_assert(kTriRecordBytes == kTriRecordFloats * 4, "device and host triangle records");
-  const std::vector<float>& dtris = bvh.tris;
-  const size_t b_tris = align256(dtris.size() * 4);
-  const size_t b_shade = align256(bvh.tshade.size() * 4);
-  const uint32_t waves = ps_waves_for(bvh, n_tris);
-  const size_t total = b_quads + b_sph + b_nodes + b_tris + b_shade + b_cnodes + b_level;
+  // The scene's device layout, each part 256-B aligned: quads (lights first), spheres, then the
+  // tree: both node forms stay resident (the compact one is 63% of the 128-B one; the launch
+  // picks one per frame, DevFrame::cnode), the triangle and shading records, the node levels
+  size_t total = 0;
+  const auto place = [&total](size_t bytes) {
+    const size_t at = total;
+    total += align256(bytes);
+    return at;
+  };
+  const size_t o_quads = place((size_t)(n_lights + n_quads) * 96), o_sph = place((size_t)n_spheres * 32);
+  const size_t o_nodes = place(bvh.nodes.size() * 4), o_tris = place(bvh.tris.size() * 4);
+  const size_t o_shade = place(bvh.tshade.size() * 4), o_cnodes = place(crec.size() * 4), o_level = place(level.size());
 
   {
     int rc = use_drain(ctx);  // no launch on any stream may still read the old scene
@@ -645,28 +671,28 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   WGT_HIP(ctx, hipMalloc(&ctx->scene_mem, total));
   char* base = (char*)ctx->scene_mem;
   std::vector<char> host(total, 0);
-  std::memcpy(host.data(), lights, (size_t)n_lights * 96);
-  if (n_quads) std::memcpy(host.data() + (size_t)n_lights * 96, quads, (size_t)n_quads * 96);
-  std::memcpy(host.data() + b_quads, spheres, (size_t)n_spheres * 32);
+  std::memcpy(host.data() + o_quads, lights, (size_t)n_lights * 96);
+  if (n_quads) std::memcpy(host.data() + o_quads + (size_t)n_lights * 96, quads, (size_t)n_quads * 96);
+  std::memcpy(host.data() + o_sph, spheres, (size_t)n_spheres * 32);
   if (n_tris) {
-    std::memcpy(host.data() + b_quads + b_sph, bvh.nodes.data(), bvh.nodes.size() * 4);
-    std::memcpy(host.data() + b_quads + b_sph + b_nodes, dtris.data(), dtris.size() * 4);
-    std::memcpy(host.data() + b_quads + b_sph + b_nodes + b_tris, bvh.tshade.data(),
-                bvh.tshade.size() * 4);
-    std::memcpy(host.data() + b_quads + b_sph + b_nodes + b_tris + b_shade, crec.data(), crec.size() * 4);
-    std::memcpy(host.data() + b_quads + b_sph + b_nodes + b_tris + b_shade + b_cnodes, level.data(), level.size());
+    std::memcpy(host.data() + o_nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
+    std::memcpy(host.data() + o_tris, bvh.tris.data(), bvh.tris.size() * 4);
+    std::memcpy(host.data() + o_shade, bvh.tshade.data(), bvh.tshade.size() * 4);
+    std::memcpy(host.data() + o_cnodes, crec.data(), crec.size() * 4);
+    std::memcpy(host.data() + o_level, level.data(), level.size());
   }
   WGT_HIP(ctx, hipMemcpy(base, host.data(), total, hipMemcpyHostToDevice));
 
+  const PsForm form = ps_form_for(bvh, n_tris);
   DevScene& sc = ctx->sc;
   sc = DevScene{};
-  sc.quads = (const float4*)base;
-  sc.spheres = (const float4*)(base + b_quads);
-  sc.nodes = (const float4*)(base + b_quads + b_sph);
-  sc.tris = (const float4*)(base + b_quads + b_sph + b_nodes);
-  sc.tshade = (const float4*)(base + b_quads + b_sph + b_nodes + b_tris);
-  sc.cnodes = (const float4*)(base + b_quads + b_sph + b_nodes + b_tris + b_shade);
-  sc.node_level = (const uint8_t*)(base + b_quads + b_sph + b_nodes + b_tris + b_shade + b_cnodes);
+  sc.quads = (const float4*)(base + o_quads);
+  sc.spheres = (const float4*)(base + o_sph);
+  sc.nodes = (const float4*)(base + o_nodes);
+  sc.tris = (const float4*)(base + o_tris);
+  sc.tshade = (const float4*)(base + o_shade);
+  sc.cnodes = (const float4*)(base + o_cnodes);
+  sc.node_level = (const uint8_t*)(base + o_level);
   sc.cstep = bvh.cstep;
   sc.cbound = bvh.cbound;
   sc.rcstep = 1.0f / sc.cstep;  // a power of two: exact
@@ -679,13 +705,10 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   const f3 lr = f3{lights[0].right[0], lights[0].right[1], lights[0].right[2]};
   const f3 lu = f3{lights[0].up[0], lights[0].up[1], lights[0].up[2]};
   sc.light_area = length(cross(lr, lu));  // path_tracer.wgsl:205
-  // + 1: the speculative traversal parks a second leaf on the stack (wgt_device.h)
-  sc.stack = (bvh.stack_need > 0 ? bvh.stack_need : 1u) + 1u;
-  sc.ps_waves = waves;
-  // parked traversal state (WGT_PARK=0: the whole stack in LDS);
-  // the LDS stack holds what fits beside the parked words at the wave budget, or the whole
-  // stack when that is smaller (WGT_PS_CAP lowers it, down to kMinPsCap, for tests)
-  ps_park_cap(n_tris, sc.stack, sc.ps_waves, sc.ps_park, sc.ps_cap);
+  sc.stack = stack_entries(bvh);
+  sc.ps_waves = form.waves;
+  sc.ps_park = form.park;
+  sc.ps_cap = form.cap;
   WGT_HIP(ctx, ps_resident_waves(sc, ctx->device, ctx->ps_resident));
   if (env_u32("WGT_DEBUG", 0))
     std::fprintf(stderr, "[wgt] resident: k_render_ps %u waves; LDS stack %u of %u entries, parked %u\n",
@@ -693,25 +716,11 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
 
   wgt_scene_info& in = ctx->info;
   in = wgt_scene_info{};
+  fill_bvh_info(bvh, n_tris, form, in);
   in.n_lights = n_lights;
   in.n_quads = n_quads;
   in.n_spheres = n_spheres;
-  in.n_tris = n_tris;
-  in.bvh_nodes = bvh.n_nodes;
-  in.bvh_leaves = bvh.n_leaves;
-  in.bvh_max_depth = bvh.max_depth;
-  in.bvh_max_leaf = bvh.max_leaf;
   in.device_bytes = total;
-  in.sah_cost = bvh.sah_cost;
-  in.bvh_width = n_tris ? (uint32_t)kBvhWidth : 0u;
-  in.bvh_stack = n_tris ? std::max(bvh.stack_need, 1u) : 0u;
-  in.bvh2_nodes = bvh.n_nodes2;
-  in.bvh2_depth = bvh.depth2;
-  in.bvh_compact = (size_t)bvh.n_nodes * kNode4Floats * 4 > kCompactNodeBytes ? 1u : 0u;
-  in.bvh_compact_step = bvh.cstep;
-  in.ps_waves = n_tris ? sc.ps_waves : 0u;
-  in.ps_park = sc.ps_park;
-  in.ps_stack = n_tris ? sc.ps_cap : 0u;
   {
     const wgt_camera_param cam{{278.0f, 278.0f, -800.0f}, 0.0f, {278.0f, 278.0f, 0.0f}, 0.0f, 1.0f, 40.0f, 1u, 0u};
     in.node_form = n_tris ? (uint32_t)node_form(sc, make_frame(cam, 1, 1)) : 0u;
@@ -736,10 +745,7 @@ int wgt_render_tiles_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W
   if (n_tiles == 0) return WGT_OK;
   if (!d_tiles) return fail(ctx, WGT_E_INVALID, "null tile list");
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  DevFrame fr = make_frame(*cam, W, H);
-  fr.tw = tw;
-  fr.th = th;
-  fr.n_tiles = n_tiles;
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   return render_frame(ctx, fr, d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr, s,
                       nullptr);
@@ -757,10 +763,7 @@ int wgt_render_tiles_stats(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = ensure(ctx, ctx->counters, CNT_N * 8))) return rc;
   WGT_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, CNT_N * 8, ctx->stream));
-  DevFrame fr = make_frame(*cam, W, H);
-  fr.tw = tw;
-  fr.th = th;
-  fr.n_tiles = n_tiles;
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   if ((rc = render_frame(ctx, fr, d_tiles, nullptr, nullptr, nullptr,
                          (unsigned long long*)ctx->counters.p, ctx->stream, nullptr)))
     return rc;
@@ -781,17 +784,12 @@ int wgt_render_tiles_profile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t
   if (n_tiles == 0) return WGT_OK;
   if (!d_tiles) return fail(ctx, WGT_E_INVALID, "null tile list");
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  DevFrame fr = make_frame(*cam, W, H);
-  fr.tw = tw;
-  fr.th = th;
-  fr.n_tiles = n_tiles;
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   FrameTiming timing;
   if ((rc = render_frame(ctx, fr, d_tiles, nullptr, nullptr, nullptr, nullptr, ctx->stream, &timing)))
     return rc;
   WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  stats->kernel_ms = timing.total_ms;
-  stats->trace_ms = timing.total_ms;
-  stats->iterations = 1;
+  fill_timing(timing, stats);
   return WGT_OK;
 }
 
@@ -811,24 +809,14 @@ int wgt_render_frames(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uin
   if ((rc = ensure(ctx, ctx->out8, npx * n_frames * 4))) return rc;
   WGT_HIP(ctx, hipMemcpyAsync(ctx->tiles.p, tl.data(), n_frames * sizeof(wgt_tile), hipMemcpyHostToDevice,
                               ctx->stream));
-  DevFrame fr = make_frame(*cam, W, H);
-  fr.tw = W;
-  fr.th = H;
-  fr.n_tiles = n_frames;
+  const DevFrame fr = tile_frame(*cam, W, H, W, H, n_frames);
   FrameTiming timing;
   if ((rc = render_frame(ctx, fr, (const wgt_tile*)ctx->tiles.p, (uchar4*)ctx->out8.p, nullptr, nullptr, nullptr,
                          ctx->stream, stats ? &timing : nullptr)))
     return rc;
   WGT_HIP(ctx, hipMemcpyAsync(rgba8_out, ctx->out8.p, npx * n_frames * 4, hipMemcpyDeviceToHost, ctx->stream));
   WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (stats) {
-    rc = wgt_render_tiles_stats(ctx, cam, W, H, W, H, (const wgt_tile*)ctx->tiles.p, n_frames, stats);
-    if (rc) return rc;
-    stats->kernel_ms = timing.total_ms;
-    stats->trace_ms = timing.total_ms;
-    stats->iterations = 1;
-  }
-  return WGT_OK;
+  return stats ? stats_of_render(ctx, cam, W, H, W, H, n_frames, timing, stats) : WGT_OK;
 }
 
 int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0,
@@ -852,10 +840,7 @@ int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint3
     if (rgba32f_out) WGT_HIP(ctx, hipMemsetAsync(ctx->out32.p, 0, npx * 16, ctx->stream));
     if (hit_id_out) WGT_HIP(ctx, hipMemsetAsync(ctx->hit.p, 0xff, npx * 4, ctx->stream));
   }
-  DevFrame fr = make_frame(*cam, W, H);
-  fr.tw = tw;
-  fr.th = th;
-  fr.n_tiles = 1;
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, 1);
   FrameTiming timing;
   if ((rc = render_frame(ctx, fr, (const wgt_tile*)ctx->tiles.p, rgba8_out ? (uchar4*)ctx->out8.p : nullptr,
                          rgba32f_out ? (float4*)ctx->out32.p : nullptr,
@@ -869,14 +854,7 @@ int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint3
   if (hit_id_out)
     WGT_HIP(ctx, hipMemcpyAsync(hit_id_out, ctx->hit.p, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
   WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (stats) {
-    rc = wgt_render_tiles_stats(ctx, cam, W, H, tw, th, (const wgt_tile*)ctx->tiles.p, 1, stats);
-    if (rc) return rc;
-    stats->kernel_ms = timing.total_ms;
-    stats->trace_ms = timing.total_ms;
-    stats->iterations = 1;
-  }
-  return WGT_OK;
+  return stats ? stats_of_render(ctx, cam, W, H, tw, th, 1, timing, stats) : WGT_OK;
 }
 
 int wgt_trace_rays_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t* d_prim_id,
