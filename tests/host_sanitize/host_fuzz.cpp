@@ -1,6 +1,7 @@
 // host_fuzz.cpp — the product's host code under AddressSanitizer + UBSan (CPU only; built and
 // run by tests/test_host_sanitize.py): the BVH builder over random, degenerate and extreme
-// triangle sets and every stack budget, the OBJ parser over valid, malformed and random
+// triangle sets, every stack budget and both collapses, with the device image of every tree it
+// builds, the OBJ parser over valid, malformed and random
 // text, the procedural meshes, and the host C-ABI entry points (Cornell scene, triangle
 // packing, OBJ and PNG writers).  Exits non-zero on a failed invariant; the sanitizers
 // abort on the first finding.
@@ -46,14 +47,44 @@ static std::vector<wgt_triangle> pack(const std::vector<float>& v) {  // 9 float
   return t;
 }
 
-// The 64-B compact form (WGT_CN64) holds the tree whenever no coordinate is farther from the world
-// origin than ~the scene's extent (its origins are 512 K steps with K a signed byte, and the step is
-// ~extent / 65504): checked for such triangle sets.
-// Returns whether the build succeeded (its output checked).
-static bool build(const std::vector<wgt_triangle>& t, uint32_t stack_limit, uint32_t narrow) {
+// The device image of a built tree (wgt::DeviceImage), checked completely: the 128-B nodes and the
+// 80-B compact records are the builder's with internal refs as byte offsets, and a node's level is
+// its parent's + 1, saturating at 255.
+static void check_image(const wgt::BvhOut& out) {
+  const wgt::BvhImage im = wgt::DeviceImage(out);
+  const bool sized = im.nodes.size() == out.nodes.size() && im.crecs.size() == (size_t)out.n_nodes * 20 &&
+                     im.level.size() == out.n_nodes;
+  CHECK(sized);
+  if (!sized) return;
+  CHECK(im.level[0] == 0);
+  for (size_t i = 0; i < out.n_nodes; ++i) {
+    const auto a = wgt::Node4(out.nodes, i), b = wgt::Node4(im.nodes, i);
+    for (int s = 0; s < 4; ++s) {
+      for (int c = 0; c < 3; ++c)
+        CHECK(std::memcmp(&a.lo(c, s), &b.lo(c, s), 4) == 0 && std::memcmp(&a.hi(c, s), &b.hi(c, s), 4) == 0);
+      CHECK(std::memcmp(&a.pad(s), &b.pad(s), 4) == 0);
+      const int32_t r = a.ref(s), cr = out.crefs[i * 4 + s];
+      CHECK(b.ref(s) == (r >= 0 ? r * 128 : r));
+      int32_t rec;
+      std::memcpy(&rec, &im.crecs[i * 20 + 16 + s], 4);
+      CHECK(rec == (cr >= 0 ? cr * 80 : cr));
+      if (r >= 0 && (size_t)r < out.n_nodes) CHECK(im.level[r] == std::min(255, im.level[i] + 1));
+    }
+    CHECK(std::memcmp(&im.crecs[i * 20], &out.cnodes[i * 16], 64) == 0);
+  }
+}
+
+// Returns whether the build succeeded (its output checked).  `opt` carries the builder's tuning;
+// the limits are set here.
+static bool build(const std::vector<wgt_triangle>& t, uint32_t stack_limit, uint32_t narrow, wgt::BvhOptions opt = {}) {
   wgt::BvhOut out;
   std::string err;
-  const bool ok = wgt::BuildBvh(t.data(), (uint32_t)t.size(), 24, stack_limit, narrow, 1.03, 1e4, out, err);
+  opt.max_depth = 24;
+  opt.stack_limit = stack_limit;
+  opt.narrow_limit = narrow;
+  opt.narrow_ratio = 1.03;
+  opt.origin_bound = 1e4;
+  const bool ok = wgt::BuildBvh(t.data(), (uint32_t)t.size(), opt, out, err);
   if (!ok) {  // a refusal must say why
     CHECK(!err.empty());
     return false;
@@ -74,6 +105,7 @@ static bool build(const std::vector<wgt_triangle>& t, uint32_t stack_limit, uint
   for (int s : seen) CHECK(s == 1);
   // the compact form: one record and 4 refs per node
   CHECK(out.cnodes.size() == (size_t)out.n_nodes * 16 && out.crefs.size() == (size_t)out.n_nodes * 4);
+  check_image(out);
   return true;
 }
 
@@ -116,6 +148,17 @@ static void fuzz_bvh() {
     for (float& x : v) x *= s;
     build(pack(v), 31, 0);
   }
+  // the collapses the defaults do not reach: the greedy one, and the optimal one merging BVH2
+  // subtrees into leaves (a node weight of 2 makes merges pay)
+  wgt::BvhOptions greedy, merge;
+  greedy.collapse = wgt::BvhOptions::kGreedy;
+  merge.dp_leaf = 8;
+  merge.dp_node = 2.0;
+  for (const wgt::BvhOptions& opt : {greedy, merge})
+    for (uint32_t n : sizes) {
+      for (uint32_t lim : {31u, 24u, 20u, 16u}) build(pack(soup(g, n, 500.0f, 20.0f)), lim, 0, opt);
+      build(pack(soup(g, n, 500.0f, 20.0f)), 31, 25, opt);
+    }
 }
 
 static void fuzz_obj() {

@@ -9,21 +9,20 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <memory>
 
-#include "../wgt_geom.h"
-
 namespace wgt {
 namespace {
+
+constexpr float kInf = std::numeric_limits<float>::infinity();
 
 struct Box {
   float lo[3], hi[3];
   void reset() {
     for (int c = 0; c < 3; ++c) {
-      lo[c] = std::numeric_limits<float>::infinity();
-      hi[c] = -std::numeric_limits<float>::infinity();
+      lo[c] = kInf;
+      hi[c] = -kInf;
     }
   }
   void grow(const Box& b) {
@@ -45,44 +44,32 @@ struct Prim {
   uint32_t idx;
 };
 
-constexpr int kMaxBins = 256;
-// SAH bins per axis (WGT_SAH_BINS, <= kMaxBins; tuning sweeps)
-int SahBins() {
-  const char* v = std::getenv("WGT_SAH_BINS");
-  const int n = v && *v ? std::atoi(v) : 128;
-  return std::max(2, std::min(n, kMaxBins));
-}
+// A child of a BVH2 node, or a slot of a BVH4 node: its box and its ref (wgt_geom.h)
+struct Child {
+  Box b;
+  int ref;
+};
+// The SAH BVH2 (host only), in preorder: children follow their parent.
+struct Node2 {
+  Child c[2];
+};
+using Bvh2 = std::vector<Node2>;
 
-// Depth of a median-split subtree over `count` primitives (leaves <= leaf_max).
-uint32_t MedianDepth(uint32_t count, uint32_t leaf_max = (uint32_t)kLeafMax) {
+constexpr int kMaxBins = 256;
+constexpr double kCostTri = 1.0;  // SAH cost of a triangle test (BvhOptions::sah_trav: of a node visit)
+
+// Depth of a median-split subtree over `count` primitives (leaves <= kLeafMax).
+uint32_t MedianDepth(uint32_t count) {
   uint32_t d = 0;
-  while (count > leaf_max) {
-    count = (count + 1) / 2;
-    ++d;
-  }
+  for (; count > (uint32_t)kLeafMax; count = (count + 1) / 2) ++d;
   return d;
-}
-// SAH costs of a BVH2 node visit and a triangle test, and the largest leaf the
-// SAH may choose (<= kLeafMax, the encoding's limit).  WGT_SAH_TRAV / WGT_SAH_LEAF
-// override them for tuning sweeps; the defaults are the measured best.
-constexpr double kCostTri = 1.0;
-double SahTravCost() {
-  const char* v = std::getenv("WGT_SAH_TRAV");
-  return v && *v ? std::atof(v) : 1.0;
-}
-uint32_t SahLeafMax() {
-  const char* v = std::getenv("WGT_SAH_LEAF");
-  const int n = v && *v ? std::atoi(v) : kLeafMax;
-  return (uint32_t)std::max(1, std::min(n, kLeafMax));
 }
 
 class Builder {
  public:
-  // leaf_max: the largest leaf (kLeafMax, the BVH4 record's limit)
-  Builder(std::vector<Prim>& p, BvhOut& o, std::vector<float>& n2, uint32_t limit,
-          uint32_t leaf_max = (uint32_t)kLeafMax)
-      : prims_(p), out_(o), nodes_(n2), limit_(limit), leaf_max_(leaf_max),
-        sah_leaf_(std::min(SahLeafMax(), leaf_max)) {}
+  Builder(std::vector<Prim>& p, BvhOut& o, Bvh2& n2, const BvhOptions& opt)
+      : prims_(p), out_(o), nodes_(n2), limit_(opt.max_depth), sah_leaf_(std::min(opt.sah_leaf, (uint32_t)kLeafMax)),
+        cost_trav_(opt.sah_trav), bins_(std::max(2, std::min(opt.sah_bins, kMaxBins))) {}
 
   // Returns the child reference of the subtree over prims_[begin, end).
   int Build(uint32_t begin, uint32_t end, uint32_t depth, Box& box) {
@@ -104,68 +91,61 @@ class Builder {
     // Depth guarantee: every leaf at depth <= limit_ (the traversal stack holds at
     // most `depth` entries).  Invariant: depth + MedianDepth(count) <= limit_; an SAH
     // split is taken only if both children keep it, otherwise the median split does.
-    bool median = false;
-    {
-      double best = std::numeric_limits<double>::infinity();
-      int best_axis = -1, best_bin = -1;
-      const double parea = box.area();
-      for (int axis = 0; axis < 3; ++axis) {
-        const float ext = cb.hi[axis] - cb.lo[axis];
-        if (!(ext > 0.0f)) continue;
-        Box bb[kMaxBins];
-        uint32_t bn[kMaxBins] = {};
-        for (int k = 0; k < bins_; ++k) bb[k].reset();
-        const double scale = bins_ / (double)ext;
-        for (uint32_t i = begin; i < end; ++i) {
-          int k = std::min(bins_ - 1, (int)((prims_[i].c[axis] - cb.lo[axis]) * scale));
-          bb[k].grow(prims_[i].b);
-          bn[k]++;
-        }
-        double rarea[kMaxBins];
-        uint32_t rcount[kMaxBins];
-        Box acc;
-        acc.reset();
-        uint32_t n = 0;
-        for (int k = bins_ - 1; k > 0; --k) {
-          acc.grow(bb[k]);
-          n += bn[k];
-          rarea[k] = acc.area();
-          rcount[k] = n;
-        }
-        acc.reset();
-        n = 0;
-        for (int k = 0; k < bins_ - 1; ++k) {
-          acc.grow(bb[k]);
-          n += bn[k];
-          if (n == 0 || rcount[k + 1] == 0) continue;
-          double cost = acc.area() * n + rarea[k + 1] * rcount[k + 1];
-          if (cost < best) {
-            best = cost;
-            best_axis = axis;
-            best_bin = k;
-          }
-        }
+    bool median = true;  // unless an SAH split is taken; of few enough triangles, a leaf instead
+    double best = std::numeric_limits<double>::infinity();
+    int best_axis = -1, best_bin = -1;
+    const double parea = box.area();
+    for (int axis = 0; axis < 3; ++axis) {
+      const float ext = cb.hi[axis] - cb.lo[axis];
+      if (!(ext > 0.0f)) continue;
+      Box bb[kMaxBins];
+      uint32_t bn[kMaxBins] = {};
+      for (int k = 0; k < bins_; ++k) bb[k].reset();
+      const double scale = bins_ / (double)ext;
+      for (uint32_t i = begin; i < end; ++i) {
+        int k = std::min(bins_ - 1, (int)((prims_[i].c[axis] - cb.lo[axis]) * scale));
+        bb[k].grow(prims_[i].b);
+        bn[k]++;
       }
-      const double split_cost = cost_trav_ + kCostTri * (parea > 0 ? best / parea : 0.0);
-      const double leaf_cost = kCostTri * count;
-      if (best_axis >= 0 && !(count <= sah_leaf_ && leaf_cost <= split_cost)) {
-        const float ext = cb.hi[best_axis] - cb.lo[best_axis];
-        const double scale = bins_ / (double)ext;
-        auto it = std::partition(prims_.begin() + begin, prims_.begin() + end, [&](const Prim& p) {
-          int k = std::min(bins_ - 1, (int)((p.c[best_axis] - cb.lo[best_axis]) * scale));
-          return k <= best_bin;
-        });
-        mid = (uint32_t)(it - prims_.begin());
-        if (mid == begin || mid == end) median = true;
-        else if (depth + 1 + MedianDepth(std::max(mid - begin, end - mid), leaf_max_) > limit_) median = true;
-      } else if (count <= leaf_max_) {
-        return MakeLeaf(begin, count, box);
-      } else {
-        median = true;
+      double rarea[kMaxBins];
+      uint32_t rcount[kMaxBins];
+      Box acc;
+      acc.reset();
+      uint32_t n = 0;
+      for (int k = bins_ - 1; k > 0; --k) {
+        acc.grow(bb[k]);
+        n += bn[k];
+        rarea[k] = acc.area();
+        rcount[k] = n;
+      }
+      acc.reset();
+      n = 0;
+      for (int k = 0; k < bins_ - 1; ++k) {
+        acc.grow(bb[k]);
+        n += bn[k];
+        if (n == 0 || rcount[k + 1] == 0) continue;
+        double cost = acc.area() * n + rarea[k + 1] * rcount[k + 1];
+        if (cost < best) {
+          best = cost;
+          best_axis = axis;
+          best_bin = k;
+        }
       }
     }
+    const double split_cost = cost_trav_ + kCostTri * (parea > 0 ? best / parea : 0.0);
+    const double leaf_cost = kCostTri * count;
+    if (best_axis >= 0 && !(count <= sah_leaf_ && leaf_cost <= split_cost)) {
+      const float ext = cb.hi[best_axis] - cb.lo[best_axis];
+      const double scale = bins_ / (double)ext;
+      auto it = std::partition(prims_.begin() + begin, prims_.begin() + end, [&](const Prim& p) {
+        int k = std::min(bins_ - 1, (int)((p.c[best_axis] - cb.lo[best_axis]) * scale));
+        return k <= best_bin;
+      });
+      mid = (uint32_t)(it - prims_.begin());
+      median = mid == begin || mid == end || depth + 1 + MedianDepth(std::max(mid - begin, end - mid)) > limit_;
+    }
     if (median) {
-      if (count <= leaf_max_) return MakeLeaf(begin, count, box);
+      if (count <= (uint32_t)kLeafMax) return MakeLeaf(begin, count, box);
       int axis = 0;
       for (int c = 1; c < 3; ++c)
         if (cb.hi[c] - cb.lo[c] > cb.hi[axis] - cb.lo[axis]) axis = c;
@@ -175,25 +155,14 @@ class Builder {
                          return a.c[axis] < b.c[axis] || (a.c[axis] == b.c[axis] && a.idx < b.idx);
                        });
     }
-    const uint32_t id = (uint32_t)(nodes_.size() / 16);
-    nodes_.resize(nodes_.size() + 16);
-    Box bl, br;
-    const int rl = Build(begin, mid, depth + 1, bl);
-    const int rr = Build(mid, end, depth + 1, br);
-    WriteNode(id, bl, rl, br, rr);
+    const size_t id = nodes_.size();
+    nodes_.emplace_back();
+    Child l, r;
+    l.ref = Build(begin, mid, depth + 1, l.b);
+    r.ref = Build(mid, end, depth + 1, r.b);
+    nodes_[id] = Node2{{l, r}};
     out_.sah_cost += cost_trav_ * box.area();
     return (int)id;
-  }
-
-  void WriteNode(uint32_t id, const Box& b0, int r0, const Box& b1, int r1) {
-    float* n = &nodes_[(size_t)id * 16];
-    n[0] = b0.lo[0]; n[1] = b0.hi[0]; n[2] = b0.lo[1]; n[3] = b0.hi[1];
-    n[4] = b1.lo[0]; n[5] = b1.hi[0]; n[6] = b1.lo[1]; n[7] = b1.hi[1];
-    n[8] = b0.lo[2]; n[9] = b0.hi[2]; n[10] = b1.lo[2]; n[11] = b1.hi[2];
-    std::memcpy(&n[12], &r0, 4);
-    std::memcpy(&n[13], &r1, 4);
-    n[14] = 0.0f;
-    n[15] = 0.0f;
   }
 
  private:
@@ -206,58 +175,77 @@ class Builder {
 
   std::vector<Prim>& prims_;
   BvhOut& out_;
-  std::vector<float>& nodes_;
-  uint32_t limit_;
-  uint32_t leaf_max_;
-  uint32_t sah_leaf_;
-  double cost_trav_ = SahTravCost();
-  int bins_ = SahBins();
+  Bvh2& nodes_;
+  uint32_t limit_, sah_leaf_;
+  double cost_trav_;
+  int bins_;
 };
 
-
-// BVH2 child `which` (0/1) of node `id`, from the 16-float BVH2 layout.
-struct Child {
-  Box b;
-  int ref;
+// A collapse's result: the BVH4 nodes in preorder, their exact worst-case stack need and depth.
+struct Tree4 {
+  std::vector<float> nodes;
+  uint32_t stack_need = 0, max_depth = 0;
+  uint32_t size() const { return (uint32_t)(nodes.size() / kNode4Floats); }
 };
-Child Child2(const std::vector<float>& n2, int id, int which) {
-  const float* n = &n2[(size_t)id * 16];
-  Child c;
-  const int o = which ? 4 : 0;
-  c.b.lo[0] = n[o + 0]; c.b.hi[0] = n[o + 1]; c.b.lo[1] = n[o + 2]; c.b.hi[1] = n[o + 3];
-  c.b.lo[2] = n[8 + 2 * which]; c.b.hi[2] = n[9 + 2 * which];
-  std::memcpy(&c.ref, &n[12 + which], 4);
-  return c;
+
+// Appends the BVH4 node of the slots ch[0, n) (2 <= n <= kBvhWidth) at `depth` and, through
+// sub(ref2, need) -> node index, the subtrees of its internal slots, in preorder; returns its
+// index.  `need` receives the worst-case stack entries of the subtree: the traversal pushes at
+// most (children - 1) per node on a root-to-node path, so need = (n - 1) + max over internal
+// slots.  Empty slots are padded as wgt_geom.h says.
+template <class Sub>
+int EmitNode(Tree4& t, const Child* ch, int n, uint32_t depth, uint32_t& need, Sub&& sub) {
+  const size_t id = t.size();
+  t.nodes.resize(t.nodes.size() + kNode4Floats);
+  t.max_depth = std::max(t.max_depth, depth + 1);
+  int refs[kBvhWidth];
+  uint32_t deepest = 0;
+  for (int i = 0; i < n; ++i) {
+    refs[i] = ch[i].ref;
+    if (ch[i].ref < 0) continue;
+    uint32_t sn = 0;
+    refs[i] = sub(ch[i].ref, sn);
+    deepest = std::max(deepest, sn);
+  }
+  need = (uint32_t)(n - 1) + deepest;
+  const auto o = Node4(t.nodes, id);  // only now: the subtrees grew t.nodes
+  for (int i = 0; i < kBvhWidth; ++i) {
+    const bool live = i < n;
+    for (int c = 0; c < 3; ++c) {
+      o.lo(c, i) = live ? ch[i].b.lo[c] : kEmptySlotCoord;
+      o.hi(c, i) = live ? ch[i].b.hi[c] : kEmptySlotCoord;
+    }
+    o.set_ref(i, live ? refs[i] : refs[0]);
+    o.pad(i) = 0.0f;
+  }
+  return (int)id;
 }
 
 // Budgeted greedy collapse: a BVH4 node starts from the two children of a BVH2
 // node and repeatedly opens its largest-area internal child until it has 4
-// slots.  Returns the BVH4 node index; `need` receives the worst-case stack
-// entries of the subtree: the traversal pushes at most (children - 1) per node
-// on a root-to-node path, so need = (children - 1) + max over internal children.
-// The stack is bounded by `budget`: a child is opened only while (children - 1)
+// slots.  The stack is bounded by `budget`: a child is opened only while (children - 1)
 // + the least need any child can still reach (its BVH2 height: a 2-wide node
 // pushes one entry per level) fits, so only the deep, stack-heavy paths get
 // narrower nodes.  Any budget >= the BVH2 height is met.
 class Collapser {
  public:
-  Collapser(const std::vector<float>& n2, BvhOut& o) : n2_(n2), out_(o), h_(n2.size() / 16, 0u) {
-    for (size_t i = h_.size(); i-- > 0;) {  // children follow their parent (preorder)
-      uint32_t m = 0;
-      for (int w = 0; w < 2; ++w) {
-        const Child c = Child2(n2_, (int)i, w);
-        if (c.ref >= 0) m = std::max(m, h_[c.ref]);
-      }
-      h_[i] = 1u + m;
-    }
+  explicit Collapser(const Bvh2& n2) : n2_(n2), h_(n2.size(), 0u) {
+    for (size_t i = h_.size(); i-- > 0;) h_[i] = 1u + std::max(Below(n2_[i].c[0]), Below(n2_[i].c[1]));
   }
   uint32_t Height(int id2) const { return h_[id2]; }
 
-  int Collapse(int id2, uint32_t depth, uint32_t budget, uint32_t& need) {
-    Child ch[kBvhWidth];
+  Tree4 Run(uint32_t budget) const {
+    Tree4 t;
+    Collapse(t, 0, 0, budget, t.stack_need);
+    return t;
+  }
+
+ private:
+  uint32_t Below(const Child& c) const { return c.ref >= 0 ? h_[c.ref] : 0u; }
+
+  int Collapse(Tree4& t, int id2, uint32_t depth, uint32_t budget, uint32_t& need) const {
+    Child ch[kBvhWidth] = {n2_[id2].c[0], n2_[id2].c[1]};
     int n = 2;
-    ch[0] = Child2(n2_, id2, 0);
-    ch[1] = Child2(n2_, id2, 1);
     bool blocked[kBvhWidth] = {false, false, false, false};
     while (n < kBvhWidth) {
       int best = -1;
@@ -269,58 +257,27 @@ class Collapser {
         }
       if (best < 0) break;
       // the node after opening `best`: n children, the least subtree need of each
-      uint32_t m = 0;
+      const Child a = n2_[ch[best].ref].c[0], b = n2_[ch[best].ref].c[1];
+      uint32_t m = std::max(Below(a), Below(b));
       for (int i = 0; i < n; ++i)
-        if (i != best && ch[i].ref >= 0) m = std::max(m, h_[ch[i].ref]);
-      const int r = ch[best].ref;
-      for (int w = 0; w < 2; ++w) {
-        const Child c = Child2(n2_, r, w);
-        if (c.ref >= 0) m = std::max(m, h_[c.ref]);
-      }
+        if (i != best) m = std::max(m, Below(ch[i]));
       if ((uint32_t)n + m > budget) {  // (n + 1 children) - 1 + m
         blocked[best] = true;
         continue;
       }
-      ch[best] = Child2(n2_, r, 0);
-      ch[n++] = Child2(n2_, r, 1);
-      blocked[best] = false;
+      ch[best] = a;
+      ch[n++] = b;
     }
-    const uint32_t id = (uint32_t)(out_.nodes.size() / kNode4Floats);
-    out_.nodes.resize(out_.nodes.size() + kNode4Floats);
-    out_.max_depth = std::max(out_.max_depth, depth + 1);
-    int refs[kBvhWidth];
-    uint32_t sub = 0;
-    for (int i = 0; i < n; ++i) {
-      if (ch[i].ref >= 0) {
-        uint32_t sn = 0;
-        refs[i] = Collapse(ch[i].ref, depth + 1, budget - (uint32_t)(n - 1), sn);
-        sub = std::max(sub, sn);
-      } else {
-        refs[i] = ch[i].ref;
-      }
-    }
-    need = (uint32_t)(n - 1) + sub;
-    float* o = &out_.nodes[(size_t)id * kNode4Floats];
-    for (int i = 0; i < kBvhWidth; ++i) {
-      const bool live = i < n;
-      for (int c = 0; c < 3; ++c) {
-        o[(2 * c) * 4 + i] = live ? ch[i].b.lo[c] : kEmptySlotCoord;
-        o[(2 * c + 1) * 4 + i] = live ? ch[i].b.hi[c] : kEmptySlotCoord;
-      }
-      const int r = live ? refs[i] : refs[0];
-      std::memcpy(&o[24 + i], &r, 4);
-      o[28 + i] = 0.0f;
-    }
-    return (int)id;
+    return EmitNode(t, ch, n, depth, need, [&](int ref2, uint32_t& sn) {
+      return Collapse(t, ref2, depth + 1, budget - (uint32_t)(n - 1), sn);
+    });
   }
 
- private:
-  const std::vector<float>& n2_;
-  BvhOut& out_;
+  const Bvh2& n2_;
   std::vector<uint32_t> h_;  // BVH2 height (internal levels) of every BVH2 node
 };
 
-// SAH-optimal collapse under the stack budget (the default; WGT_COLLAPSE=greedy
+// SAH-optimal collapse under the stack budget (the default; BvhOptions::kGreedy
 // selects Collapser).  Every BVH4 node is a frontier of 2..4 descendants of a BVH2
 // node; a dynamic program over the BVH2 (children before parents) picks, per node
 // and per stack budget B, the frontier minimising the BVH4 SAH cost
@@ -331,36 +288,17 @@ class Collapser {
 // subtree's stack need is (k - 1) + the largest need of its internal slots).
 // Like the greedy collapse it only regroups BVH2 boxes: the BVH4 child boxes are
 // BVH2 node boxes and the exactness argument is unchanged.
-double DpNodeCost() {
-  const char* v = std::getenv("WGT_DP_NODE");
-  return v && *v ? std::atof(v) : 1.0;
-}
-double DpTriCost() {
-  const char* v = std::getenv("WGT_DP_TRI");
-  return v && *v ? std::atof(v) : 1.0;
-}
-// Largest leaf the collapse may make of a BVH2 subtree (its triangles are one
-// contiguous range): 0 keeps the BVH2 leaves (WGT_DP_LEAF, <= kLeafMax).
-uint32_t DpLeafMax() {
-  const char* v = std::getenv("WGT_DP_LEAF");
-  const int n = v && *v ? std::atoi(v) : 0;
-  return (uint32_t)std::max(0, std::min(n, kLeafMax));
-}
-bool UseDpCollapse() {
-  const char* v = std::getenv("WGT_COLLAPSE");
-  return !(v && std::strcmp(v, "greedy") == 0);
-}
-
+// The table is built once, for every budget up to `budget`; Run queries it.
 class DpCollapser {
  public:
-  DpCollapser(const std::vector<float>& n2, BvhOut& o, uint32_t budget)
-      : n2_(n2), out_(&o), nb_(budget + 1), n_(n2.size() / 16) {
-    const float inf = std::numeric_limits<float>::infinity();
-    cost_.assign(n_ * 4 * nb_, inf);  // [node][k-1][B]: k = 1 is N(node, B)
+  DpCollapser(const Bvh2& n2, const BvhOptions& opt, uint32_t budget)
+      : n2_(n2), nb_(budget + 1), n_(n2.size()), c_node_(opt.dp_node), c_tri_(opt.dp_tri),
+        leaf_max_(std::min(opt.dp_leaf, (uint32_t)kLeafMax)) {
+    cost_.assign(n_ * 4 * nb_, kInf);  // [node][k-1][B]: k = 1 is N(node, B)
     range_.assign(n_, Range{0u, 0u});
     area_.assign(n_, 0.0);
     for (size_t i = n_; i-- > 0;) {   // preorder: children have larger ids
-      const Child a = Child2(n2_, (int)i, 0), b = Child2(n2_, (int)i, 1);
+      const Child a = n2_[i].c[0], b = n2_[i].c[1];
       Box u = a.b;
       u.grow(b.b);
       const double area = u.area();
@@ -371,70 +309,48 @@ class DpCollapser {
       for (uint32_t B = 0; B < nb_; ++B) {
         // k slots of node i's frontier, each with need <= B
         for (int k = 2; k <= 4; ++k) {
-          float best = inf;
+          float best = kInf;
           for (int ia = 1; ia < k; ++ia) best = std::min(best, Slots(a, ia, B) + Slots(b, k - ia, B));
           Q(i, k, B) = best;
         }
-        float best = inf;
+        float best = kInf;
         for (int k = 2; k <= 4; ++k)
           if ((uint32_t)(k - 1) <= B) best = std::min(best, Q(i, k, B - (uint32_t)(k - 1)));
         Q(i, 1, B) = (float)(c_node_ * area) + best;
       }
     }
   }
-  float Cost(uint32_t budget) const { return budget < nb_ ? Q(0, 1, budget) : std::numeric_limits<float>::infinity(); }
-  void Retarget(BvhOut& o) { out_ = &o; }
+  // The least SAH cost of a tree with stack need <= budget (infinite: the table has none).
+  float Cost(uint32_t budget) const { return budget < nb_ ? Q(0, 1, budget) : kInf; }
 
-  // Emit node id2 as a BVH4 node with stack need <= budget (preorder ids).
-  int Emit(int id2, uint32_t depth, uint32_t budget, uint32_t& need) {
-    const Child a = Child2(n2_, id2, 0), b = Child2(n2_, id2, 1);
+  Tree4 Run(uint32_t budget) const {
+    Tree4 t;
+    Emit(t, 0, 0, budget, t.stack_need);
+    return t;
+  }
+
+ private:
+  // Emit node id2 as a BVH4 node with stack need <= budget.
+  int Emit(Tree4& t, int id2, uint32_t depth, uint32_t budget, uint32_t& need) const {
     int best_k = 2;
-    float best = std::numeric_limits<float>::infinity();
+    float best = kInf;
     for (int k = 2; k <= 4; ++k)
       if ((uint32_t)(k - 1) <= budget && Q(id2, k, budget - (uint32_t)(k - 1)) < best) {
         best = Q(id2, k, budget - (uint32_t)(k - 1));
         best_k = k;
       }
     const uint32_t sb = budget - (uint32_t)(best_k - 1);
-    std::vector<Child> slots;
-    Split(a, b, best_k, sb, slots);
-    BvhOut& out = *out_;
-    const uint32_t id = (uint32_t)(out.nodes.size() / kNode4Floats);
-    out.nodes.resize(out.nodes.size() + kNode4Floats);
-    out.max_depth = std::max(out.max_depth, depth + 1);
-    const int n = (int)slots.size();
-    int refs[kBvhWidth];
-    uint32_t sub = 0;
-    for (int i = 0; i < n; ++i) {
-      if (slots[i].ref >= 0) {
-        uint32_t sn = 0;
-        refs[i] = Emit(slots[i].ref, depth + 1, sb, sn);
-        sub = std::max(sub, sn);
-      } else {
-        refs[i] = slots[i].ref;
-      }
-    }
-    need = (uint32_t)(n - 1) + sub;
-    float* o = &out.nodes[(size_t)id * kNode4Floats];
-    for (int i = 0; i < kBvhWidth; ++i) {
-      const bool live = i < n;
-      for (int c = 0; c < 3; ++c) {
-        o[(2 * c) * 4 + i] = live ? slots[i].b.lo[c] : kEmptySlotCoord;
-        o[(2 * c + 1) * 4 + i] = live ? slots[i].b.hi[c] : kEmptySlotCoord;
-      }
-      const int r = live ? refs[i] : refs[0];
-      std::memcpy(&o[24 + i], &r, 4);
-      o[28 + i] = 0.0f;
-    }
-    return (int)id;
+    Child slots[kBvhWidth];
+    int n = 0;
+    Split(n2_[id2].c[0], n2_[id2].c[1], best_k, sb, slots, n);
+    return EmitNode(t, slots, n, depth, need, [&](int ref2, uint32_t& sn) { return Emit(t, ref2, depth + 1, sb, sn); });
   }
 
- private:
   float& Q(size_t node, int k, uint32_t B) { return cost_[(node * 4 + (size_t)(k - 1)) * nb_ + B]; }
   float Q(size_t node, int k, uint32_t B) const { return cost_[(node * 4 + (size_t)(k - 1)) * nb_ + B]; }
   // cost of covering child c with k slots, each of stack need <= B
   float Slots(const Child& c, int k, uint32_t B) const {
-    if (c.ref < 0) return k == 1 ? (float)(c_tri_ * leaf_count(c.ref) * c.b.area()) : std::numeric_limits<float>::infinity();
+    if (c.ref < 0) return k == 1 ? (float)(c_tri_ * leaf_count(c.ref) * c.b.area()) : kInf;
     if (k == 1 && Mergeable(c)) return std::min(Q((size_t)c.ref, 1, B), MergedCost(c));
     return Q((size_t)c.ref, k, B);
   }
@@ -462,10 +378,10 @@ class DpCollapser {
     }
     return c;
   }
-  // the slots of the cheapest cover of a and b by k slots (budget B each)
-  void Split(const Child& a, const Child& b, int k, uint32_t B, std::vector<Child>& out) const {
+  // the slots of the cheapest cover of a and b by k slots (budget B each), appended to out[n...]
+  void Split(const Child& a, const Child& b, int k, uint32_t B, Child* out, int& n) const {
     int best_i = 1;
-    float best = std::numeric_limits<float>::infinity();
+    float best = kInf;
     for (int i = 1; i < k; ++i) {
       const float c = Slots(a, i, B) + Slots(b, k - i, B);
       if (c < best) {
@@ -473,23 +389,19 @@ class DpCollapser {
         best_i = i;
       }
     }
-    Cover(a, best_i, B, out);
-    Cover(b, k - best_i, B, out);
+    Cover(a, best_i, B, out, n);
+    Cover(b, k - best_i, B, out, n);
   }
-  void Cover(const Child& c, int k, uint32_t B, std::vector<Child>& out) const {
-    if (k == 1) {
-      out.push_back(AsSlot(c, B));
-      return;
-    }
-    Split(Child2(n2_, c.ref, 0), Child2(n2_, c.ref, 1), k, B, out);
+  void Cover(const Child& c, int k, uint32_t B, Child* out, int& n) const {
+    if (k == 1) out[n++] = AsSlot(c, B);
+    else Split(n2_[c.ref].c[0], n2_[c.ref].c[1], k, B, out, n);
   }
 
-  const std::vector<float>& n2_;
-  BvhOut* out_;
+  const Bvh2& n2_;
   uint32_t nb_;
   size_t n_;
-  double c_node_ = DpNodeCost(), c_tri_ = DpTriCost();
-  uint32_t leaf_max_ = DpLeafMax();
+  double c_node_, c_tri_;
+  uint32_t leaf_max_;
   std::vector<float> cost_;
   std::vector<Range> range_;
   std::vector<double> area_;
@@ -500,31 +412,29 @@ class DpCollapser {
 // fused step instead of decoding the plane first), so the codes keep a margin G
 // from the exact child bounds: a lo code's plane org' + h*s (org' = the stored
 // org/s times s) lies <= lo - G, a hi code's >= hi + G.  G = 2^-21 * M, with M
-// >= |org'| and >= |ray origin| (BuildBvh's origin_bound), covers the rounding of
+// >= |org'| and >= |ray origin| (BvhOptions::origin_bound), covers the rounding of
 // c: every decoded interval then contains, bit for bit, the
 // slab interval fma(b, 1/d, ot) of every triangle box b below the child.  Codes
 // are the tightest binary16 values with the margin (non-negative half bit
 // patterns order like their values, so a binary search finds them).
 double CDecD(uint32_t h, double s, double orgd) { return orgd + (double)half_bits_to_float(h) * s; }
-void CompactNode(const float* n, float s, double G, uint32_t* q) {
-  bool live[kBvhWidth];
-  for (int i = 0; i < kBvhWidth; ++i) live[i] = !(n[i] == kEmptySlotCoord && n[4 + i] == kEmptySlotCoord);
+void CompactNode(Node4T<const float> n, float s, double G, uint32_t* q) {
   float orgs[3];
   for (int a = 0; a < 3; ++a) {
     double ulo = std::numeric_limits<double>::infinity();
     for (int i = 0; i < kBvhWidth; ++i)
-      if (live[i]) ulo = std::min(ulo, (double)n[(2 * a) * 4 + i]);
+      if (n.live(i)) ulo = std::min(ulo, (double)n.lo(a, i));
     // org/s as a float whose value times s is <= ulo - G
     const double target = (ulo - G) / (double)s;
     float f = (float)target;
-    while ((double)f > target) f = std::nextafter(f, -std::numeric_limits<float>::infinity());
+    while ((double)f > target) f = std::nextafter(f, -kInf);
     orgs[a] = f;
     const double orgd = (double)f * (double)s;
     uint32_t lo_h[kBvhWidth], hi_h[kBvhWidth];
     for (int i = 0; i < kBvhWidth; ++i) {
       lo_h[i] = hi_h[i] = 0x7c00u;  // an empty slot: +inf planes on every axis, never entered
-      if (!live[i]) continue;
-      const double blo = (double)n[(2 * a) * 4 + i] - G, bhi = (double)n[(2 * a + 1) * 4 + i] + G;
+      if (!n.live(i)) continue;
+      const double blo = (double)n.lo(a, i) - G, bhi = (double)n.hi(a, i) + G;
       uint32_t l = 0, r = 0x7bffu;  // largest h with plane <= blo (h = 0 is: orgd <= ulo - G)
       while (l < r) {
         const uint32_t m = (l + r + 1) / 2;
@@ -550,19 +460,19 @@ void CompactNode(const float* n, float s, double G, uint32_t* q) {
 // The smallest power-of-two step with which code 65504 reaches every node's upper
 // bounds plus the margins (the origin sits up to G + one float step of org/s below
 // the lower bound).
-float CompactStep(const std::vector<float>& nodes, uint32_t n_nodes, double G) {
+float CompactStep(const BvhOut& out, double G) {
   int e = -24;
   for (;;) {
     const float s = std::ldexp(1.0f, e);
     bool ok = true;
-    for (uint32_t k = 0; k < n_nodes && ok; ++k) {
-      const float* n = &nodes[(size_t)k * kNode4Floats];
+    for (uint32_t k = 0; k < out.n_nodes && ok; ++k) {
+      const auto n = Node4(out.nodes, k);
       for (int a = 0; a < 3 && ok; ++a) {
         double ulo = std::numeric_limits<double>::infinity(), uhi = -ulo;
         for (int i = 0; i < kBvhWidth; ++i)
-          if (!(n[i] == kEmptySlotCoord && n[4 + i] == kEmptySlotCoord)) {
-            ulo = std::min(ulo, (double)n[(2 * a) * 4 + i]);
-            uhi = std::max(uhi, (double)n[(2 * a + 1) * 4 + i]);
+          if (n.live(i)) {
+            ulo = std::min(ulo, (double)n.lo(a, i));
+            uhi = std::max(uhi, (double)n.hi(a, i));
           }
         const double org_low = ulo - G - (std::fabs(ulo - G) * 0x1p-23 + (double)s * 0x1p-126);
         ok = org_low + 65504.0 * (double)s >= uhi + G;
@@ -573,15 +483,14 @@ float CompactStep(const std::vector<float>& nodes, uint32_t n_nodes, double G) {
   }
 }
 
-}  // namespace
+// ---- the stages of BuildBvh, in order; a failing stage says why in err ----
 
-bool BuildBvh(const wgt_triangle* tris, uint32_t n, uint32_t max_depth_limit, uint32_t stack_limit,
-              uint32_t narrow_limit, double narrow_ratio, double origin_bound, BvhOut& out, std::string& err) {
-  out = BvhOut{};
+// The primitives: each triangle's padded box (tri_box) and its centre.
+bool MakePrims(const wgt_triangle* tris, uint32_t n, const BvhOptions& opt, std::vector<Prim>& prims, std::string& err) {
   if (n == 0) { err = "BuildBvh: no triangles"; return false; }
   // leaf walks use 32-bit byte offsets into the 64-B records (wgt_geom.h kTriRecordBytes)
   if (n >= (1u << 26)) { err = "BuildBvh: too many triangles (max 2^26-1)"; return false; }
-  std::vector<Prim> prims(n);
+  prims.resize(n);
   for (uint32_t i = 0; i < n; ++i) {
     const wgt_triangle& t = tris[i];
     f3 lo, hi;
@@ -592,127 +501,141 @@ bool BuildBvh(const wgt_triangle* tris, uint32_t n, uint32_t max_depth_limit, ui
     p.b.hi[0] = hi.x; p.b.hi[1] = hi.y; p.b.hi[2] = hi.z;
     for (int c = 0; c < 3; ++c) p.c[c] = 0.5f * p.b.lo[c] + 0.5f * p.b.hi[c];
     p.idx = i;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 3; ++c)
       if (!std::isfinite(p.b.lo[c]) || !std::isfinite(p.b.hi[c])) {
         err = "BuildBvh: non-finite triangle " + std::to_string(i);
         return false;
       }
-    }
   }
-  if (MedianDepth(n) > max_depth_limit) {
-    err = "BuildBvh: too many triangles for depth limit " + std::to_string(max_depth_limit);
+  if (MedianDepth(n) > opt.max_depth) {
+    err = "BuildBvh: too many triangles for depth limit " + std::to_string(opt.max_depth);
     return false;
   }
-  std::vector<float> n2;
-  n2.reserve((size_t)16 * 2 * (n / 2 + 1));
-  Builder b(prims, out, n2, max_depth_limit);
+  return true;
+}
+
+// The SAH BVH2 over prims (reordered into leaf order), with its counts and SAH cost in out.
+bool BuildBvh2(std::vector<Prim>& prims, const BvhOptions& opt, Bvh2& n2, BvhOut& out, std::string& err) {
+  const uint32_t n = (uint32_t)prims.size();
+  n2.reserve(2 * ((size_t)n / 2 + 1));
   Box root_box;
-  const int root = b.Build(0, n, 0, root_box);
+  const int root = Builder(prims, out, n2, opt).Build(0, n, 0, root_box);
   if (root < 0) {
     // single leaf: a root node whose second child is an empty slot (wgt_geom.h)
-    n2.assign(16, 0.0f);
     Box empty;
     for (int c = 0; c < 3; ++c) empty.lo[c] = empty.hi[c] = kEmptySlotCoord;
-    b.WriteNode(0, root_box, root, empty, root);
+    n2.assign(1, Node2{{{root_box, root}, {empty, root}}});
     out.depth2 = 1;
   }
-  if (out.depth2 > max_depth_limit) {
-    err = "BuildBvh: depth " + std::to_string(out.depth2) + " exceeds " + std::to_string(max_depth_limit);
+  if (out.depth2 > opt.max_depth) {
+    err = "BuildBvh: depth " + std::to_string(out.depth2) + " exceeds " + std::to_string(opt.max_depth);
     return false;
   }
-  out.n_nodes2 = (uint32_t)(n2.size() / 16);
-  const double ra = root_box.area();
-  if (ra > 0) out.sah_cost /= ra;
-  out.nodes.reserve(n2.size() * 2);
-  Collapser greedy(n2, out);
-  if (greedy.Height(0) > stack_limit) {
+  out.n_nodes2 = (uint32_t)n2.size();
+  if (root_box.area() > 0) out.sah_cost /= root_box.area();
+  return true;
+}
+
+// The BVH4: the BVH2 collapsed under the stack limit and, when asked for and feasible, under
+// the narrow limit too; the narrow tree is taken if it is cheap enough.  The greedy heights
+// judge feasibility; the optimal collapse's table, built once at the wide budget, serves both.
+bool CollapseBvh2(const Bvh2& n2, const BvhOptions& opt, BvhOut& out, std::string& err) {
+  const Collapser greedy(n2);
+  if (greedy.Height(0) > opt.stack_limit) {
     err = "BuildBvh: BVH2 height " + std::to_string(greedy.Height(0)) + " exceeds the stack limit " +
-          std::to_string(stack_limit);
+          std::to_string(opt.stack_limit);
     return false;
   }
-  const bool dp = UseDpCollapse();
-  std::unique_ptr<DpCollapser> opt;
-  if (dp) {
-    opt.reset(new DpCollapser(n2, out, stack_limit));
-    if (!(opt->Cost(stack_limit) < std::numeric_limits<float>::infinity())) opt.reset();
+  std::unique_ptr<DpCollapser> dp;
+  if (opt.collapse == BvhOptions::kOptimal) {
+    dp.reset(new DpCollapser(n2, opt, opt.stack_limit));
+    if (!(dp->Cost(opt.stack_limit) < kInf)) dp.reset();
   }
-  if (opt) opt->Emit(0, 0, stack_limit, out.stack_need);
-  else greedy.Collapse(0, 0, stack_limit, out.stack_need);
-  if (out.stack_need > stack_limit) {
-    err = "BuildBvh: traversal stack " + std::to_string(out.stack_need) + " exceeds " +
-          std::to_string(stack_limit);
+  const auto collapse = [&](uint32_t budget) {
+    return dp && dp->Cost(budget) < kInf ? dp->Run(budget) : greedy.Run(budget);
+  };
+  Tree4 tree = collapse(opt.stack_limit);
+  if (tree.stack_need > opt.stack_limit) {
+    err = "BuildBvh: traversal stack " + std::to_string(tree.stack_need) + " exceeds " + std::to_string(opt.stack_limit);
     return false;
   }
-  out.n_nodes = (uint32_t)(out.nodes.size() / kNode4Floats);
-  if (out.n_nodes >= (1u << 24)) {  // the device copies address nodes by 32-bit byte offsets below kNoRef
+  if (tree.size() >= (1u << 24)) {  // the device copies address nodes by 32-bit byte offsets below kNoRef
     err = "BuildBvh: too many BVH nodes (max 2^24-1)";
     return false;
   }
-  if (narrow_limit > 0 && narrow_limit < stack_limit && greedy.Height(0) <= narrow_limit) {
-    BvhOut nar;
-    if (opt && opt->Cost(narrow_limit) < std::numeric_limits<float>::infinity()) {
-      opt->Retarget(nar);
-      opt->Emit(0, 0, narrow_limit, nar.stack_need);
-    } else {
-      Collapser tight(n2, nar);
-      tight.Collapse(0, 0, narrow_limit, nar.stack_need);
-    }
-    const uint32_t nn = (uint32_t)(nar.nodes.size() / kNode4Floats);
+  if (opt.narrow_limit > 0 && opt.narrow_limit < opt.stack_limit && greedy.Height(0) <= opt.narrow_limit) {
+    Tree4 nar = collapse(opt.narrow_limit);
     // greedy trees: at most narrow_ratio x the nodes; optimal trees: at most narrow_ratio
     // x the SAH cost of the wide tree
-    const bool cheap = opt ? opt->Cost(narrow_limit) <= narrow_ratio * opt->Cost(stack_limit)
-                           : nn <= narrow_ratio * out.n_nodes;
-    if (nar.stack_need <= narrow_limit && cheap) {
-      out.nodes.swap(nar.nodes);
-      out.n_nodes = nn;
-      out.stack_need = nar.stack_need;
-      out.max_depth = nar.max_depth;
+    const bool cheap = dp ? dp->Cost(opt.narrow_limit) <= opt.narrow_ratio * dp->Cost(opt.stack_limit)
+                          : nar.size() <= opt.narrow_ratio * tree.size();
+    if (nar.stack_need <= opt.narrow_limit && cheap) {
+      tree = std::move(nar);
       out.narrow = true;
     }
   }
-  // The device traversal has no iteration cap: it terminates because every
-  // internal ref points forward (preorder), so no node is visited twice.
-  for (uint32_t i = 0; i < out.n_nodes; ++i) {
-    for (int s = 0; s < 4; ++s) {
-      int32_t r;
-      std::memcpy(&r, &out.nodes[(size_t)i * kNode4Floats + 24 + s], 4);
+  out.n_nodes = tree.size();
+  out.stack_need = tree.stack_need;
+  out.max_depth = tree.max_depth;
+  out.nodes = std::move(tree.nodes);
+  return true;
+}
+
+// The device traversal has no iteration cap: it terminates because every
+// internal ref points forward (preorder), so no node is visited twice.
+bool CheckRefs(const BvhOut& out, uint32_t n_tris, std::string& err) {
+  for (uint32_t i = 0; i < out.n_nodes; ++i)
+    for (int s = 0; s < kBvhWidth; ++s) {
+      const int32_t r = Node4(out.nodes, i).ref(s);
       const uint32_t u = ~(uint32_t)r;
       const bool ok = r >= 0 ? ((uint32_t)r > i && (uint32_t)r < out.n_nodes)
-                             : ((uint64_t)(u >> 3) + (u & 7u) + 1u <= n);
+                             : ((uint64_t)(u >> 3) + (u & 7u) + 1u <= n_tris);
       if (!ok) {
         err = "BuildBvh: malformed node " + std::to_string(i);
         return false;
       }
     }
-  }
-  // the compact codes' margin: M bounds |ray origin| (the caller's origin_bound) and
-  // every coordinate of the tree (so |org'| <= M as well)
+  return true;
+}
+
+// The compact form of out.nodes.  The codes' margin: M bounds |ray origin| (origin_bound)
+// and every coordinate of the tree (so |org'| <= M as well).
+void CompactForm(double origin_bound, BvhOut& out) {
+  const std::vector<float>& nodes = out.nodes;
   double M = std::max(origin_bound, 0x1p-60);
   for (uint32_t i = 0; i < out.n_nodes; ++i)
-    for (int k = 0; k < 24; ++k) {
-      const float v = out.nodes[(size_t)i * kNode4Floats + k];
-      if (v != kEmptySlotCoord) M = std::max(M, 2.0 * std::fabs((double)v));
-    }
+    for (int a = 0; a < 3; ++a)
+      for (int s = 0; s < kBvhWidth; ++s)
+        for (const float v : {Node4(nodes, i).lo(a, s), Node4(nodes, i).hi(a, s)})
+          if (v != kEmptySlotCoord) M = std::max(M, 2.0 * std::fabs((double)v));
   out.cbound = (float)M;
   const double G = std::ldexp(M, -21);
-  out.cstep = CompactStep(out.nodes, out.n_nodes, G);
+  out.cstep = CompactStep(out, G);
   out.cnodes.resize((size_t)out.n_nodes * kCNodeFloats);
-  out.crefs.resize((size_t)out.n_nodes * 4);
+  out.crefs.resize((size_t)out.n_nodes * kBvhWidth);
   for (uint32_t i = 0; i < out.n_nodes; ++i) {
-    CompactNode(&out.nodes[(size_t)i * kNode4Floats], out.cstep, G, &out.cnodes[(size_t)i * kCNodeFloats]);
-    std::memcpy(&out.crefs[(size_t)i * 4], &out.nodes[(size_t)i * kNode4Floats + 24], 16);
+    CompactNode(Node4(nodes, i), out.cstep, G, &out.cnodes[(size_t)i * kCNodeFloats]);
+    for (int s = 0; s < kBvhWidth; ++s) out.crefs[(size_t)i * kBvhWidth + s] = Node4(nodes, i).ref(s);
   }
-  out.tris.resize((size_t)n * kTriRecordFloats);
-  for (uint32_t i = 0; i < n; ++i) {
+}
+
+// The leaf-ordered triangle records (wgt_geom.h).
+void TriRecords(const wgt_triangle* tris, const std::vector<Prim>& prims, BvhOut& out) {
+  out.tris.resize(prims.size() * kTriRecordFloats);
+  for (size_t i = 0; i < prims.size(); ++i) {
     const wgt_triangle& t = tris[prims[i].idx];
     const Box& b = prims[i].b;
-    float* o = &out.tris[(size_t)i * kTriRecordFloats];
+    float* o = &out.tris[i * kTriRecordFloats];
     o[0] = t.v0[0]; o[1] = t.v0[1]; o[2] = t.v0[2];
     std::memcpy(&o[3], &prims[i].idx, 4);
     o[4] = t.e1[0]; o[5] = t.e1[1]; o[6] = t.e1[2]; o[7] = b.lo[0];
     o[8] = t.e2[0]; o[9] = t.e2[1]; o[10] = t.e2[2]; o[11] = b.lo[1];
     o[12] = b.lo[2]; o[13] = b.hi[0]; o[14] = b.hi[1]; o[15] = b.hi[2];
   }
+}
+
+// The shading records, in the triangles' original order (wgt_internal.h tshade).
+void ShadeRecords(const wgt_triangle* tris, uint32_t n, BvhOut& out) {
   out.tshade.resize((size_t)n * 8);
   for (uint32_t i = 0; i < n; ++i) {
     const wgt_triangle& t = tris[i];
@@ -720,7 +643,71 @@ bool BuildBvh(const wgt_triangle* tris, uint32_t n, uint32_t max_depth_limit, ui
     o[0] = t.face_norm[0]; o[1] = t.face_norm[1]; o[2] = t.face_norm[2]; o[3] = t.emissive;
     o[4] = t.col[0]; o[5] = t.col[1]; o[6] = t.col[2]; o[7] = 0.0f;
   }
+}
+
+}  // namespace
+
+// The builder's tuning knobs (defaults: the measured best), all read here.
+BvhOptions BvhOptionsFromEnv(uint32_t max_depth, uint32_t stack_max, uint32_t stack_narrow, double origin_bound) {
+  const auto env = [](const char* name) { const char* v = std::getenv(name); return v && *v ? v : nullptr; };
+  const auto real = [&](const char* name, double dflt) { return env(name) ? std::atof(env(name)) : dflt; };
+  const auto clamped = [&](const char* name, int dflt, int lo, int hi) {
+    return std::max(lo, std::min(env(name) ? std::atoi(env(name)) : dflt, hi));
+  };
+  const auto u32 = [&](const char* name, uint32_t dflt) {
+    return env(name) ? (uint32_t)std::strtoul(env(name), nullptr, 10) : dflt;
+  };
+  BvhOptions o;
+  o.max_depth = max_depth;
+  o.origin_bound = origin_bound;
+  // WGT_STACK_LIMIT (stack_max): a lower stack bound, for sweeps and tests
+  o.stack_limit = std::min(u32("WGT_STACK_LIMIT", stack_max), stack_max);
+  // WGT_NARROW (0): the narrow collapse, off since 3-byte stack entries give 6 waves per SIMD the full bound;
+  // 1 takes it when its cost is within the default narrow_ratio of the wide tree's, 2 whenever it is feasible
+  const uint32_t narrow = u32("WGT_NARROW", 0);
+  o.narrow_limit = narrow ? stack_narrow : 0u;
+  if (narrow == 2) o.narrow_ratio = 1e30;
+  o.sah_bins = clamped("WGT_SAH_BINS", o.sah_bins, 2, kMaxBins);          // (128) 2..256
+  o.sah_trav = real("WGT_SAH_TRAV", o.sah_trav);                          // (1.0)
+  o.sah_leaf = (uint32_t)clamped("WGT_SAH_LEAF", kLeafMax, 1, kLeafMax);  // (8) 1..8
+  o.dp_node = real("WGT_DP_NODE", o.dp_node);                             // (1.0)
+  o.dp_tri = real("WGT_DP_TRI", o.dp_tri);                                // (1.0)
+  o.dp_leaf = (uint32_t)clamped("WGT_DP_LEAF", 0, 0, kLeafMax);           // (0) 0..8
+  // WGT_COLLAPSE (dp): "greedy" selects the greedy collapse, anything else the optimal one
+  const char* c = env("WGT_COLLAPSE");
+  o.collapse = c && std::strcmp(c, "greedy") == 0 ? BvhOptions::kGreedy : BvhOptions::kOptimal;
+  return o;
+}
+
+bool BuildBvh(const wgt_triangle* tris, uint32_t n, const BvhOptions& opt, BvhOut& out, std::string& err) {
+  out = BvhOut{};
+  std::vector<Prim> prims;
+  Bvh2 n2;
+  if (!MakePrims(tris, n, opt, prims, err) || !BuildBvh2(prims, opt, n2, out, err) ||
+      !CollapseBvh2(n2, opt, out, err) || !CheckRefs(out, n, err))
+    return false;
+  CompactForm(opt.origin_bound, out);
+  TriRecords(tris, prims, out);
+  ShadeRecords(tris, n, out);
   return true;
+}
+
+BvhImage DeviceImage(const BvhOut& bvh) {
+  constexpr size_t kRecWords = kCRecordFloat4s * 4;
+  BvhImage im{bvh.nodes, std::vector<uint32_t>(bvh.n_nodes * kRecWords), std::vector<uint8_t>(bvh.n_nodes, 0)};
+  for (size_t i = 0; i < bvh.n_nodes; ++i) {
+    uint32_t* rec = &im.crecs[i * kRecWords];
+    std::memcpy(rec, &bvh.cnodes[i * kCNodeFloats], kCNodeFloats * 4);
+    for (int s = 0; s < kBvhWidth; ++s) {
+      const int32_t r = Node4(bvh.nodes, i).ref(s), c = bvh.crefs[i * kBvhWidth + s];
+      Node4(im.nodes, i).set_ref(s, r >= 0 ? r * (int32_t)(kNode4Floats * 4) : r);
+      const int32_t cr = c >= 0 ? c * (int32_t)(kRecWords * 4) : c;
+      std::memcpy(&rec[kCNodeFloats + s], &cr, 4);
+      // preorder refs point forward, so one pass sets a child's level after its parent's
+      if (c >= 0 && (size_t)c < bvh.n_nodes) im.level[c] = (uint8_t)std::min(255, im.level[i] + 1);
+    }
+  }
+  return im;
 }
 
 }  // namespace wgt

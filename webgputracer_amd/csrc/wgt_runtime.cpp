@@ -135,21 +135,6 @@ uint32_t env_u32(const char* name, uint32_t dflt) {
   return (uint32_t)std::strtoul(v, nullptr, 10);
 }
 
-// The builder's stack bound (WGT_STACK_LIMIT overrides kStackMax for sweeps).
-uint32_t stack_limit() { return std::min(env_u32("WGT_STACK_LIMIT", (uint32_t)kStackMax), (uint32_t)kStackMax); }
-// The narrow collapse (a 25-entry stack bound), off by default since 3-byte stack
-// entries give 6 waves per SIMD the full bound: WGT_NARROW=1 takes it when its SAH
-// cost is within kNarrowNodeRatio of the wide tree's, 2 whenever the BVH2 is shallow
-// enough (sweeps).
-uint32_t narrow_limit() { return env_u32("WGT_NARROW", 0) ? (uint32_t)kStackNarrow : 0u; }
-double narrow_ratio() { return env_u32("WGT_NARROW", 0) == 2 ? 1e30 : kNarrowNodeRatio; }
-// The build with the project's knobs, for ray origins within kOriginBoundScale x `extent`
-// (scene_extent)
-constexpr double kOriginBoundScale = 4.0;
-bool build_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh, std::string& err) {
-  return BuildBvh(tris, n_tris, (uint32_t)kMaxBvhDepth, stack_limit(), narrow_limit(), narrow_ratio(),
-                  kOriginBoundScale * extent, bvh, err);
-}
 // The traversal stack of the built tree, entries per lane (DevScene::stack): + 1, the
 // speculative traversal parks a second leaf on the stack (wgt_device.h)
 uint32_t stack_entries(const BvhOut& bvh) { return std::max(bvh.stack_need, 1u) + 1u; }
@@ -302,7 +287,7 @@ double sq(double x) { return x * x; }
 // Largest |coordinate| any point of the scene's primitives can have (quad corners,
 // sphere boxes, triangle vertices): hit points, i.e. secondary ray origins, lie
 // within it.  The compact nodes are built for ray origins within 4x this bound,
-// which holds the reference camera outside its Cornell box (BuildBvh origin_bound).
+// which holds the reference camera outside its Cornell box (BvhOptions::origin_bound).
 double scene_extent(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns, const wgt_triangle* tr,
                     uint32_t nt) {
   double m = 0.0;
@@ -319,6 +304,20 @@ double scene_extent(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint
       m = std::max({m, std::fabs(v), std::fabs(v + tr[i].e1[c]), std::fabs(v + tr[i].e2[c])});
     }
   return m;
+}
+
+// The build with the kernels' limits and the environment's knobs (BvhOptionsFromEnv), for ray
+// origins within kOriginBoundScale x `extent` (scene_extent)
+constexpr double kOriginBoundScale = 4.0;
+static_assert(BvhOptions{}.max_depth == kMaxBvhDepth && BvhOptions{}.stack_limit == kStackMax, "the builder's defaults");
+int build_bvh(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh) {
+  std::string err;
+  const BvhOptions opt = BvhOptionsFromEnv(kMaxBvhDepth, kStackMax, kStackNarrow, kOriginBoundScale * extent);
+  return BuildBvh(tris, n_tris, opt, bvh, err) ? WGT_OK : fail(ctx, WGT_E_INVALID, err);
+}
+// wgt_bvh_build, wgt_bvh_build_compact: the tree exactly as an upload of these triangles alone builds it
+int build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh) {
+  return build_bvh(nullptr, tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh);
 }
 
 int check_render_args(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H,
@@ -557,14 +556,12 @@ int wgt_sync(wgt_ctx* ctx) {
   return WGT_OK;
 }
 
-// Host-only: build the BVH exactly as wgt_upload_scene does and export it.
+// Host-only exports of the tree (build_for_export).
 int wgt_bvh_build(const wgt_triangle* tris, uint32_t n_tris, float* nodes_out, uint32_t nodes_cap,
                   float* tris_out, wgt_scene_info* info) {
   if (!tris || n_tris == 0 || !info) return fail(nullptr, WGT_E_INVALID, "null triangles or info");
   BvhOut bvh;
-  std::string err;
-  if (!build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
-    return fail(nullptr, WGT_E_INVALID, err);
+  if (int rc = build_for_export(tris, n_tris, bvh)) return rc;
   *info = wgt_scene_info{};
   fill_bvh_info(bvh, n_tris, ps_form_for(bvh, n_tris), *info);
   info->device_bytes = (bvh.nodes.size() + bvh.tris.size() + bvh.tshade.size()) * 4;
@@ -581,9 +578,7 @@ int wgt_bvh_build_compact(const wgt_triangle* tris, uint32_t n_tris, uint32_t* c
   if (!tris || n_tris == 0 || !cnodes_out || !crefs_out || !step_out)
     return fail(nullptr, WGT_E_INVALID, "null triangles or outputs");
   BvhOut bvh;
-  std::string err;
-  if (!build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, err))
-    return fail(nullptr, WGT_E_INVALID, err);
+  if (int rc = build_for_export(tris, n_tris, bvh)) return rc;
   if (nodes_cap < bvh.n_nodes) return fail(nullptr, WGT_E_INVALID, "node capacity too small");
   std::memcpy(cnodes_out, bvh.cnodes.data(), bvh.cnodes.size() * 4);
   std::memcpy(crefs_out, bvh.crefs.data(), bvh.crefs.size() * 4);
@@ -612,36 +607,11 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
 
   BvhOut bvh;
   if (n_tris > 0) {
-    std::string err;
     const double ext = std::max({scene_extent(lights, n_lights, spheres, n_spheres, tris, n_tris),
                                  scene_extent(quads, n_quads, nullptr, 0, nullptr, 0)});
-    if (!build_bvh(tris, n_tris, ext, bvh, err)) return fail(ctx, WGT_E_INVALID, err);
+    if (int rc = build_bvh(ctx, tris, n_tris, ext, bvh)) return rc;
   }
-  // compact records: the 64-B node followed by its 16-B refs (wgt_geom.h)
-  std::vector<uint32_t> crec((size_t)bvh.n_nodes * kCRecordFloat4s * 4);
-  for (size_t i = 0; i < bvh.n_nodes; ++i) {
-    std::memcpy(&crec[i * kCRecordFloat4s * 4], &bvh.cnodes[i * kCNodeFloats], kCNodeFloats * 4);
-    std::memcpy(&crec[i * kCRecordFloat4s * 4 + kCNodeFloats], &bvh.crefs[i * 4], 16);
-  }
-  // device copies address child nodes by byte offset (one add to the uniform base in
-  // the kernels instead of an index multiply); leaf refs are unchanged
-  for (size_t i = 0; i < bvh.n_nodes; ++i)
-    for (int k = 0; k < 4; ++k) {
-      int32_t& r = reinterpret_cast<int32_t&>(crec[i * kCRecordFloat4s * 4 + kCNodeFloats + k]);
-      if (r >= 0) r *= (int32_t)(kCRecordFloat4s * 16);
-      int32_t r128;
-      std::memcpy(&r128, &bvh.nodes[i * kNode4Floats + 24 + k], 4);
-      if (r128 >= 0) r128 *= (int32_t)(kNode4Floats * 4);
-      std::memcpy(&bvh.nodes[i * kNode4Floats + 24 + k], &r128, 4);
-    }
-  // each node's level (root 0, saturating at 255): preorder refs point forward, so one pass
-  std::vector<uint8_t> level(bvh.n_nodes, 0);
-  for (size_t i = 0; i < bvh.n_nodes; ++i)
-    for (int k = 0; k < 4; ++k) {
-      int32_t r;
-      std::memcpy(&r, &bvh.crefs[i * 4 + k], 4);
-      if (r >= 0 && (size_t)r < bvh.n_nodes) level[r] = (uint8_t)std::min(255, level[i] + 1);
-    }
+  const BvhImage image = DeviceImage(bvh);
   // the device triangle records (wgt_geom.h kTriRecordBytes): the builder's 64-B records
   static_assert(kTriRecordBytes == kTriRecordFloats * 4, "device and host triangle records");
   // The scene's device layout, each part 256-B aligned: quads (lights first), spheres, then the
@@ -654,8 +624,9 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
     return at;
   };
   const size_t o_quads = place((size_t)(n_lights + n_quads) * 96), o_sph = place((size_t)n_spheres * 32);
-  const size_t o_nodes = place(bvh.nodes.size() * 4), o_tris = place(bvh.tris.size() * 4);
-  const size_t o_shade = place(bvh.tshade.size() * 4), o_cnodes = place(crec.size() * 4), o_level = place(level.size());
+  const size_t o_nodes = place(image.nodes.size() * 4), o_tris = place(bvh.tris.size() * 4);
+  const size_t o_shade = place(bvh.tshade.size() * 4), o_cnodes = place(image.crecs.size() * 4);
+  const size_t o_level = place(image.level.size());
 
   {
     int rc = use_drain(ctx);  // no launch on any stream may still read the old scene
@@ -675,11 +646,11 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   if (n_quads) std::memcpy(host.data() + o_quads + (size_t)n_lights * 96, quads, (size_t)n_quads * 96);
   std::memcpy(host.data() + o_sph, spheres, (size_t)n_spheres * 32);
   if (n_tris) {
-    std::memcpy(host.data() + o_nodes, bvh.nodes.data(), bvh.nodes.size() * 4);
+    std::memcpy(host.data() + o_nodes, image.nodes.data(), image.nodes.size() * 4);
     std::memcpy(host.data() + o_tris, bvh.tris.data(), bvh.tris.size() * 4);
     std::memcpy(host.data() + o_shade, bvh.tshade.data(), bvh.tshade.size() * 4);
-    std::memcpy(host.data() + o_cnodes, crec.data(), crec.size() * 4);
-    std::memcpy(host.data() + o_level, level.data(), level.size());
+    std::memcpy(host.data() + o_cnodes, image.crecs.data(), image.crecs.size() * 4);
+    std::memcpy(host.data() + o_level, image.level.data(), image.level.size());
   }
   WGT_HIP(ctx, hipMemcpy(base, host.data(), total, hipMemcpyHostToDevice));
 
