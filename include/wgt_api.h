@@ -18,6 +18,7 @@
  *   Scene::Release / OnFinish scene.cpp:41-50         wgt_destroy
  *   Error(...) / callbacks render.cpp:120-133         int status + wgt_last_error
  *   sample_hit            path_tracer.wgsl:290-310    wgt_trace_rays (closest-hit query)
+ *   (none: sample_hit's dist < a limit)               wgt_occluded_rays (any-hit query)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -243,6 +244,17 @@ int wgt_render_tiles_stats(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W
 int wgt_trace_rays(wgt_ctx *ctx, const float *rays, uint32_t n, uint32_t *prim_id, float *dist);
 int wgt_trace_rays_async(wgt_ctx *ctx, const float *d_rays, uint32_t n, uint32_t *d_prim_id,
                          float *d_dist, void *stream);
+
+/* ---- occlusion (any-hit) queries with a per-ray distance limit ----------- */
+/* Rays as for wgt_trace_rays; max_dist: n floats, in scene units (the Euclidean hit
+ * distance `dist` of wgt_trace_rays, not the ray parameter).  occluded[i] = 1 iff
+ * wgt_trace_rays on ray i returns a primitive and dist < max_dist[i] (an IEEE f32
+ * comparison: a NaN limit, a limit <= 0, a miss and a NaN ray give 0; +inf asks for
+ * any hit at all), else 0.  The answer is exact; the query stops at the first such
+ * primitive and culls the tree with the limit. */
+int wgt_occluded_rays(wgt_ctx *ctx, const float *rays, const float *max_dist, uint32_t n, uint8_t *occluded);
+int wgt_occluded_rays_async(wgt_ctx *ctx, const float *d_rays, const float *d_max_dist, uint32_t n,
+                            uint8_t *d_occluded, void *stream);
 
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,

@@ -69,7 +69,8 @@ class WgtSceneInfo(ctypes.Structure):
 EXPORTS = [
     "wgt_create", "wgt_destroy", "wgt_last_error", "wgt_version", "wgt_build_id", "wgt_device_count",
     "wgt_upload_scene", "wgt_scene_info_get", "wgt_render_tile", "wgt_render_tiles_async",
-    "wgt_render_tiles_stats", "wgt_render_tiles_profile", "wgt_trace_rays", "wgt_trace_rays_async", "wgt_sync", "wgt_selftest_math", "wgt_stream",
+    "wgt_render_tiles_stats", "wgt_render_tiles_profile", "wgt_trace_rays", "wgt_trace_rays_async",
+    "wgt_occluded_rays", "wgt_occluded_rays_async", "wgt_sync", "wgt_selftest_math", "wgt_stream",
     "wgt_pipeline_stream",
     "wgt_scene_cornell", "wgt_make_triangles", "wgt_load_obj", "wgt_procedural_mesh",
     "wgt_write_obj", "wgt_write_png", "wgt_bvh_build", "wgt_bvh_build_compact",
@@ -118,6 +119,8 @@ def lib():
         "wgt_render_tiles_profile": (I, [P, P, U32, U32, U32, U32, P, U32, P]),
         "wgt_trace_rays": (I, [P, P, U32, P, P]),
         "wgt_trace_rays_async": (I, [P, P, U32, P, P, P]),
+        "wgt_occluded_rays": (I, [P, P, P, U32, P]),
+        "wgt_occluded_rays_async": (I, [P, P, P, U32, P, P]),
         "wgt_sync": (I, [P]),
         "wgt_selftest_math": (I, [P, U32, U32, P]),
         "wgt_stream": (P, [P]),

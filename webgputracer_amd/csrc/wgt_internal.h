@@ -227,4 +227,9 @@ hipError_t launch_selftest_math(uint32_t n, uint32_t seed, unsigned long long* d
 hipError_t launch_trace(const DevScene& sc, const float* d_rays, uint32_t n, uint32_t* prim,
                         float* dist, hipStream_t stream);
 
+// Launcher implemented in wgt_occlusion.hip
+// out[i] = ray i hits a primitive closer than max_dist[i] (k_occluded; rays as launch_trace's).
+hipError_t launch_occluded(const DevScene& sc, const float* d_rays, const float* d_max_dist, uint32_t n,
+                           uint8_t* d_out, hipStream_t stream);
+
 }  // namespace wgt

@@ -47,6 +47,7 @@ struct wgt_ctx {
   // scratch for the synchronous entry points
   DevBuf tiles, out8, out32, hit, counters, rays, prim, dist;
   uint32_t ps_resident = 0;
+  DevBuf occ_limit, occ_out;  // occlusion queries: the limits and the answers
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
   // previous launch that used the same slot, so consecutive frames issued on two
@@ -508,6 +509,7 @@ void wgt_destroy(wgt_ctx* ctx) {
   if (ctx->scene_mem) (void)hipFree(ctx->scene_mem);
   free_buf(ctx->tiles); free_buf(ctx->out8); free_buf(ctx->out32); free_buf(ctx->hit);
   free_buf(ctx->counters); free_buf(ctx->rays); free_buf(ctx->prim); free_buf(ctx->dist);
+  free_buf(ctx->occ_limit); free_buf(ctx->occ_out);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -840,6 +842,41 @@ int wgt_trace_rays_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t
   if ((rc = use_begin(ctx, s))) return rc;
   WGT_HIP(ctx, launch_trace(ctx->sc, d_rays, n, d_prim_id, d_dist, s));
   return use_end(ctx, s);
+}
+
+int wgt_occluded_rays_async(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n,
+                            uint8_t* d_occluded, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (n == 0) return WGT_OK;
+  if (!d_rays || !d_max_dist || !d_occluded) return fail(ctx, WGT_E_INVALID, "null buffer");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  int rc;
+  if ((rc = use_begin(ctx, s))) return rc;
+  WGT_HIP(ctx, launch_occluded(ctx->sc, d_rays, d_max_dist, n, d_occluded, s));
+  return use_end(ctx, s);
+}
+
+int wgt_occluded_rays(wgt_ctx* ctx, const float* rays, const float* max_dist, uint32_t n, uint8_t* occluded) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (n == 0) return WGT_OK;
+  if (!rays || !max_dist || !occluded) return fail(ctx, WGT_E_INVALID, "null buffer");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ensure(ctx, ctx->rays, (size_t)n * 24))) return rc;
+  if ((rc = ensure(ctx, ctx->occ_limit, (size_t)n * 4))) return rc;
+  if ((rc = ensure(ctx, ctx->occ_out, (size_t)n))) return rc;
+  WGT_HIP(ctx, hipMemcpyAsync(ctx->rays.p, rays, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+  WGT_HIP(ctx, hipMemcpyAsync(ctx->occ_limit.p, max_dist, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = use_begin(ctx, ctx->stream))) return rc;
+  WGT_HIP(ctx, launch_occluded(ctx->sc, (const float*)ctx->rays.p, (const float*)ctx->occ_limit.p, n,
+                               (uint8_t*)ctx->occ_out.p, ctx->stream));
+  if ((rc = use_end(ctx, ctx->stream))) return rc;
+  WGT_HIP(ctx, hipMemcpyAsync(occluded, ctx->occ_out.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WGT_OK;
 }
 
 int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8]) {

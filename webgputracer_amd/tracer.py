@@ -5,7 +5,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   Scene::LoadObj (scene.cpp:56-131)         -> load_obj()
   Camera::Update (camera.cpp:64-70)         -> camera_param()
   Renderer::InitDevice / OnRender dispatch  -> Context.render_tile / render_tiles_async
-  sample_hit (path_tracer.wgsl:290-310)     -> Context.trace_rays
+  sample_hit (path_tracer.wgsl:290-310)     -> Context.trace_rays, Context.occluded (dist < a limit)
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -236,6 +236,23 @@ class Context:
     def trace_rays_async(self, d_rays, n, d_prim, d_dist, stream=0):
         self._check(self._L.wgt_trace_rays_async(self.h, ctypes.c_void_p(d_rays), n, ctypes.c_void_p(d_prim),
                                                  ctypes.c_void_p(d_dist), ctypes.c_void_p(stream or None)))
+
+    def occluded(self, start, direction, max_dist):
+        """Any-hit query (wgt_occluded_rays): bool per ray, True iff trace_rays on it returns a
+        primitive at a distance below max_dist (scene units; a scalar broadcasts)."""
+        start = np.asarray(start, np.float32).reshape(-1, 3)
+        direction = np.asarray(direction, np.float32).reshape(-1, 3)
+        n = len(start)
+        soa = np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32)
+        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float32), (n,)))
+        out = np.zeros(n, np.uint8)
+        self._check(self._L.wgt_occluded_rays(self.h, ptr(soa), ptr(lim), n, ptr(out)))
+        return out.astype(bool)
+
+    def occluded_async(self, d_rays, d_max_dist, n, d_out, stream=0):
+        """Device-pointer launch (raw device addresses): d_out receives n bytes, 0 or 1."""
+        self._check(self._L.wgt_occluded_rays_async(self.h, ctypes.c_void_p(d_rays), ctypes.c_void_p(d_max_dist), n,
+                                                    ctypes.c_void_p(d_out), ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
