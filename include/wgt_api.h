@@ -19,6 +19,8 @@
  *   Error(...) / callbacks render.cpp:120-133         int status + wgt_last_error
  *   sample_hit            path_tracer.wgsl:290-310    wgt_trace_rays (closest-hit query)
  *   (none: sample_hit's dist < a limit)               wgt_occluded_rays (any-hit query)
+ *   HitInfo after sample_hit path_tracer.wgsl:27-36   wgt_trace_hits (the whole hit record)
+ *   (none: HitInfo of a pixel's first camera ray)     wgt_render_gbuffer (first-hit G-buffer)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -255,6 +257,50 @@ int wgt_trace_rays_async(wgt_ctx *ctx, const float *d_rays, uint32_t n, uint32_t
 int wgt_occluded_rays(wgt_ctx *ctx, const float *rays, const float *max_dist, uint32_t n, uint8_t *occluded);
 int wgt_occluded_rays_async(wgt_ctx *ctx, const float *d_rays, const float *d_max_dist, uint32_t n,
                             uint8_t *d_occluded, void *stream);
+
+/* ---- full hit records (HitInfo after sample_hit, path_tracer.wgsl:27-36) --- */
+#define WGT_HIT_EMISSIVE   1u
+#define WGT_HIT_FRONT_FACE 2u
+/* Planar outputs for n records; any pointer may be NULL (that field is not written),
+ * at least one must be set.  pos/norm/col: 3 planes of n floats, f[k*n + i].
+ * HitInfo's shape and uv are not returned: shading never reads them, and shape follows
+ * from the range prim lies in (lights and quads, then triangles, then spheres). */
+typedef struct {
+  uint32_t *prim;  /* as wgt_trace_rays */
+  float *dist;     /* as wgt_trace_rays */
+  float *pos;      /* HitInfo.pos  = o + t d */
+  float *norm;     /* HitInfo.norm (turned against the ray) */
+  float *col;      /* HitInfo.col */
+  uint8_t *flags;  /* WGT_HIT_EMISSIVE | WGT_HIT_FRONT_FACE */
+} wgt_hit_buffers;   /* 48 bytes */
+
+/* Rays as for wgt_trace_rays.  Record i is the reference's HitInfo after sample_hit on
+ * ray i, exact: the renderer's own functions on the same operands.  prim and dist equal
+ * wgt_trace_rays on the same ray bit for bit.  A miss is hit_init's state: prim =
+ * 0xffffffff, dist = kRayMax (1e20), zero vectors, flags = 0.  A ray with a NaN component
+ * gives the last sphere with NaN fields, as in the renderer.  The synchronous form takes
+ * a struct of host pointers, the async form a host struct of device pointers. */
+int wgt_trace_hits(wgt_ctx *ctx, const float *rays, uint32_t n, const wgt_hit_buffers *out);
+int wgt_trace_hits_async(wgt_ctx *ctx, const float *d_rays, uint32_t n, const wgt_hit_buffers *d_out,
+                         void *stream);
+
+/* First-hit G-buffer: the record of pixel (x, y) is the HitInfo of sample 0's primary ray
+ * of that pixel, the ray whose primitive wgt_render_tile reports in hit_id_out (prim
+ * equals it bit for bit).  cam->spp and cam->seed set that ray's jitter, as in the render;
+ * a pixel without samples (floor(sqrt(spp)) == 0) gets the miss record.  n = tw*th records,
+ * row-major.  rays_out (may be NULL) receives that ray as 6 planes of n floats, the layout
+ * of wgt_trace_rays' input (zeros for a pixel without samples), so it can be fed straight
+ * back into the ray queries.  Pixels of the rectangle outside the frame get prim =
+ * 0xffffffff and zeros in every other field and in the ray. */
+int wgt_render_gbuffer(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                       uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th,
+                       const wgt_hit_buffers *out, float *rays_out);
+/* The tile-list form with device buffers, as wgt_render_tiles_async: n = n_tiles*tw*th
+ * records at the pixel offset (t*th + ly)*tw + lx, cam->seed ignored (per-tile seeds),
+ * pixels of a tile outside the frame left untouched, ordered on `stream`. */
+int wgt_render_gbuffer_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                             uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
+                             const wgt_hit_buffers *d_out, float *d_rays, void *stream);
 
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,

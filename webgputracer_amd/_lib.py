@@ -29,6 +29,13 @@ assert TRI_DTYPE.itemsize == 80 and CAMERA_DTYPE.itemsize == 48 and TILE_DTYPE.i
 API_VERSION = 2  # WGT_API_VERSION of include/wgt_api.h
 WGT_OK, WGT_E_INVALID, WGT_E_HIP, WGT_E_NOSCENE, WGT_E_IO, WGT_E_NOMEM = 0, -1, -2, -3, -4, -5
 NO_HIT = 0xFFFFFFFF
+WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE = 1, 2  # wgt_hit_buffers.flags
+HIT_FIELDS = ("prim", "dist", "pos", "norm", "col", "flags")
+
+
+class WgtHitBuffers(ctypes.Structure):
+    """wgt_hit_buffers: planar outputs of the hit-record calls (None / 0 = field not written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in HIT_FIELDS]
 
 
 class WgtStats(ctypes.Structure):
@@ -70,7 +77,8 @@ EXPORTS = [
     "wgt_create", "wgt_destroy", "wgt_last_error", "wgt_version", "wgt_build_id", "wgt_device_count",
     "wgt_upload_scene", "wgt_scene_info_get", "wgt_render_tile", "wgt_render_tiles_async",
     "wgt_render_tiles_stats", "wgt_render_tiles_profile", "wgt_trace_rays", "wgt_trace_rays_async",
-    "wgt_occluded_rays", "wgt_occluded_rays_async", "wgt_sync", "wgt_selftest_math", "wgt_stream",
+    "wgt_occluded_rays", "wgt_occluded_rays_async", "wgt_trace_hits", "wgt_trace_hits_async",
+    "wgt_render_gbuffer", "wgt_render_gbuffer_async", "wgt_sync", "wgt_selftest_math", "wgt_stream",
     "wgt_pipeline_stream",
     "wgt_scene_cornell", "wgt_make_triangles", "wgt_load_obj", "wgt_procedural_mesh",
     "wgt_write_obj", "wgt_write_png", "wgt_bvh_build", "wgt_bvh_build_compact",
@@ -121,6 +129,10 @@ def lib():
         "wgt_trace_rays_async": (I, [P, P, U32, P, P, P]),
         "wgt_occluded_rays": (I, [P, P, P, U32, P]),
         "wgt_occluded_rays_async": (I, [P, P, P, U32, P, P]),
+        "wgt_trace_hits": (I, [P, P, U32, ctypes.POINTER(WgtHitBuffers)]),
+        "wgt_trace_hits_async": (I, [P, P, U32, ctypes.POINTER(WgtHitBuffers), P]),
+        "wgt_render_gbuffer": (I, [P, P, U32, U32, U32, U32, U32, U32, ctypes.POINTER(WgtHitBuffers), P]),
+        "wgt_render_gbuffer_async": (I, [P, P, U32, U32, U32, U32, P, U32, ctypes.POINTER(WgtHitBuffers), P, P]),
         "wgt_sync": (I, [P]),
         "wgt_selftest_math": (I, [P, U32, U32, P]),
         "wgt_stream": (P, [P]),

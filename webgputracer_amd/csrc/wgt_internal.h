@@ -232,4 +232,14 @@ hipError_t launch_trace(const DevScene& sc, const float* d_rays, uint32_t n, uin
 hipError_t launch_occluded(const DevScene& sc, const float* d_rays, const float* d_max_dist, uint32_t n,
                            uint8_t* d_out, hipStream_t stream);
 
+// Launchers implemented in wgt_hits.hip
+// Record i = the whole closest hit of ray i (k_trace_hits; rays as launch_trace's); out: device
+// pointers, a null field is not written.
+hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n, const wgt_hit_buffers& out,
+                             hipStream_t stream);
+// The record of sample 0's camera ray of every pixel of the tile list (k_gbuffer; fr as
+// launch_render's), at the render's pixel offsets; d_rays (may be null) receives those rays.
+hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
+                          const wgt_hit_buffers& out, float* d_rays, hipStream_t stream);
+
 }  // namespace wgt

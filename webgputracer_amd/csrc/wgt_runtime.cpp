@@ -48,6 +48,9 @@ struct wgt_ctx {
   DevBuf tiles, out8, out32, hit, counters, rays, prim, dist;
   uint32_t ps_resident = 0;
   DevBuf occ_limit, occ_out;  // occlusion queries: the limits and the answers
+  // hit records: pos | norm | col (9 planes), the flags, and the G-buffer's rays (prim and
+  // dist use the closest-hit query's buffers)
+  DevBuf hit_vec, hit_flags, gb_rays;
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
   // previous launch that used the same slot, so consecutive frames issued on two
@@ -454,6 +457,66 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, ucha
   return WGT_OK;
 }
 
+bool no_field(const wgt_hit_buffers& b) { return !b.prim && !b.dist && !b.pos && !b.norm && !b.col && !b.flags; }
+
+// Device staging of n hit records for the fields `out` asks for (the synchronous forms).
+int stage_hits(wgt_ctx* ctx, const wgt_hit_buffers& out, size_t n, wgt_hit_buffers& dev) {
+  dev = wgt_hit_buffers{};
+  int rc;
+  if (out.prim) {
+    if ((rc = ensure(ctx, ctx->prim, n * 4))) return rc;
+    dev.prim = (uint32_t*)ctx->prim.p;
+  }
+  if (out.dist) {
+    if ((rc = ensure(ctx, ctx->dist, n * 4))) return rc;
+    dev.dist = (float*)ctx->dist.p;
+  }
+  if (out.pos || out.norm || out.col) {
+    if ((rc = ensure(ctx, ctx->hit_vec, n * 36))) return rc;
+    float* v = (float*)ctx->hit_vec.p;
+    if (out.pos) dev.pos = v;
+    if (out.norm) dev.norm = v + 3 * n;
+    if (out.col) dev.col = v + 6 * n;
+  }
+  if (out.flags) {
+    if ((rc = ensure(ctx, ctx->hit_flags, n))) return rc;
+    dev.flags = (uint8_t*)ctx->hit_flags.p;
+  }
+  return WGT_OK;
+}
+// Defined contents for records no kernel writes (a tile reaching past the frame): prim = miss, zeros
+int clear_hits(wgt_ctx* ctx, const wgt_hit_buffers& dev, size_t n) {
+  if (dev.prim) WGT_HIP(ctx, hipMemsetAsync(dev.prim, 0xff, n * 4, ctx->stream));
+  if (dev.dist) WGT_HIP(ctx, hipMemsetAsync(dev.dist, 0, n * 4, ctx->stream));
+  if (dev.pos) WGT_HIP(ctx, hipMemsetAsync(dev.pos, 0, n * 12, ctx->stream));
+  if (dev.norm) WGT_HIP(ctx, hipMemsetAsync(dev.norm, 0, n * 12, ctx->stream));
+  if (dev.col) WGT_HIP(ctx, hipMemsetAsync(dev.col, 0, n * 12, ctx->stream));
+  if (dev.flags) WGT_HIP(ctx, hipMemsetAsync(dev.flags, 0, n, ctx->stream));
+  return WGT_OK;
+}
+// Copy back only the fields asked for.
+int fetch_hits(wgt_ctx* ctx, const wgt_hit_buffers& out, const wgt_hit_buffers& dev, size_t n) {
+  if (out.prim) WGT_HIP(ctx, hipMemcpyAsync(out.prim, dev.prim, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.dist) WGT_HIP(ctx, hipMemcpyAsync(out.dist, dev.dist, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.pos) WGT_HIP(ctx, hipMemcpyAsync(out.pos, dev.pos, n * 12, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.norm) WGT_HIP(ctx, hipMemcpyAsync(out.norm, dev.norm, n * 12, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.col) WGT_HIP(ctx, hipMemcpyAsync(out.col, dev.col, n * 12, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.flags) WGT_HIP(ctx, hipMemcpyAsync(out.flags, dev.flags, n, hipMemcpyDeviceToHost, ctx->stream));
+  return WGT_OK;
+}
+
+// The G-buffer launch of a tile list on stream s, ordered with the context's other launches.
+int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, const wgt_hit_buffers& dev,
+                   float* d_rays, hipStream_t s) {
+  // 32-bit pixel offsets in the kernels (slot_setup), as render_frame
+  if ((uint64_t)fr.tw * fr.th * fr.n_tiles > 0x7fffffffull)
+    return fail(ctx, WGT_E_INVALID, "too many pixels in one launch");
+  int rc;
+  if ((rc = use_begin(ctx, s))) return rc;
+  WGT_HIP(ctx, launch_gbuffer(ctx->sc, fr, d_tiles, dev, d_rays, s));
+  return use_end(ctx, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -510,6 +573,7 @@ void wgt_destroy(wgt_ctx* ctx) {
   free_buf(ctx->tiles); free_buf(ctx->out8); free_buf(ctx->out32); free_buf(ctx->hit);
   free_buf(ctx->counters); free_buf(ctx->rays); free_buf(ctx->prim); free_buf(ctx->dist);
   free_buf(ctx->occ_limit); free_buf(ctx->occ_out);
+  free_buf(ctx->hit_vec); free_buf(ctx->hit_flags); free_buf(ctx->gb_rays);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -875,6 +939,83 @@ int wgt_occluded_rays(wgt_ctx* ctx, const float* rays, const float* max_dist, ui
                                (uint8_t*)ctx->occ_out.p, ctx->stream));
   if ((rc = use_end(ctx, ctx->stream))) return rc;
   WGT_HIP(ctx, hipMemcpyAsync(occluded, ctx->occ_out.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WGT_OK;
+}
+
+int wgt_trace_hits_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, const wgt_hit_buffers* d_out, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (n == 0) return WGT_OK;
+  if (!d_rays || !d_out) return fail(ctx, WGT_E_INVALID, "null buffer");
+  if (no_field(*d_out)) return fail(ctx, WGT_E_INVALID, "no hit field asked for");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  int rc;
+  if ((rc = use_begin(ctx, s))) return rc;
+  WGT_HIP(ctx, launch_trace_hits(ctx->sc, d_rays, n, *d_out, s));
+  return use_end(ctx, s);
+}
+
+int wgt_trace_hits(wgt_ctx* ctx, const float* rays, uint32_t n, const wgt_hit_buffers* out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (n == 0) return WGT_OK;
+  if (!rays || !out) return fail(ctx, WGT_E_INVALID, "null buffer");
+  if (no_field(*out)) return fail(ctx, WGT_E_INVALID, "no hit field asked for");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  int rc;
+  wgt_hit_buffers dev;
+  if ((rc = ensure(ctx, ctx->rays, (size_t)n * 24))) return rc;
+  if ((rc = stage_hits(ctx, *out, n, dev))) return rc;
+  WGT_HIP(ctx, hipMemcpyAsync(ctx->rays.p, rays, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = use_begin(ctx, ctx->stream))) return rc;
+  WGT_HIP(ctx, launch_trace_hits(ctx->sc, (const float*)ctx->rays.p, n, dev, ctx->stream));
+  if ((rc = use_end(ctx, ctx->stream))) return rc;
+  if ((rc = fetch_hits(ctx, *out, dev, n))) return rc;
+  WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WGT_OK;
+}
+
+int wgt_render_gbuffer_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw,
+                             uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles, const wgt_hit_buffers* d_out,
+                             float* d_rays, void* stream) {
+  int rc = check_render_args(ctx, cam, W, H, tw, th);
+  if (rc) return rc;
+  if (n_tiles == 0) return WGT_OK;
+  if (!d_tiles) return fail(ctx, WGT_E_INVALID, "null tile list");
+  if (!d_out) return fail(ctx, WGT_E_INVALID, "null buffer");
+  if (no_field(*d_out)) return fail(ctx, WGT_E_INVALID, "no hit field asked for");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
+  return gbuffer_launch(ctx, fr, d_tiles, *d_out, d_rays, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int wgt_render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0,
+                       uint32_t tw, uint32_t th, const wgt_hit_buffers* out, float* rays_out) {
+  int rc = check_render_args(ctx, cam, W, H, tw, th);
+  if (rc) return rc;
+  if (!out) return fail(ctx, WGT_E_INVALID, "null buffer");
+  if (no_field(*out)) return fail(ctx, WGT_E_INVALID, "no hit field asked for");
+  if (x0 >= W || y0 >= H) return fail(ctx, WGT_E_INVALID, "tile origin outside the frame");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npx = (size_t)tw * th;
+  wgt_tile tile{x0, y0, cam->seed, 0u};
+  wgt_hit_buffers dev;
+  if ((rc = ensure(ctx, ctx->tiles, sizeof tile))) return rc;
+  if ((rc = stage_hits(ctx, *out, npx, dev))) return rc;
+  if (rays_out && (rc = ensure(ctx, ctx->gb_rays, npx * 24))) return rc;
+  float* d_rays = rays_out ? (float*)ctx->gb_rays.p : nullptr;
+  WGT_HIP(ctx, hipMemcpyAsync(ctx->tiles.p, &tile, sizeof tile, hipMemcpyHostToDevice, ctx->stream));
+  // pixels of a partially covered tile outside the frame are not written by the kernel
+  if (x0 + (uint64_t)tw > W || y0 + (uint64_t)th > H) {
+    if ((rc = clear_hits(ctx, dev, npx))) return rc;
+    if (d_rays) WGT_HIP(ctx, hipMemsetAsync(d_rays, 0, npx * 24, ctx->stream));
+  }
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, 1);
+  if ((rc = gbuffer_launch(ctx, fr, (const wgt_tile*)ctx->tiles.p, dev, d_rays, ctx->stream))) return rc;
+  if ((rc = fetch_hits(ctx, *out, dev, npx))) return rc;
+  if (rays_out) WGT_HIP(ctx, hipMemcpyAsync(rays_out, d_rays, npx * 24, hipMemcpyDeviceToHost, ctx->stream));
   WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WGT_OK;
 }

@@ -19,6 +19,9 @@ context's two pipeline streams (DESIGN.md §4.2a): batch k+1 starts in batch k's
 drain, while the host encodes batch k-1's PNGs.  Every frame is bit-identical to a
 single-frame render.
 
+`--gbuffer` also writes NNN_gbuffer.npz next to each NNN.png: the first-hit G-buffer of the frame
+(Context.render_gbuffer with the frame's camera and seed), the guides a denoiser asks for.
+
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
       -m webgputracer_amd.frames --frame 1 600 --spp 64 --batch 4 --out out/
@@ -75,6 +78,13 @@ class FrameRenderer:
         """{frame: (H, W, 4) uint8} for the batch `frames`, seed = frame index."""
         out = self.ctx.render_frames(self.cam, self.W, self.H, np.asarray(frames, np.uint32))
         return {f: out[j] for j, f in enumerate(frames)}
+
+    def gbuffer(self, frame: int):
+        """The frame's first-hit G-buffer (one render_gbuffer call with the frame's camera and
+        seed) under a denoiser's names: prim, depth (the hit distance), pos, normal, albedo, flags."""
+        g = self.ctx.render_gbuffer(camera_param(self.W / self.H, self.spp, frame), self.W, self.H)
+        return {"prim": g["prim"], "depth": g["dist"], "pos": g["pos"], "normal": g["norm"], "albedo": g["col"],
+                "flags": g["flags"]}
 
     def stream(self, frame_batches, depth: int = 2):
         """Yield (batch, {frame: (H, W, 4) uint8}) for each batch of `frame_batches`, in
@@ -137,7 +147,12 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="directory for NNN.png (none: render only)")
     ap.add_argument("--png-threads", type=int, default=0,
                     help="PNG encoder threads (0: this process's CPU share, capped by OMP_NUM_THREADS and 16)")
+    ap.add_argument("--gbuffer", action="store_true",
+                    help="also write NNN_gbuffer.npz next to each NNN.png: prim, depth, pos, normal, albedo, flags "
+                         "of each pixel's first hit (guides for a denoiser)")
     a = ap.parse_args(argv)
+    if a.gbuffer and not a.out:
+        ap.error("--gbuffer needs --out")
     if a.frame[0] < 1 or a.frame[1] < a.frame[0]:
         ap.error("bad frame range")  # the C++ CLI's check (csrc/main.cpp)
     if not 1 <= a.pipeline <= 4:
@@ -174,6 +189,8 @@ def main(argv=None):
         if a.out:
             for f in b:  # render.cpp:494-497
                 pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
+                if a.gbuffer:
+                    np.savez(os.path.join(a.out, f"{f:03d}_gbuffer.npz"), **fr.gbuffer(f))
             while len(pending) > 4 * workers:
                 pending.popleft().result()
     while pending:

@@ -6,6 +6,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   Camera::Update (camera.cpp:64-70)         -> camera_param()
   Renderer::InitDevice / OnRender dispatch  -> Context.render_tile / render_tiles_async
   sample_hit (path_tracer.wgsl:290-310)     -> Context.trace_rays, Context.occluded (dist < a limit)
+  HitInfo (path_tracer.wgsl:27-36)          -> Context.trace_hits, Context.render_gbuffer (whole records)
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -15,8 +16,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtSceneInfo, WgtStats,
-                   WGT_E_HIP, WgtError, check, lib, ptr)
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtHitBuffers,
+                   WgtSceneInfo, WgtStats, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -253,6 +254,68 @@ class Context:
         """Device-pointer launch (raw device addresses): d_out receives n bytes, 0 or 1."""
         self._check(self._L.wgt_occluded_rays_async(self.h, ctypes.c_void_p(d_rays), ctypes.c_void_p(d_max_dist), n,
                                                     ctypes.c_void_p(d_out), ctypes.c_void_p(stream or None)))
+
+    @staticmethod
+    def _hit_arrays(want, shape):
+        """Host arrays of the hit-record fields in `want` (planar vectors: (3,) + shape) and their struct."""
+        bad = set(want) - set(HIT_FIELDS)
+        if bad:
+            raise ValueError(f"unknown hit field(s) {sorted(bad)}; choose from {HIT_FIELDS}")
+        dt = {"prim": np.uint32, "flags": np.uint8}
+        arr = {k: np.zeros(((3,) if k in ("pos", "norm", "col") else ()) + shape, dt.get(k, np.float32))
+               for k in HIT_FIELDS if k in want}
+        return arr, WgtHitBuffers(**{k: a.ctypes.data for k, a in arr.items()})
+
+    @staticmethod
+    def _hit_dict(arr):
+        """Vectors last: (3,) + shape -> shape + (3,)."""
+        return {k: np.ascontiguousarray(np.moveaxis(a, 0, -1)) if k in ("pos", "norm", "col") else a
+                for k, a in arr.items()}
+
+    def trace_hits(self, start, direction, want=HIT_FIELDS):
+        """Whole hit records (wgt_trace_hits): a dict of the fields in `want`; prim (n,) uint32 and
+        dist (n,) as trace_rays, pos / norm / col (n, 3), flags (n,) uint8 (WGT_HIT_EMISSIVE |
+        WGT_HIT_FRONT_FACE)."""
+        start = np.asarray(start, np.float32).reshape(-1, 3)
+        direction = np.asarray(direction, np.float32).reshape(-1, 3)
+        n = len(start)
+        soa = np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32)
+        arr, bufs = self._hit_arrays(want, (n,))
+        self._check(self._L.wgt_trace_hits(self.h, ptr(soa), n, ctypes.byref(bufs)))
+        return self._hit_dict(arr)
+
+    def trace_hits_async(self, d_rays, n, prim=0, dist=0, pos=0, norm=0, col=0, flags=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = field not written): pos / norm / col
+        receive 3 planes of n floats."""
+        bufs = WgtHitBuffers(prim or None, dist or None, pos or None, norm or None, col or None, flags or None)
+        self._check(self._L.wgt_trace_hits_async(self.h, ctypes.c_void_p(d_rays), n, ctypes.byref(bufs),
+                                                 ctypes.c_void_p(stream or None)))
+
+    def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False):
+        """First-hit G-buffer (wgt_render_gbuffer): the hit record of sample 0's primary ray of each
+        pixel of the rectangle, (th, tw) and (th, tw, 3) arrays; rays=True adds that ray as
+        "origin" and "direction", (th, tw, 3) each."""
+        tw = W if tw is None else tw
+        th = H if th is None else th
+        arr, bufs = self._hit_arrays(want, (th, tw))
+        r = np.zeros((6, th, tw), np.float32) if rays else None
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        self._check(self._L.wgt_render_gbuffer(self.h, ptr(cam), W, H, x0, y0, tw, th, ctypes.byref(bufs), ptr(r)))
+        out = self._hit_dict(arr)
+        if rays:
+            out["origin"] = np.ascontiguousarray(np.moveaxis(r[:3], 0, -1))
+            out["direction"] = np.ascontiguousarray(np.moveaxis(r[3:], 0, -1))
+        return out
+
+    def render_gbuffer_async(self, cam, W, H, tw, th, d_tiles, n_tiles, prim=0, dist=0, pos=0, norm=0, col=0,
+                             flags=0, d_rays=0, stream=0):
+        """Tile-list G-buffer launch with device buffers (raw device addresses, 0 = NULL): n =
+        n_tiles * tw * th records at render_tiles_async's pixel offsets; d_rays: 6 planes of n floats."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        bufs = WgtHitBuffers(prim or None, dist or None, pos or None, norm or None, col or None, flags or None)
+        self._check(self._L.wgt_render_gbuffer_async(self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles),
+                                                     n_tiles, ctypes.byref(bufs), ctypes.c_void_p(d_rays or None),
+                                                     ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
