@@ -23,7 +23,8 @@
  *
  * Triangles/BVH are NEW semantics (the reference shader has none):
  * the triangle hit is min (t, index) over triangles that pass Moller-Trumbore and
- * whose own padded box contains t.  o_trace(..., brute=1) is that
+ * whose own padded box the ray crosses, with t clamped to that box's slab interval
+ * (DESIGN.md §3.4).  o_trace(..., brute=1) is that
  * spec by linear scan; the oracle's own median-split BVH must (and is tested to)
  * return the identical answer.
  */
@@ -422,10 +423,14 @@ static inline void tri_candidate(const o_scene *s, int i, v3 o, v3 d, const floa
                                  const float inv[3], float *best_t, uint32_t *best_i) {
   float t;
   if (!mt_test(o, d, &s->tris[i], &t)) return;
-  if (!(t < *best_t || (t == *best_t && (uint32_t)i < *best_i))) return;
+  /* the hit parameter is t clamped to the slab interval of the triangle's own box */
   float n, f;
   slab(ot, inv, &s->tbox[6 * i], &s->tbox[6 * i + 3], &n, &f);
-  if (!(n <= t && t <= f)) return;
+  if (!(n <= f)) return;
+  t = t < n ? n : t;
+  t = t > f ? f : t;
+  if (t < kRayMin || kRayMax < t) return;
+  if (!(t < *best_t || (t == *best_t && (uint32_t)i < *best_i))) return;
   *best_t = t;
   *best_i = (uint32_t)i;
 }

@@ -1,0 +1,594 @@
+"""Float64 ground truth for ray queries, written from geometry.  TEST INFRASTRUCTURE ONLY.
+
+Shared by tests/test_truth_f64.py (the oracle and the restatements) and tests/test_gpu_truth.py
+(the kernels).  Every other GPU test compares a kernel with the C oracle bit for bit, which pins
+the kernels to the oracle but not the oracle, or the triangle rule of DESIGN.md §3.4, to
+geometry.  Here the float32 inputs are widened to float64 and every primitive is intersected by
+a plain scan: no BVH, no boxes, no fp32 intermediates.  Quads and spheres are built from their
+corner data (pos, right, up; center, radius), not from the packed norm, w and d, so the restated
+constructors are checked too.
+
+Which rays can be checked.  fp32 and float64 legitimately disagree on a ray that passes an edge
+within rounding error, so each primitive gets, per ray, a first-order forward error bound of its
+fp32 evaluation: the same expression evaluated in float64 with the absolute value of every
+product, times gamma_n = n u / (1 - n u), u = 2^-24, for the n roundings on the longest path of
+that expression, divided by |det| (or the expression's own divisor).  That gives E_m for the
+inside margin (barycentrics, quad coordinates, the sphere's discriminant) and E_t for the ray
+parameter.  A ray is DECIDED when its float64 winner is inside by more than E_m, lies more than
+E_t inside [kRayMin, kRayMax], and every other primitive that could come out at a parameter not
+beyond the winner's (t - E_t <= t_win + E_t,win: this is also the runner-up condition) is outside
+by more than its own E_m.  On decided rays a caller demands the exact primitive (or an exact miss)
+and |t32 - t64| <= 4 E_t; the factor 4 covers the bound's first-order nature.  Undecided rays
+are only counted; an input set states the share of decided rays it must reach.
+
+The reference's non-geometric rejections are part of its specification and are honoured: a
+triangle with |det| < 1e-12 and a quad with |d . n| < kRayMin are not hit.  A primitive for which
+the bound cannot tell which side of such a threshold fp32 falls on makes its ray undecided.
+"""
+import functools
+
+import numpy as np
+
+U = 2.0 ** -24
+RAY_MIN = float(np.float32(0.001))  # kRayMin
+RAY_MAX = float(np.float32(1e20))   # kRayMax
+DET_MIN = float(np.float32(1e-12))  # mt_test's determinant threshold
+CAP_LATTICE, CAP_MESH = 0.95, 0.85  # required shares of decided rays
+TOL = 4.0                           # |t32 - t64| <= TOL * E_t
+
+
+def gamma(n):
+    return n * U / (1.0 - n * U)
+
+
+def _c(a):
+    """(n, 3) -> three (n, 1) float64 columns (rays)."""
+    a = np.asarray(a, np.float64)
+    return a[:, 0:1], a[:, 1:2], a[:, 2:3]
+
+
+def _r(a):
+    """(n, 3) -> three (1, n) float64 rows (primitives)."""
+    a = np.asarray(a, np.float64)
+    return a[None, :, 0], a[None, :, 1], a[None, :, 2]
+
+
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _across(a, b):
+    """cross with the absolute value of every product."""
+    return (abs(a[1] * b[2]) + abs(a[2] * b[1]), abs(a[2] * b[0]) + abs(a[0] * b[2]),
+            abs(a[0] * b[1]) + abs(a[1] * b[0]))
+
+
+def _dot(a, b):
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+
+
+def _adot(a, b):
+    """dot of |a| with b, b already a sum of absolute products."""
+    return abs(a[0]) * b[0] + abs(a[1]) * b[1] + abs(a[2]) * b[2]
+
+
+def _terms(t, Et, m, Em, ignore, amb):
+    """Normalise one primitive class: an ignored primitive never competes; an ambiguous one
+    (a threshold the bound cannot decide, or a NaN) competes with unbounded errors."""
+    bad = amb | ~(np.isfinite(t) & np.isfinite(m) & np.isfinite(Et) & np.isfinite(Em))
+    bad &= ~ignore
+    t = np.where(ignore, np.inf, np.where(bad, 1.0, t))
+    m = np.where(ignore, -np.inf, np.where(bad, 0.0, m))
+    Et = np.where(ignore, 0.0, np.where(bad, np.inf, Et))
+    Em = np.where(ignore, 0.0, np.where(bad, np.inf, Em))
+    return t, Et, m, Em
+
+
+def tri_terms(o, d, v0, e1, e2):
+    """Two-sided ray / triangle intersection of rays (R, 3) with triangles (T, 3): t, E_t, the
+    barycentric margin min(u, v, 1 - u - v) and its bound E_uv, each (R, T).
+
+    The bounds follow fp32 Moller-Trumbore (pvec = d x e2, det = e1 . pvec, tvec = o - v0,
+    u = tvec . pvec / det, qvec = tvec x e1, v = d . qvec / det, t = e2 . qvec / det): det has 5
+    roundings on its longest path, the numerators 6 (tvec 1, cross 2, dot 3) and the quotient 2
+    more; x = N / det gives |dx| <= (gamma_8 |N|_abs + |x| gamma_5 |det|_abs) / |det|."""
+    o, d, v0, e1, e2 = _c(o), _c(d), _r(v0), _r(e1), _r(e2)
+    with np.errstate(all="ignore"):
+        p, ap = _cross(d, e2), _across(d, e2)
+        det, adet = _dot(e1, p), _adot(e1, ap)
+        tv = (o[0] - v0[0], o[1] - v0[1], o[2] - v0[2])
+        q, aq = _cross(tv, e1), _across(tv, e1)
+        Edet = gamma(5) * adet
+        ad = abs(det)
+        Nu, Nv = _dot(tv, p), _dot(d, q)
+        u, v, t = Nu / det, Nv / det, _dot(e2, q) / det
+        rel = Edet / ad
+        Eu = gamma(8) * _adot(tv, ap) / ad + abs(u) * rel
+        Ev = gamma(8) * _adot(d, aq) / ad + abs(v) * rel
+        Et = gamma(8) * _adot(e2, aq) / ad + abs(t) * rel
+        Euv = Eu + Ev + U * (abs(u) + abs(v))
+        m = np.minimum(np.minimum(u, v), 1.0 - u - v)
+        # every product of det is exactly zero: fp32 computes det = 0 too, and rejects
+        ignore = (det == 0.0) & (adet == 0.0)
+        amb = ad - Edet < DET_MIN
+        # a determinant within its own rounding error of zero (a degenerate triangle, or a ray in
+        # the triangle's plane) still rejects for certain when a numerator certainly exceeds it:
+        # |u| > 1 or |v| > 1 whatever fp32 makes of det
+        top = (ad + Edet) * (1.0 + gamma(4))
+        ignore |= amb & ((abs(Nu) - gamma(6) * _adot(tv, ap) > top) | (abs(Nv) - gamma(6) * _adot(d, aq) > top))
+    return _terms(t, Et, m, Em=Euv, ignore=ignore, amb=amb)
+
+
+def quad_terms(o, d, pos, right, up):
+    """Rays with parallelograms pos + a right + b up, 0 <= a, b <= 1: t, E_t, the margin
+    min(a, 1 - a, b, 1 - b) and its bound.  n = right x up; t = (pos - o) . n / (d . n);
+    a = n . (h x up) / (n . n), b = n . (right x h) / (n . n), h = o + t d - pos.
+
+    fp32 works from the packed unit normal, d = n . pos and w = n / (n . n) (about 8 roundings
+    each), then t = (d - o . n) / (d . n) and a = w . (h x up): 16 roundings bound the longest
+    path of t, and a inherits the error of the hit point, E_p = E_t |d| + gamma_3 (|o| + |t d|)
+    + gamma_1 |pos|, through |w| |up| (b: |w| |right|), plus 16 roundings of its own."""
+    o, d, qp, r, up = _c(o), _c(d), _r(pos), _r(right), _r(up)
+    with np.errstate(all="ignore"):
+        n = _cross(r, up)
+        nn = _dot(n, n)
+        dn = _dot(d, n)
+        adn = abs(d[0] * n[0]) + abs(d[1] * n[1]) + abs(d[2] * n[2])
+        num = _dot((qp[0] - o[0], qp[1] - o[1], qp[2] - o[2]), n)
+        anum = sum(abs(qp[k] * n[k]) + abs(o[k] * n[k]) for k in range(3))
+        t = num / dn
+        Et = gamma(16) * anum / abs(dn) + abs(t) * gamma(16) * adn / abs(dn)
+        h = tuple(o[k] + t * d[k] - qp[k] for k in range(3))
+        a = _dot(n, _cross(h, up)) / nn
+        b = _dot(n, _cross(r, h)) / nn
+        nd = np.sqrt(_dot(d, d))
+        Ep = Et * nd + gamma(3) * (np.sqrt(_dot(o, o)) + abs(t) * nd) + U * np.sqrt(_dot(qp, qp))
+        wl = 1.0 / np.sqrt(nn)
+        an = tuple(abs(x) for x in n)
+        Ea = Ep * wl * np.sqrt(_dot(up, up)) + gamma(16) * _adot(an, _across(h, up)) / nn
+        Eb = Ep * wl * np.sqrt(_dot(r, r)) + gamma(16) * _adot(an, _across(r, h)) / nn
+        m = np.minimum(np.minimum(a, 1.0 - a), np.minimum(b, 1.0 - b))
+        # the reference rejects |d . n_unit| < kRayMin
+        dnu, Ednu = abs(dn) * wl, gamma(16) * adn * wl
+        ignore = dnu + Ednu < RAY_MIN
+        amb = ~ignore & (dnu - Ednu < RAY_MIN)
+    return _terms(t, Et, m, Em=np.maximum(Ea, Eb), ignore=ignore | (nn == 0.0), amb=amb)
+
+
+def sphere_terms(o, d, center, radius):
+    """Rays with spheres, as two candidates per sphere (columns 2k and 2k + 1): the near root
+    of |o + t d - c|^2 = r^2 and the far root, which the reference takes only when the near
+    one is outside [kRayMin, kRayMax].  The margin is r^2 - rho^2 = disc / (d . d), rho the
+    distance of the centre from the line.  disc = h^2 - a cc has 8 roundings on its longest path
+    (oc 1, dot 3, square 1, cc's subtraction, the product, the difference)."""
+    o, d, c = _c(o), _c(d), _r(center)
+    r = np.asarray(radius, np.float64)[None, :]
+    with np.errstate(all="ignore"):
+        oc = (o[0] - c[0], o[1] - c[1], o[2] - c[2])
+        a = _dot(d, d)
+        h = _dot(oc, d)
+        ah = abs(oc[0] * d[0]) + abs(oc[1] * d[1]) + abs(oc[2] * d[2])
+        cc = _dot(oc, oc) - r * r
+        disc = h * h - a * cc
+        Edisc = gamma(8) * (ah * ah + a * (_dot(oc, oc) + r * r))
+        m, Em = disc / a, Edisc / a
+        sq = np.sqrt(np.maximum(disc, 0.0))
+        Esq = Edisc / (2.0 * sq) + U * sq
+        t1, t2 = (-h - sq) / a, (-h + sq) / a
+        Et1 = (gamma(4) * ah + Esq) / a + gamma(3) * abs(t1)
+        Et2 = (gamma(4) * ah + Esq) / a + gamma(3) * abs(t2)
+        none = (m + Em < 0.0) | ((r == 0.0) & (m < 0.0) & (Edisc == 0.0))
+        near_in = (t1 - Et1 > RAY_MIN) & (t1 + Et1 < RAY_MAX)
+        near_out = (t1 + Et1 < RAY_MIN) | (t1 - Et1 > RAY_MAX)
+    n1 = _terms(t1, Et1, m, Em, ignore=none | near_out, amb=~(near_in | near_out))
+    n2 = _terms(t2, Et2, m, Em, ignore=none | near_in, amb=~(near_in | near_out))
+    return tuple(np.stack([x, y], axis=2).reshape(x.shape[0], -1) for x, y in zip(n1, n2))
+
+
+def decide(t, Et, m, Em):
+    """The closest primitive of each ray among the columns, and whether the ray is decided."""
+    R = t.shape[0]
+    rows = np.arange(R)
+    with np.errstate(all="ignore"):
+        hit = (m >= 0.0) & (t >= RAY_MIN) & (t <= RAY_MAX) & np.isfinite(Em)
+        tw = np.where(hit, t, np.inf)
+        win = np.argmin(tw, axis=1)
+        t_w = tw[rows, win]
+        found = np.isfinite(t_w)
+        Et_w = np.where(found, Et[rows, win], 0.0)
+        Em_w = np.where(found, Em[rows, win], 0.0)
+        m_w = np.where(found, m[rows, win], np.inf)
+        other = np.isfinite(t) | np.isinf(Et)
+        other[rows[found], win[found]] = False
+        tw[rows[found], win[found]] = np.inf
+        t_run = tw.min(axis=1)
+        lim = np.where(found, t_w + Et_w, RAY_MAX)
+        front = other & (t - Et <= lim[:, None]) & (t + Et >= RAY_MIN)
+        threat = front & (m + Em >= 0.0)
+        loser = other & ~hit & (t >= RAY_MIN) & (t < t_w[:, None])
+        front_margin = np.where(loser, m, -np.inf).max(axis=1)
+        ok_w = (m_w > Em_w) & (t_w - RAY_MIN > Et_w) & (t_w + Et_w < RAY_MAX)
+        decided = ~threat.any(axis=1) & np.where(found, ok_w, True)
+    return {"col": np.where(found, win, -1), "t": np.where(found, t_w, np.inf), "E_t": Et_w, "margin": m_w,
+            "E_m": Em_w, "front_margin": front_margin, "t_runner": t_run, "decided": decided}
+
+
+def _unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def scan(o, d, lights=None, quads=None, spheres=None, tris=None):
+    """Closest hit of rays (o, d) (float32 (R, 3)) on the scene, in float64, with the primitive
+    id in scan order (lights, quads, triangles, spheres; -1 for a miss), the decided mask, the
+    error bounds and the hit record: pos = o + t d, the unit geometric normal turned against
+    the ray, the front-face flag, dist = t |d|."""
+    o = np.ascontiguousarray(o, np.float32).astype(np.float64)
+    d = np.ascontiguousarray(d, np.float32).astype(np.float64)
+    lq = [a for a in (lights, quads) if a is not None and len(a)]
+    qpos = np.concatenate([a["pos"][:, :3] for a in lq]).astype(np.float64) if lq else np.zeros((0, 3))
+    qr = np.concatenate([a["right"][:, :3] for a in lq]).astype(np.float64) if lq else np.zeros((0, 3))
+    qu = np.concatenate([a["up"][:, :3] for a in lq]).astype(np.float64) if lq else np.zeros((0, 3))
+    nq = len(qpos)
+    nt = 0 if tris is None else len(tris)
+    if nt:
+        v0, e1, e2 = (tris[k][:, :3].astype(np.float64) for k in ("v0", "e1", "e2"))
+    ns = 0 if spheres is None else len(spheres)
+    if ns:
+        sc, sr = spheres["center"].astype(np.float64), spheres["radius"].astype(np.float64)
+    # column -> primitive id
+    ids = np.concatenate([np.arange(nq + nt), nq + nt + np.repeat(np.arange(ns), 2)]).astype(np.int64)
+    R = len(o)
+    step = max(1, 1_500_000 // max(1, len(ids)))
+    parts = []
+    for a in range(0, R, step):
+        oo, dd = o[a:a + step], d[a:a + step]
+        cls = []
+        if nq:
+            cls.append(quad_terms(oo, dd, qpos, qr, qu))
+        if nt:
+            cls.append(tri_terms(oo, dd, v0, e1, e2))
+        if ns:
+            cls.append(sphere_terms(oo, dd, sc, sr))
+        parts.append(decide(*(np.concatenate([c[k] for c in cls], axis=1) for k in range(4))))
+    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]} if parts else decide(*(np.zeros((0, 1)),) * 4)
+    col = out.pop("col")
+    prim = np.where(col >= 0, ids[np.maximum(col, 0)], -1)
+    out["prim"] = prim
+    t = np.where(prim >= 0, out["t"], 0.0)
+    pos = o + t[:, None] * d
+    n = np.zeros((R, 3))
+    k = (prim >= 0) & (prim < nq)
+    n[k] = np.cross(qr[prim[k]], qu[prim[k]])
+    k = (prim >= nq) & (prim < nq + nt)
+    if nt:
+        n[k] = np.cross(e1[prim[k] - nq], e2[prim[k] - nq])
+    k = prim >= nq + nt
+    if ns:
+        n[k] = pos[k] - sc[prim[k] - nq - nt]
+    with np.errstate(all="ignore"):
+        n = np.where((prim >= 0)[:, None], _unit(n), 0.0)
+    ff = (np.einsum("ij,ij->i", d, n) < 0.0) & (prim >= 0)
+    out["pos"] = np.where((prim >= 0)[:, None], pos, 0.0)
+    out["norm"] = np.where(ff[:, None], n, -n)
+    out["front"] = ff
+    out["dnorm"] = np.linalg.norm(d, axis=1)
+    out["dist"] = out["t"] * out["dnorm"]
+    out["o"], out["d"] = o, d
+    out["inv_r"] = np.zeros(R)  # spheres: 1 / radius (check_records)
+    if ns:
+        ks = prim >= nq + nt
+        with np.errstate(all="ignore"):
+            out["inv_r"][ks] = 1.0 / sr[prim[ks] - nq - nt]
+    return out
+
+
+def scan_tris(o, d, tris):
+    """scan on the triangles alone: prim is the triangle index (OracleScene.trace_tris)."""
+    return scan(o, d, tris=tris)
+
+
+def take(truth, k):
+    return {f: v[k] for f, v in truth.items()}
+
+
+def tri_view(truth, nlq, nt):
+    """The truth of a whole scene as the triangle query alone sees it (OracleScene.trace_tris):
+    a decided triangle winner is the closest triangle too, and a decided miss misses every
+    triangle; a ray whose winner is a quad or a sphere says nothing about the triangles behind it
+    and counts as undecided."""
+    out = dict(truth)
+    tri = (truth["prim"] >= nlq) & (truth["prim"] < nlq + nt)
+    out["prim"] = np.where(tri, truth["prim"] - nlq, -1)
+    out["decided"] = truth["decided"] & (tri | (truth["prim"] < 0))
+    return out
+
+
+# ------------------------------------------------------------------ checks shared by both suites
+def _own_dist(truth):
+    """The roundings of ray_dist = |fl(o + fl(t d)) - o| itself, beyond the error of t: 6 on the
+    path of t d (product, sum, difference, square, sum, root) and the absolute u |o| that the
+    rounding of o + t d loses when the origin is far from the hit.  No fp32 result can be closer
+    than this, so it is added to 4 E_t |d|."""
+    return gamma(6) * truth["dist"] + gamma(2) * np.linalg.norm(truth["o"], axis=1)
+
+
+def _own_pos(truth):
+    """The roundings of pos = fl(o + fl(t d)) per component (half an ulp of the position and
+    more is lost whatever t is), added to 4 E_t |d|."""
+    return gamma(2) * (np.abs(truth["o"]) + np.abs(truth["t"][:, None] * truth["d"]))
+
+
+def check_closest(name, truth, prim32, t32=None, dist32=None, miss=0xFFFFFFFF):
+    """On decided rays: the exact primitive or an exact miss, |t32 - t64| <= 4 E_t and
+    |dist32 - dist64| <= 4 E_t |d| + the rounding of the distance expression itself
+    (_own_dist).  Returns the largest observed (error - own rounding) / E_t (printed by the
+    tests, recorded in DESIGN.md §3.4)."""
+    dec = truth["decided"]
+    want = np.where(truth["prim"] >= 0, truth["prim"], miss).astype(np.int64)
+    got = np.asarray(prim32).astype(np.int64)
+    bad = np.flatnonzero(dec & (got != want))
+    dropped = int(np.sum(dec & (got != want) & (got == miss)))
+    assert bad.size == 0, (f"{name}: {bad.size} of {int(dec.sum())} decided rays return another primitive than float64 "
+                           f"({dropped} of them drop the hit); first: ray {bad[0]} got {got[bad[0]]} want {want[bad[0]]} "
+                           f"t64 {truth['t'][bad[0]]!r} margin {truth['margin'][bad[0]]:.3g} E_m {truth['E_m'][bad[0]]:.3g}")
+    k = dec & (truth["prim"] >= 0)
+    worst = 0.0
+    for what, got32 in (("t", t32), ("dist", dist32)):
+        if got32 is None or not k.any():
+            continue
+        ref = truth[what][k]
+        E = truth["E_t"][k] * (1.0 if what == "t" else truth["dnorm"][k])
+        own = 0.0 if what == "t" else _own_dist(truth)[k]
+        err = np.maximum(np.abs(np.asarray(got32, np.float64)[k] - ref) - own, 0.0)
+        with np.errstate(all="ignore"):
+            ratio = np.where(err > 0, err / E, 0.0)
+        i = int(np.argmax(ratio))
+        worst = max(worst, float(ratio[i]))
+        assert ratio[i] <= TOL, (f"{name}: {what} is off by {ratio[i]:.2f} E_t (> {TOL}) on decided ray "
+                                 f"{np.flatnonzero(k)[i]}: got {np.asarray(got32)[k][i]!r} want {ref[i]!r} E {E[i]:.3g}")
+    return worst
+
+
+ULP1 = 2.0 ** -23  # the ulp of 1.0: a unit normal's components are compared in it
+
+
+def check_records(name, truth, rec, front_bit=2):
+    """On decided hits: pos within 4 E_t |d| (+ _own_pos) of o + t d per component, norm within
+    4 ulp (of 1.0) of the float64 unit normal turned against the ray, the front-face flag exact.
+    A sphere's normal (pos - c) / r is computed from the hit point and inherits the position's
+    tolerance over r.  Returns the largest observed pos error / (E_t |d|) (less its own rounding)
+    and norm error in ulp."""
+    k = truth["decided"] & (truth["prim"] >= 0)
+    if not k.any():
+        return 0.0, 0.0
+    E = (truth["E_t"] * truth["dnorm"])[k][:, None]
+    own = _own_pos(truth)[k]
+    perr = np.maximum(np.abs(np.asarray(rec["pos"], np.float64)[k] - truth["pos"][k]) - own, 0.0)
+    with np.errstate(all="ignore"):
+        pr = np.where(perr > 0, perr / E, 0.0).max(axis=1)
+    ntol = 4.0 * ULP1 + truth["inv_r"][k] * (TOL * E[:, 0] + own.max(axis=1) + gamma(2) * np.abs(truth["pos"][k]).max(axis=1))
+    nerr = np.abs(np.asarray(rec["norm"], np.float64)[k] - truth["norm"][k]).max(axis=1)
+    ff = (np.asarray(rec["flags"])[k] & front_bit) != 0
+    i, j = int(np.argmax(pr)), int(np.argmax(nerr / ntol))
+    rays = np.flatnonzero(k)
+    assert pr[i] <= TOL, f"{name}: pos is off by {pr[i]:.2f} E_t |d| on decided ray {rays[i]}"
+    assert nerr[j] <= ntol[j], f"{name}: norm is off by {nerr[j] / ULP1:.2f} ulp on decided ray {rays[j]} (allowed {ntol[j] / ULP1:.2f})"
+    bad = np.flatnonzero(ff != truth["front"][k])
+    assert bad.size == 0, f"{name}: {bad.size} front-face flags differ on decided rays; first: ray {rays[bad[0]]}"
+    plane = truth["inv_r"][k] == 0
+    return float(pr[i]), float((nerr[plane] / ULP1).max()) if plane.any() else 0.0
+
+
+def check_share(name, truth, cap):
+    share = float(np.mean(truth["decided"])) if len(truth["decided"]) else 1.0
+    assert share >= cap, f"{name}: only {share:.3f} of the rays are decided (cap {cap})"
+    return share
+
+
+# ------------------------------------------------------------------------------ input sets
+def _wgt():
+    import webgputracer_amd
+
+    return webgputracer_amd
+
+
+def _interior(rng, n, margin):
+    """Barycentrics (u, v) with min(u, v, 1 - u - v) >= margin."""
+    b = margin + (1.0 - 3.0 * margin) * rng.dirichlet((1.0, 1.0, 1.0), n)
+    return b[:, 0:1], b[:, 1:2]
+
+
+LATTICE_SIZES, LATTICE_OFFSETS, LATTICE_LENGTHS = (0.01, 1.0, 30.0), (0.0, 250.0), (100.0, 800.0, 1e4, 1e5)
+LATTICE_SCENES = [(s, off, flat) for s in LATTICE_SIZES for off in LATTICE_OFFSETS for flat in (True, False)]
+
+
+def lattice_lengths(size):
+    """The tested range: length / size <= 1e5 (beyond it E_uv passes the 0.1 aiming margin)."""
+    return [L for L in LATTICE_LENGTHS if L / size <= 1e5 * (1 + 1e-9)]
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_tris(size, offset, flat):
+    """About 1500 triangles of the given size on lattices with spacing 8 size, at coordinates
+    near `offset`.  flat: three patches of triangles that are flat along x, y and z (all three
+    vertices share that coordinate exactly); else general triangles on one lattice in x / y."""
+    w = _wgt()
+    rng = np.random.default_rng([7, int(size * 100), int(offset), int(flat)])
+
+    def shapes(n, dims):
+        out = np.zeros((n, 3, 3))
+        todo = np.arange(n)
+        while todo.size:  # redraw slivers and steep ones: projected area >= 0.1 size^2
+            p = np.zeros((todo.size, 3, 3))
+            p[:, :, dims] = rng.uniform(-0.5, 0.5, (todo.size, 3, len(dims)))
+            nrm = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+            area = 0.5 * (np.abs(nrm[:, 2]) if len(dims) == 3 else np.linalg.norm(nrm, axis=1))
+            out[todo] = p
+            todo = todo[area < 0.1]
+        return out * size
+
+    pitch = 8.0 * size
+    if flat:
+        verts, axis = [], []
+        for a in range(3):
+            i, j = np.meshgrid(np.arange(22), np.arange(23), indexing="ij")
+            u, v = [k for k in range(3) if k != a]
+            c = np.zeros((i.size, 3))
+            c[:, u] = (i.ravel() + 30 * a) * pitch
+            c[:, v] = (j.ravel() + 30 * a) * pitch
+            verts.append(shapes(i.size, [u, v]) + c[:, None, :] + offset)
+            axis.append(np.full(i.size, a))
+        verts, axis = np.concatenate(verts), np.concatenate(axis)
+    else:
+        i, j = np.meshgrid(np.arange(39), np.arange(39), indexing="ij")
+        c = np.stack([i.ravel() * pitch, j.ravel() * pitch, np.zeros(i.size)], axis=1)
+        verts, axis = shapes(i.size, [0, 1, 2]) + c[:, None, :] + offset, np.full(i.size, 2)
+    tris = w.make_triangles(verts.astype(np.float32))
+    return tris, axis
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_rays(size, offset, flat, n_per=125):
+    """Rays at interior points (barycentric margin >= 0.1) of random lattice triangles, for every
+    tested length, from both sides, as d = target - o and as unit directions.  flat: within
+    1e-3 rad of the triangle's flat axis; else within 45 degrees of z up to length / size =
+    1e4 and within 3 degrees above it: E_uv grows as (length / size) / cos(incidence), about
+    gamma_8 1e5 = 0.05 at normal incidence at the top of the range, so at oblique incidence
+    it passes the 0.1 aiming margin there and the rays would not be decidable."""
+    tris, axis = lattice_tris(size, offset, flat)
+    rng = np.random.default_rng([11, int(size * 100), int(offset), int(flat)])
+    v0, e1, e2 = (tris[k][:, :3].astype(np.float64) for k in ("v0", "e1", "e2"))
+    O, D, tag = [], [], []
+    for length in lattice_lengths(size):
+        for unit in (False, True):
+            k = rng.integers(0, len(tris), n_per)
+            bu, bv = _interior(rng, n_per, 0.1)
+            target = v0[k] + bu * e1[k] + bv * e2[k]
+            ang = rng.uniform(0, 1e-3 if flat else (np.pi / 4 if length / size <= 1e4 else np.radians(3.0)), n_per)
+            phi = rng.uniform(0, 2 * np.pi, n_per)
+            sgn = rng.choice([-1.0, 1.0], n_per)
+            a = axis[k]
+            dirs = np.zeros((n_per, 3))
+            rows = np.arange(n_per)
+            dirs[rows, a] = sgn * np.cos(ang)
+            dirs[rows, (a + 1) % 3] = np.sin(ang) * np.cos(phi)
+            dirs[rows, (a + 2) % 3] = np.sin(ang) * np.sin(phi)
+            o = (target - length * dirs).astype(np.float32)
+            d = target - o.astype(np.float64)
+            if unit:
+                d = _unit(d)
+            O.append(o)
+            D.append(d.astype(np.float32))
+            tag += [(length, unit)] * n_per
+    return np.concatenate(O), np.concatenate(D), tag
+
+
+def tri_scene(far_sphere=False):
+    """What a triangle scene needs besides its triangles (an upload wants a light and a sphere):
+    the Cornell light and the reference's dummy sphere of radius 0, which sits at the origin;
+    far_sphere moves it to (-1e4, -1e4, -1e4), off every lattice ray's line (a lattice at the
+    origin seen from 1e5 away would have fp32 unable to tell whether its rays pass through it)."""
+    L, _, S = _wgt().cornell_scene()
+    S = S.copy()
+    if far_sphere:
+        S["center"][0] = (-1e4, -1e4, -1e4)
+    return L, S
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_truth(size, offset, flat):
+    o, d, _ = lattice_rays(size, offset, flat)
+    L, S = tri_scene(far_sphere=True)
+    return scan(o, d, L, None, S, lattice_tris(size, offset, flat)[0])
+
+
+def _mesh_rays(tris, n, rng, margin=0.02):
+    """From random points in the Cornell box to interior points of random triangles, as the
+    parity tests draw them; every other ray with a unit direction."""
+    v0, e1, e2 = (tris[k][:, :3].astype(np.float64) for k in ("v0", "e1", "e2"))
+    o = rng.uniform(5, 550, (n, 3)).astype(np.float32)
+    k = rng.integers(0, len(tris), n)
+    bu, bv = _interior(rng, n, margin)
+    d = v0[k] + bu * e1[k] + bv * e2[k] - o
+    d[1::2] = _unit(d[1::2])
+    return o, d.astype(np.float32)
+
+
+def _perpendicular_rays(tris, n, away, rng, margin=0.1):
+    """Perpendicular rays at axis-aligned triangles from `away`, from either side."""
+    v0, e1, e2 = (tris[k][:, :3].astype(np.float64) for k in ("v0", "e1", "e2"))
+    flat = np.stack([(e1[:, a] == 0) & (e2[:, a] == 0) for a in range(3)], axis=1)
+    idx = np.flatnonzero(flat.any(axis=1))
+    k = rng.choice(idx, n)
+    a = np.argmax(flat[k], axis=1)
+    bu, bv = _interior(rng, n, margin)
+    target = v0[k] + bu * e1[k] + bv * e2[k]
+    dirs = np.zeros((n, 3))
+    dirs[np.arange(n), a] = rng.choice([-1.0, 1.0], n)
+    o = (target - away * dirs).astype(np.float32)
+    return o, dirs.astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def bunny_set():
+    """procedural_mesh("bunny", 2000) with 2000 box-to-triangle rays: (tris, o, d, truth of the
+    scene tri_scene() + tris)."""
+    tris = _wgt().procedural_mesh("bunny", 2000)
+    o, d = _mesh_rays(tris, 2000, np.random.default_rng(21))
+    L, S = tri_scene()
+    return tris, o, d, scan(o, d, L, None, S, tris)
+
+
+@functools.lru_cache(maxsize=None)
+def sponza_set():
+    """A sponza stand-in of about 20,000 triangles: 600 box-to-triangle rays and 300
+    perpendicular rays each from 50 and 300 away at its axis-aligned triangles."""
+    tris = _wgt().procedural_mesh("sponza", 20000)
+    rng = np.random.default_rng(22)
+    parts = [_mesh_rays(tris, 600, rng), _perpendicular_rays(tris, 300, 50.0, rng),
+             _perpendicular_rays(tris, 300, 300.0, rng)]
+    o, d = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    L, S = tri_scene()
+    return tris, o, d, scan(o, d, L, None, S, tris)
+
+
+@functools.lru_cache(maxsize=None)
+def cornell_set():
+    """The Cornell light and quads and a real sphere (radius 50): 1000 rays from inside the box
+    with unit directions, 1000 from 1500 away aimed into it (back faces of the walls), d = target - o."""
+    L, Q, S = _wgt().cornell_scene()
+    S = np.concatenate([S, S])
+    S[1]["center"] = (400, 400, 278)
+    S[1]["radius"] = 50
+    rng = np.random.default_rng(23)
+    o1 = rng.uniform(5, 550, (1000, 3)).astype(np.float32)
+    d1 = _unit(rng.normal(size=(1000, 3))).astype(np.float32)
+    o2 = (277.5 + 1500.0 * _unit(rng.normal(size=(1000, 3)))).astype(np.float32)
+    d2 = (rng.uniform(5, 550, (1000, 3)) - o2).astype(np.float32)
+    o, d = np.concatenate([o1, o2]), np.concatenate([d1, d2])
+    return L, Q, S, o, d, scan(o, d, L, Q, S)
+
+
+@functools.lru_cache(maxsize=None)
+def flat_box_mesh(n=4):
+    """An axis-aligned box [0, 3]^3 of 12 n^2 flat triangles (n = 4: 192), the kind of mesh an
+    OBJ file modelled at unit scale near the origin holds.  The vertices inside each face are
+    moved within the face (the box stays flat and watertight), so the edges are general in-plane
+    vectors: with every edge on the grid Moller-Trumbore's products are nearly exact and the
+    mesh would test nothing."""
+    rng = np.random.default_rng(31)
+    tris = []
+    g = np.arange(n + 1) * (3.0 / n)
+    for a in range(3):
+        u, v = [k for k in range(3) if k != a]
+        for side in (0.0, 3.0):
+            P = np.zeros((n + 1, n + 1, 3))
+            P[:, :, a] = side
+            P[:, :, u], P[:, :, v] = g[:, None], g[None, :]
+            P[1:n, 1:n, u] += rng.uniform(-0.3, 0.3, (n - 1, n - 1)) * (3.0 / n)
+            P[1:n, 1:n, v] += rng.uniform(-0.3, 0.3, (n - 1, n - 1)) * (3.0 / n)
+            for i in range(n):
+                for j in range(n):
+                    c = (P[i, j], P[i + 1, j], P[i + 1, j + 1], P[i, j + 1])
+                    tris += [(c[0], c[1], c[2]), (c[0], c[2], c[3])]
+    return _wgt().make_triangles(np.array(tris, np.float32))

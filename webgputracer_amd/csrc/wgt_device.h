@@ -219,9 +219,11 @@ __device__ __forceinline__ void simt_count(uint32_t& wave, uint32_t& lane) {
 }
 
 // One triangle test of a 64-B record (wgt_geom.h kTriRecordBytes) held in registers:
-// Moller-Trumbore, then for a candidate that beats (bt, bi) the slab check against the
-// triangle's own padded box.  inv: 1/d.  Returns true with (tt, idx)
-// when the triangle becomes the closest hit.
+// Moller-Trumbore, then for every triangle that passes it the slab interval [bn, bf] of the
+// triangle's own padded box: an empty interval rejects, and the hit parameter
+// is t clamped to it (bn <= bf and no NaN, so the median of the three is the clamp: one
+// v_med3_f32), rejected when the clamp leaves [kRayMin, kRayMax].  Only then the comparison
+// with (bt, bi).  inv: 1/d.  Returns true with (tt, idx) when the triangle becomes the closest hit.
 // SHORT: mt_test's short reciprocal (render rays only, wgt_geom.h).
 template <bool SHORT>
 __device__ __forceinline__ bool tri_test_rec(float4 A, float4 B, float4 C, float4 D, f3 o, f3 d, f3 ot, f3 inv,
@@ -230,10 +232,14 @@ __device__ __forceinline__ bool tri_test_rec(float4 A, float4 B, float4 C, float
   idx = __float_as_uint(A.w);
   const f3 blo = f3{B.w, C.w, D.x}, bhi = f3{D.y, D.z, D.w};
   if (!mt_test<SHORT>(o, d, v0, e1, e2, tt)) return false;
-  if (!(tt < bt || (tt == bt && idx < bi))) return false;
   float bn, bf;
   slab(ot, inv, blo, bhi, bn, bf);
-  return bn <= tt && tt <= bf;
+  tt = __builtin_amdgcn_fmed3f(tt, bn, bf);
+  // One predicate, no branch (nested early-outs here cost the triangle step more exec-mask
+  // bookkeeping than the three compares they saved).  The clamp cannot leave the range upwards
+  // unnoticed: an accepted t is <= bt <= kRayMax (bt starts at kRayMax, or is a quad's t, an
+  // earlier triangle's or the occlusion bound).  For an empty interval tt is meaningless and unused.
+  return (bn <= bf) & (tt >= kRayMin) & ((tt < bt) | ((tt == bt) & (idx < bi)));
 }
 // The same for the record at byte offset lf: all four float4 loaded at once (the padded box D,
 // for a candidate closest hit, used to be loaded in the branch, a second dependent round trip).

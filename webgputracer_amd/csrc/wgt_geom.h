@@ -4,12 +4,16 @@
 // v0, e1 = v1 - v0, e2 = v2 - v0 (src/objects/triangle.cpp:9-11), which are
 // what the kernel consumes.
 //
-// Spec: a triangle is hit at t iff Moller-Trumbore passes with t in
-// [kRayMin, kRayMax] AND t lies inside the slab interval of the triangle's own
-// padded box (tri_box).  The closest triangle is the minimum (t, index).  Node
-// boxes are unions of tri boxes and use the same slab formula, so node tests
-// are conservative bit-for-bit (rounding is monotone) and BVH traversal returns
-// exactly the brute-force answer.
+// Spec: a triangle is a candidate iff Moller-Trumbore passes with t in
+// [kRayMin, kRayMax] AND the ray's slab interval [near, far] of the triangle's
+// own padded box (tri_box) is not empty.  Its hit parameter is t clamped to
+// [near, far], rejected if the clamp leaves [kRayMin, kRayMax].  (Demanding
+// near <= t <= far instead dropped hits well inside flat triangles: their
+// interval is a few ulps of t wide, narrower than Moller-Trumbore's own
+// cancellation error in t.)  The closest triangle is the minimum (clamped t,
+// index).  Node boxes are unions of tri boxes and use the same slab formula,
+// so a node's interval contains every clamped t below it bit for bit (rounding
+// is monotone) and BVH traversal returns exactly the brute-force answer.
 #pragma once
 
 #include "wgt_math.h"
@@ -102,8 +106,8 @@ WGT_HD bool mt_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& tout) {
 //   A = (v0.xyz, original index bits)   B = (e1.xyz, box.lo.x)
 //   C = (e2.xyz, box.lo.y)              D = (box.lo.z, box.hi.xyz)
 // A-C feed Moller-Trumbore; D (same 128-B line, loaded with A-C) is used only for a
-// candidate closest hit, to check t against the triangle's own padded box (tri_box,
-// computed by the host builder with the same fp32 operations).
+// triangle that passes it, to clamp t to the slab interval of the triangle's own padded
+// box (tri_box, computed by the host builder with the same fp32 operations).
 constexpr int kTriRecordFloats = 16;  // the host / exported record (wgt_bvh_build)
 // The device record the kernels walk (by byte offsets) is the 64-B record above.  Records
 // without the padded box (40 B, round 3; 48 B with 16-B aligned loads, round 6) load one

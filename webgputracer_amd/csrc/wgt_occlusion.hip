@@ -27,7 +27,12 @@ namespace wgt {
 namespace {
 
 // The bound t_hi on the ray parameter: every primitive accepted at parameter t >= kRayMin
-// with ray_dist < m has t <= t_hi.
+// with ray_dist < m has t <= t_hi.  For a triangle t is the hit parameter of the spec, the
+// Moller-Trumbore t clamped to the triangle's own slab interval (tri_test_rec): that is the
+// t its ray_dist is computed from, and tri_test_rec compares that t with the bound, so the
+// derivation below never sees the unclamped value.  The clamped t lies in the triangle's
+// interval, hence in every ancestor's, so a node entered beyond t_hi still holds no
+// triangle with t <= t_hi.
 //
 // ray_dist = fl(sqrt(fl(v . v))), v_i = fl(fl(o_i + fl(t d_i)) - o_i).  With u = 2^-24 and
 // every operation rounding by a factor within 1 +- u:
