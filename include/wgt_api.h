@@ -242,7 +242,15 @@ int wgt_render_tiles_stats(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W
 /* ---- closest-hit queries (sample_hit, path_tracer.wgsl:290-310) ---------- */
 /* Rays as SoA host arrays ox,oy,oz,dx,dy,dz (each n floats, packed in that order
  * in `rays`, i.e. rays[k*n + i]).  Writes prim id (lights, quads, triangles,
- * spheres numbered consecutively; 0xffffffff = miss) and hit distance. */
+ * spheres numbered consecutively; 0xffffffff = miss) and hit distance.
+ * Rays are not validated.  The answers equal the reference's arithmetic for any finite ray,
+ * which outside the scene limits (coordinates within 2^40) means: a ray exactly parallel to an
+ * axis (a direction component below 2^-87 in magnitude, which the triangle boxes' slab test
+ * replaces by +-2^-87) misses every triangle once its origin component on that axis reaches
+ * 2^41 in magnitude, because the slab offset o/d overflows; and a ray with |d| |o - c| above
+ * 1.8e19 for a sphere centre c returns that sphere with a NaN distance (the discriminant is
+ * inf - inf, and the reference accepts a NaN).  The same holds for wgt_trace_hits and
+ * wgt_occluded_rays (a NaN distance is below no limit). */
 int wgt_trace_rays(wgt_ctx *ctx, const float *rays, uint32_t n, uint32_t *prim_id, float *dist);
 int wgt_trace_rays_async(wgt_ctx *ctx, const float *d_rays, uint32_t n, uint32_t *d_prim_id,
                          float *d_dist, void *stream);

@@ -374,13 +374,30 @@ static void tri_box(const o_tri *t, float lo[3], float hi[3]) {
   }
 }
 
-/* Slab spec: inverse direction with |d| < 1e-30 replaced by
- * copysign(1e-30, d); per plane t = fma(b, inv, -(o*inv)). */
+/* Slab spec: inverse direction with |d| < 2^-87 replaced by
+ * copysign(2^-87, d); per plane t = fma(b, inv, -(o*inv)).
+ * Why 2^-87 (the clamp was 1e-30 until the float64 tests met axis-parallel rays on
+ * large scenes: o * 1e30 overflows for |o| > 3.4e8, the offset is then infinite, both
+ * planes of the axis come out at the same infinity and every triangle is missed):
+ *  - |inv| <= 2^87, so o * inv is finite for every |o| < 2^41: all scene coordinates,
+ *    cameras and hit points under the 2^40 limit.  A caller ray that is parallel to an
+ *    axis still overflows from |o| >= 2^41 on that axis.
+ *  - with ot finite, fma(b, inv, ot) has finite operands: it is never NaN, and where it
+ *    overflows the exact b * inv + ot is beyond 2^128 while ot's rounding moved it by
+ *    at most 2^104, so the infinity has the sign of (b - o) * inv.
+ *  - on a clamped axis with the origin inside the box's unpadded extent, the planes lie
+ *    at -(o - lo) * 2^87 and (hi - o) * 2^87, at least 0.99 pad * 2^87 >= 0.99e-6
+ *    * 2^87 = 1.53e20 > kRayMax away on either side (hi = fl(mx + pad) loses at most half
+ *    an ulp of mx, under 0.6 % of pad >= 1e-5 |mx| + 1e-6; the fma is one rounding of the
+ *    exact (hi - o) * 2^87): the axis does not narrow [near, far]
+ *    inside [-kRayMax, kRayMax] and the clamp of an accepted t to it moves nothing.  (The
+ *    next power of two, 2^-86, gives 7.7e19 and would; 2^-88 halves the finite range.) */
+#define SLAB_DIR_MIN 0x1p-87f
 static inline void inv_dir(v3 d, float inv[3]) {
   float dd[3] = {d.x, d.y, d.z};
   for (int c = 0; c < 3; ++c) {
     float x = dd[c];
-    if (fabs_w(x) < 1e-30f) x = copysignf(1e-30f, x);
+    if (fabs_w(x) < SLAB_DIR_MIN) x = copysignf(SLAB_DIR_MIN, x);
     inv[c] = 1.0f / x;
   }
 }

@@ -32,6 +32,7 @@ import numpy as np
 U = 2.0 ** -24
 RAY_MIN = float(np.float32(0.001))  # kRayMin
 RAY_MAX = float(np.float32(1e20))   # kRayMax
+FLT_MAX = float(np.finfo(np.float32).max)
 DET_MIN = float(np.float32(1e-12))  # mt_test's determinant threshold
 CAP_LATTICE, CAP_MESH = 0.95, 0.85  # required shares of decided rays
 TOL = 4.0                           # |t32 - t64| <= TOL * E_t
@@ -160,7 +161,14 @@ def sphere_terms(o, d, center, radius):
     of |o + t d - c|^2 = r^2 and the far root, which the reference takes only when the near
     one is outside [kRayMin, kRayMax].  The margin is r^2 - rho^2 = disc / (d . d), rho the
     distance of the centre from the line.  disc = h^2 - a cc has 8 roundings on its longest path
-    (oc 1, dot 3, square 1, cc's subtraction, the product, the difference)."""
+    (oc 1, dot 3, square 1, cc's subtraction, the product, the difference).
+
+    Also returns the (R, S) mask of the spheres whose fp32 discriminant is certainly inf - inf:
+    h^2 and a cc both beyond FLT_MAX (|d| |o - c| above 1.8e19: long unnormalised rays across a
+    scene of 2^30 and more).  The reference rejects `disc < 0` and roots outside the range, a NaN
+    passes both, so it accepts such a sphere with a NaN distance over whatever was hit before
+    (occlusion queries); that is honoured like its other non-geometric rules.  Such
+    a sphere does not compete geometrically; one that may or may not overflow is ambiguous."""
     o, d, c = _c(o), _c(d), _r(center)
     r = np.asarray(radius, np.float64)[None, :]
     with np.errstate(all="ignore"):
@@ -178,11 +186,17 @@ def sphere_terms(o, d, center, radius):
         Et1 = (gamma(4) * ah + Esq) / a + gamma(3) * abs(t1)
         Et2 = (gamma(4) * ah + Esq) / a + gamma(3) * abs(t2)
         none = (m + Em < 0.0) | ((r == 0.0) & (m < 0.0) & (Edisc == 0.0))
+        # fp32 overflow of h^2 and a cc, each with the error bound of its factors on either side
+        Eh, Ecc = gamma(4) * ah, gamma(4) * (_dot(oc, oc) + r * r)
+        nan = ((abs(h) - Eh) ** 2 > FLT_MAX * 1.001) & (a * (cc - Ecc) > FLT_MAX * 1.001)
+        maybe = ((abs(h) + Eh) ** 2 >= FLT_MAX * 0.999) | (a * (abs(cc) + Ecc) >= FLT_MAX * 0.999)
+        none = (none & ~maybe) | nan
+        over = maybe & ~nan
         near_in = (t1 - Et1 > RAY_MIN) & (t1 + Et1 < RAY_MAX)
         near_out = (t1 + Et1 < RAY_MIN) | (t1 - Et1 > RAY_MAX)
-    n1 = _terms(t1, Et1, m, Em, ignore=none | near_out, amb=~(near_in | near_out))
-    n2 = _terms(t2, Et2, m, Em, ignore=none | near_in, amb=~(near_in | near_out))
-    return tuple(np.stack([x, y], axis=2).reshape(x.shape[0], -1) for x, y in zip(n1, n2))
+    n1 = _terms(t1, Et1, m, Em, ignore=none | (near_out & ~over), amb=~(near_in | near_out) | over)
+    n2 = _terms(t2, Et2, m, Em, ignore=none | (near_in & ~over), amb=~(near_in | near_out) | over)
+    return tuple(np.stack([x, y], axis=2).reshape(x.shape[0], -1) for x, y in zip(n1, n2)), nan
 
 
 def decide(t, Et, m, Em):
@@ -221,7 +235,10 @@ def scan(o, d, lights=None, quads=None, spheres=None, tris=None):
     """Closest hit of rays (o, d) (float32 (R, 3)) on the scene, in float64, with the primitive
     id in scan order (lights, quads, triangles, spheres; -1 for a miss), the decided mask, the
     error bounds and the hit record: pos = o + t d, the unit geometric normal turned against
-    the ray, the front-face flag, dist = t |d|."""
+    the ray, the front-face flag, dist = t |d|.  nan_prim: the last sphere whose fp32
+    discriminant certainly overflows to NaN (sphere_terms), which the reference then returns with
+    a NaN distance whatever the geometry says, or -1; prim and the record stay the geometric ones
+    (the triangle query, tri_view, is not affected by a sphere)."""
     o = np.ascontiguousarray(o, np.float32).astype(np.float64)
     d = np.ascontiguousarray(d, np.float32).astype(np.float64)
     lq = [a for a in (lights, quads) if a is not None and len(a)]
@@ -243,14 +260,20 @@ def scan(o, d, lights=None, quads=None, spheres=None, tris=None):
     for a in range(0, R, step):
         oo, dd = o[a:a + step], d[a:a + step]
         cls = []
+        nanp = np.full(len(oo), -1, np.int64)
         if nq:
             cls.append(quad_terms(oo, dd, qpos, qr, qu))
         if nt:
             cls.append(tri_terms(oo, dd, v0, e1, e2))
         if ns:
-            cls.append(sphere_terms(oo, dd, sc, sr))
+            terms, nan = sphere_terms(oo, dd, sc, sr)
+            cls.append(terms)
+            nanp = np.where(nan.any(axis=1), nq + nt + ns - 1 - np.argmax(nan[:, ::-1], axis=1), -1)
         parts.append(decide(*(np.concatenate([c[k] for c in cls], axis=1) for k in range(4))))
-    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]} if parts else decide(*(np.zeros((0, 1)),) * 4)
+        parts[-1]["nan_prim"] = nanp
+    if not parts:
+        parts = [dict(decide(*(np.zeros((0, 1)),) * 4), nan_prim=np.zeros(0, np.int64))]
+    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
     col = out.pop("col")
     prim = np.where(col >= 0, ids[np.maximum(col, 0)], -1)
     out["prim"] = prim
@@ -297,6 +320,7 @@ def tri_view(truth, nlq, nt):
     triangle; a ray whose winner is a quad or a sphere says nothing about the triangles behind it
     and counts as undecided."""
     out = dict(truth)
+    out["nan_prim"] = np.full(len(truth["prim"]), -1, np.int64)
     tri = (truth["prim"] >= nlq) & (truth["prim"] < nlq + nt)
     out["prim"] = np.where(tri, truth["prim"] - nlq, -1)
     out["decided"] = truth["decided"] & (tri | (truth["prim"] < 0))
@@ -322,16 +346,20 @@ def check_closest(name, truth, prim32, t32=None, dist32=None, miss=0xFFFFFFFF):
     """On decided rays: the exact primitive or an exact miss, |t32 - t64| <= 4 E_t and
     |dist32 - dist64| <= 4 E_t |d| + the rounding of the distance expression itself
     (_own_dist).  Returns the largest observed (error - own rounding) / E_t (printed by the
-    tests, recorded in DESIGN.md §3.4)."""
+    tests, recorded in DESIGN.md §3.4).  A ray with a nan_prim (scan) must return that sphere and
+    a NaN distance."""
     dec = truth["decided"]
-    want = np.where(truth["prim"] >= 0, truth["prim"], miss).astype(np.int64)
+    nanp = truth["nan_prim"]
+    want = np.where(nanp >= 0, nanp, np.where(truth["prim"] >= 0, truth["prim"], miss)).astype(np.int64)
     got = np.asarray(prim32).astype(np.int64)
     bad = np.flatnonzero(dec & (got != want))
     dropped = int(np.sum(dec & (got != want) & (got == miss)))
     assert bad.size == 0, (f"{name}: {bad.size} of {int(dec.sum())} decided rays return another primitive than float64 "
                            f"({dropped} of them drop the hit); first: ray {bad[0]} got {got[bad[0]]} want {want[bad[0]]} "
                            f"t64 {truth['t'][bad[0]]!r} margin {truth['margin'][bad[0]]:.3g} E_m {truth['E_m'][bad[0]]:.3g}")
-    k = dec & (truth["prim"] >= 0)
+    k = dec & (truth["prim"] >= 0) & (nanp < 0)
+    if dist32 is not None:
+        assert np.all(np.isnan(np.asarray(dist32)[dec & (nanp >= 0)])), f"{name}: a NaN sphere's distance is a number"
     worst = 0.0
     for what, got32 in (("t", t32), ("dist", dist32)):
         if got32 is None or not k.any():
@@ -352,13 +380,13 @@ def check_closest(name, truth, prim32, t32=None, dist32=None, miss=0xFFFFFFFF):
 ULP1 = 2.0 ** -23  # the ulp of 1.0: a unit normal's components are compared in it
 
 
-def check_records(name, truth, rec, front_bit=2):
+def check_records(name, truth, rec, front_bit=2, norms=True):
     """On decided hits: pos within 4 E_t |d| (+ _own_pos) of o + t d per component, norm within
     4 ulp (of 1.0) of the float64 unit normal turned against the ray, the front-face flag exact.
     A sphere's normal (pos - c) / r is computed from the hit point and inherits the position's
     tolerance over r.  Returns the largest observed pos error / (E_t |d|) (less its own rounding)
-    and norm error in ulp."""
-    k = truth["decided"] & (truth["prim"] >= 0)
+    and norm error in ulp.  norms=False: pos alone (triangles whose stored normal is not one)."""
+    k = truth["decided"] & (truth["prim"] >= 0) & (truth["nan_prim"] < 0)
     if not k.any():
         return 0.0, 0.0
     E = (truth["E_t"] * truth["dnorm"])[k][:, None]
@@ -372,6 +400,8 @@ def check_records(name, truth, rec, front_bit=2):
     i, j = int(np.argmax(pr)), int(np.argmax(nerr / ntol))
     rays = np.flatnonzero(k)
     assert pr[i] <= TOL, f"{name}: pos is off by {pr[i]:.2f} E_t |d| on decided ray {rays[i]}"
+    if not norms:
+        return float(pr[i]), 0.0
     assert nerr[j] <= ntol[j], f"{name}: norm is off by {nerr[j] / ULP1:.2f} ulp on decided ray {rays[j]} (allowed {ntol[j] / ULP1:.2f})"
     bad = np.flatnonzero(ff != truth["front"][k])
     assert bad.size == 0, f"{name}: {bad.size} front-face flags differ on decided rays; first: ray {rays[bad[0]]}"
@@ -592,3 +622,70 @@ def flat_box_mesh(n=4):
                     c = (P[i, j], P[i + 1, j], P[i + 1, j + 1], P[i, j + 1])
                     tris += [(c[0], c[1], c[2]), (c[0], c[2], c[3])]
     return _wgt().make_triangles(np.array(tris, np.float32))
+
+
+# Scaled soups: the same 300 triangles at scales 2^-12 to 2^31 and rays that are exactly parallel to
+# an axis, the domain the lattices above (coordinates near 0 and 250) leave out.  (30, 0) and
+# (31, 0) have edges beyond the 2^30 upload limit and run on the oracle only.
+SOUP_KINDS = ("axis", "aimed", "unit")
+SOUP_CASES_GPU = [(-12, 0.0), (0, 0.0), (20, 0.0), (22, 0.0), (22, 2e5)]
+SOUP_CASES_CPU = SOUP_CASES_GPU + [(30, 0.0), (31, 0.0)]
+SOUP_AWAY = 800.0  # an axis ray starts this far (times the scale) from its target
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_soup_tris(log2_scale, offset):
+    """300 triangles: v0 uniform in [0, 500)^3 + offset, the other vertices v0 + N(0, 30), all
+    times 2^log2_scale in float64, then rounded to float32.  (22, 2e5) reaches coordinates of
+    2^39.6 with edges below 2^30."""
+    rng = np.random.default_rng(1)
+    v0 = rng.uniform(0.0, 500.0, (300, 3)) + offset
+    verts = np.stack([v0, v0 + rng.normal(0.0, 30.0, (300, 3)), v0 + rng.normal(0.0, 30.0, (300, 3))], axis=1)
+    return _wgt().make_triangles((verts * 2.0 ** log2_scale).astype(np.float32))
+
+
+def soup_scene(log2_scale, offset):
+    """The light and the dummy sphere (radius 0) a soup is traced with: the sphere sits at the
+    centre of the soup's cube.  Anywhere else its discriminant would overflow in fp32 for the
+    aimed rays of (22, 2e5) (sphere_terms: |d| |o - c| above 1.8e19) and the queries would
+    return it; at 2^30 and 2^31 it does so wherever it is, and the truth says so (nan_prim)."""
+    L, S = tri_scene()
+    S["center"][0] = np.float32((250.0 + offset) * 2.0 ** log2_scale)
+    return L, S
+
+
+def soup_has_normals(log2_scale):
+    """Above the upload limit (edge components within 2^30) the triangle constructor's
+    |e1 x e2|^2 overflows and the stored normal is not a unit vector: the soups of 2^30 and 2^31
+    are checked for the primitive, t, dist and pos, not for norm and the front-face flag."""
+    return log2_scale < 30
+
+
+@functools.lru_cache(maxsize=None)
+def scaled_soup_set(log2_scale, offset, kind):
+    """(tris, o, d, truth of soup_scene + tris) for 3,000 rays of one kind at
+    targets v0 + w1 e1 + w2 e2, w ~ Dirichlet(2, 2, 2), of random triangles:
+      axis   d is one of +-x, +-y, +-z, an exact unit vector with two zero components, and
+             o = target - 800 scale d rounded to float32;
+      aimed  o uniform in the soup's cube, d = target - o;
+      unit   as aimed, normalised in float64."""
+    tris = scaled_soup_tris(log2_scale, offset)
+    s = 2.0 ** log2_scale
+    rng = np.random.default_rng([1, SOUP_KINDS.index(kind)])
+    n = 3000
+    v0, e1, e2 = (tris[k][:, :3].astype(np.float64) for k in ("v0", "e1", "e2"))
+    k = rng.integers(0, len(tris), n)
+    w = rng.dirichlet((2.0, 2.0, 2.0), n)
+    target = v0[k] + w[:, 1:2] * e1[k] + w[:, 2:3] * e2[k]
+    if kind == "axis":
+        d = np.zeros((n, 3))
+        d[np.arange(n), rng.integers(0, 3, n)] = rng.choice([-1.0, 1.0], n)
+        o = (target - SOUP_AWAY * s * d).astype(np.float32)
+    else:
+        o = ((rng.uniform(0.0, 500.0, (n, 3)) + offset) * s).astype(np.float32)
+        d = target - o.astype(np.float64)
+        if kind == "unit":
+            d = _unit(d)
+    d = d.astype(np.float32)
+    L, S = soup_scene(log2_scale, offset)
+    return tris, o, d, scan(o, d, L, None, S, tris)

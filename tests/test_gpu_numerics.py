@@ -144,11 +144,12 @@ def test_selftest_math_sequences_are_exact(ctx, seed):
     every exponent of the numerator included; denominators up to 2^35, the bound
     2*sqrt(3)*2^32 of |qn . d|), and the IEEE bits of 1/det on 16M determinants over
     Moller-Trumbore's range 2^-40 <= |det| < 2^95 under the limits; since round 6 also the
-    short reciprocal of the traversal's 1/d on every bit pattern 1e-30 <= |x| <= 2^34 (render rays'
-    direction components after safe_inv's clamp), DESIGN.md §3.2."""
+    short reciprocal of the traversal's 1/d on every bit pattern 2^-87 <= |x| <= 2^34 (render rays'
+    direction components after safe_inv's clamp, wgt_geom.h kSlabDirMin: every value the sequence
+    can be given), DESIGN.md §3.2."""
     c = ctx.selftest_math(1 << 24, seed)
     print("selftest", c)
-    lo = int(np.float32(1e-30).view(np.uint32))
+    lo = int(np.float32(2.0 ** -87).view(np.uint32))
     hi = int(np.float32(2.0 ** 34).view(np.uint32))
     # div_tests: 2^24 quad-distance quotients + 2^24 Moller-Trumbore reciprocals 1/det + every
     # traversal reciprocal pattern (both signs)

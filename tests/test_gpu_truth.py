@@ -26,7 +26,7 @@ def _queries_vs_truth(ctx, name, o, d, truth, cap):
     pos_r, norm_ulp = ft.check_records(f"{name}: trace_hits", truth, rec)
     # occlusion: limits at 0.5 x and 2 x the float64 distance are answered exactly on decided rays
     # (a decided miss is not occluded at any limit); the two limits next to the hit are counted
-    dec, hit = truth["decided"], truth["prim"] >= 0
+    dec, hit = truth["decided"], (truth["prim"] >= 0) & (truth["nan_prim"] < 0)  # a NaN distance is below no limit
     d64 = np.where(hit, truth["dist"], 1e9)
     near = {}
     for f in (0.5, 0.999, 1.001, 2.0):
@@ -50,6 +50,18 @@ def test_lattice_queries_vs_float64(ctx, size, offset, flat):
     ctx.upload_scene(L, L[:0], S, tris)
     name = f"lattice size {size:g} near {offset:g} {'flat' if flat else 'general'}"
     _queries_vs_truth(ctx, name, o, d, ft.lattice_truth(size, offset, flat), ft.CAP_LATTICE)
+
+
+@pytest.mark.parametrize("kind", ft.SOUP_KINDS)
+@pytest.mark.parametrize("log2_scale,offset", ft.SOUP_CASES_GPU)
+def test_scaled_soup_queries_vs_float64(ctx, log2_scale, offset, kind):
+    """The uploadable soups of tests/test_truth_f64.py::test_scaled_soup_vs_float64 (up to
+    coordinates of 2^39.6) through the three queries: exactly axis-parallel rays, d = target - o
+    and unit directions."""
+    tris, o, d, truth = ft.scaled_soup_set(log2_scale, offset, kind)
+    L, S = ft.soup_scene(log2_scale, offset)
+    ctx.upload_scene(L, L[:0], S, tris)
+    _queries_vs_truth(ctx, f"soup 2^{log2_scale} offset {offset:g} {kind}", o, d, truth, ft.CAP_LATTICE)
 
 
 def test_bunny_queries_vs_float64(ctx):

@@ -21,9 +21,10 @@ def v3(a):
     return (a[:, 0].astype(f32), a[:, 1].astype(f32), a[:, 2].astype(f32))
 
 
-def quad_scan_fast(o, d, quads):
+def quad_scan_fast(o, d, quads, details=False):
     """(prim, t, exact) per ray: the smallest-t valid quad (first on equal t), and whether the
-    kernel's tie test lets it stand (else the kernel runs the reference scan)."""
+    kernel's tie test lets it stand (else the kernel runs the reference scan).  details: also
+    the operands of the test's guards, (prev, D, L) (tests/test_gpu_query_range.py)."""
     n = len(o[0])
     prim = np.full(n, NO_HIT, np.uint32)
     qt = np.full(n, np.inf, f32)
@@ -48,11 +49,13 @@ def quad_scan_fast(o, d, quads):
             prim = np.where(ok, np.uint32(k), prim)
         D = np.maximum(np.maximum(np.abs(d[0]), np.abs(d[1])), np.abs(d[2]))
         L = np.maximum(np.maximum(np.abs(o[0]), np.abs(o[1])), np.abs(o[2]))
-        exact = (qt * D < f32(2.0 ** 64))
+        exact = (qt * D < f32(2.0 ** 62))
         g = (prev - qt) - f32(2.0 ** -19) * (prev + qt)
         tie_free = (g * D > f32(2.0 ** -18) * L) & (prev * D >= f32(2.0 ** -49))
         exact &= np.where(prev != np.inf, tie_free, True)
         exact = np.where(prim != NO_HIT, exact, True)
+    if details:
+        return prim, qt, exact, (prev, D, L)
     return prim, qt, exact
 
 

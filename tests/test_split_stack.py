@@ -78,7 +78,7 @@ class Lane:
     def __init__(self, tree, cap, o, d, rng):
         self.T, self.cap, self.o, self.d, self.rng = tree, cap, o, d, rng
         with np.errstate(divide="ignore"):
-            self.inv = np.where(np.abs(d) < 1e-30, np.copysign(1e30, d), 1.0 / d)
+            self.inv = np.where(np.abs(d) < 2.0 ** -87, np.copysign(2.0 ** 87, d), 1.0 / d)  # safe_inv
         self.lds = [None] * cap
         self.glob = []
         self.sp = 0

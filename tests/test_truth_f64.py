@@ -25,7 +25,7 @@ def _same_bits(a, b):
     return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
 
 
-def _triangle_scene_vs_truth(oracle, name, L, S, tris, o, d, truth, cap):
+def _triangle_scene_vs_truth(oracle, name, L, S, tris, o, d, truth, cap, norms=True):
     share = ft.check_share(name, truth, cap)
     nlq, nt = len(L), len(tris)
     osc = oracle.OracleScene(L, L[:0], S, tris)
@@ -41,7 +41,7 @@ def _triangle_scene_vs_truth(oracle, name, L, S, tris, o, d, truth, cap):
     k = np.flatnonzero(tview["decided"] & (tview["prim"] >= 0))
     tid, t = res["tris", False]
     rec = hr.triangle_records(o[k], d[k], tris, tid[k], t[k], nlq)
-    pos_r, norm_ulp = ft.check_records(f"{name}: triangle_records", ft.take(truth, k), rec)
+    pos_r, norm_ulp = ft.check_records(f"{name}: triangle_records", ft.take(truth, k), rec, norms=norms)
     assert np.array_equal(rec["prim"], truth["prim"][k])
     print(f"{name}: {len(o)} rays, decided {share:.3f}, hits {len(k)}, max error / E_t {worst:.3f}, "
           f"pos {pos_r:.3f}, norm {norm_ulp:.2f} ulp")
@@ -66,6 +66,28 @@ def test_bunny_vs_float64(oracle):
 def test_sponza_vs_float64(oracle):
     tris, o, d, truth = ft.sponza_set()
     _triangle_scene_vs_truth(oracle, "sponza-20000", *ft.tri_scene(), tris, o, d, truth, ft.CAP_MESH)
+
+
+@pytest.mark.parametrize("kind", ft.SOUP_KINDS)
+@pytest.mark.parametrize("log2_scale,offset", ft.SOUP_CASES_CPU)
+def test_scaled_soup_vs_float64(oracle, log2_scale, offset, kind):
+    """A 300-triangle soup scaled by 2^-12 to 2^31 (coordinates up to 2^40.2; (22, 2e5): 2^39.6
+    with edges an upload accepts), hit by rays exactly parallel to an axis from 800 scale away, by
+    d = target - o from inside the soup's cube and by unit directions.  An axis-parallel ray has
+    two zero direction components, where the slab rule's 1/d is the clamp's:
+    with the clamp at 1e-30 the slab offset overflowed from coordinates of 3.4e8 and the oracle
+    dropped 1,762 of the 3,000 decided axis hits at 2^20, 2,942 at 2^22, 3,000 at (22, 2e5), 2^30
+    and 2^31, and none at 2^-12 and 2^0 (the aimed and unit rays lost none at any scale).
+    At 2^30 and 2^31 the aimed rays' full-scene answer is the dummy sphere with a NaN distance
+    (f64_truth.sphere_terms; the triangle query is checked as everywhere), and the triangles'
+    stored normals are not unit vectors (f64_truth.soup_has_normals)."""
+    tris, o, d, truth = ft.scaled_soup_set(log2_scale, offset, kind)
+    L, S = ft.soup_scene(log2_scale, offset)
+    name = f"soup 2^{log2_scale} offset {offset:g} {kind}"
+    _triangle_scene_vs_truth(oracle, name, L, S, tris, o, d, truth, ft.CAP_LATTICE, norms=ft.soup_has_normals(log2_scale))
+    nan = int(np.sum(truth["nan_prim"] >= 0))
+    if nan:
+        print(f"{name}: {nan} rays return the dummy sphere with a NaN distance (its fp32 discriminant is inf - inf)")
 
 
 def test_cornell_and_sphere_vs_float64(oracle):

@@ -131,8 +131,17 @@ __device__ __forceinline__ void quad_scan(const DevScene& sc, f3 o, f3 d, Hit& h
 // t of the best it replaced, `prev`: the smallest t of the valid quads before it in scan order.  Its
 // answer is quad_scan's unless f(prev) == f(t) (an earlier quad ties in distance) or f(t) >= kRayMax.
 // Both are excluded by a test on the max norms D = max|d_i|, L = max|o_i| (|.| <= ||.|| <= sqrt(3) |.|):
-//   * f(t) < kRayMax when t D < 2^64: f(t) <= (sqrt(3) t D (1 + 3 eps) + eps sqrt(3) L)(1 + 2.6 eps)
-//     + 2^-74 < 1e20 (eps = 2^-24, L < 2^41 under the scene limits);
+//   * f(t) < kRayMax when t D < 2^62, for ANY origin (render rays have L < 2^41 under the scene
+//     limits; k_trace's caller rays are not bounded).  With x_i = fl(t d_i), |x_i| <= t D (1 + eps),
+//     eps = 2^-24: fl(o_i + x_i) is the float nearest o_i + x_i and o_i is a float |x_i| away from
+//     it, so |fl(o_i + x_i) - o_i| <= 2 |x_i| whatever o_i is, and each component of pos - o is
+//     within 2 t D (1 + 3 eps) < 2^63 (1 + 3 eps).  The three squares then sum to at most 12 t^2 D^2
+//     (1 + 8 eps) < 0.75 2^128 (1 + 8 eps): no partial sum overflows, and f(t) <= sqrt(12) 2^62
+//     (1 + 6 eps) = 1.6e19 < 1e20.  The bound was 2^64 until tests/test_gpu_query_range.py sent
+//     diagonal rays from 2^63.5 away: from the render limits' L < 2^41 it followed that each
+//     component is within t D (1 + 3 eps) + eps L, which gives f(t) < 1e20 but forgot the sum of the
+//     squares, 3 (2^63.5)^2 > FLT_MAX: the reference computes an infinite distance and rejects the
+//     quad, and this scan returned it;
 //   * f(t) < f(prev) when g = (prev - t) - 2^-19 (prev + t) > 0, g D > 2^-18 L and prev D >= 2^-49: each
 //     component of pos - o is t d_i within eps (3 |t d_i| + |o_i|), so ||pos - o|| is t ||d|| within
 //     eps (3 t ||d|| + ||o||); the test (computed in fp32, whose roundings its factor-2 margins absorb)
@@ -171,7 +180,7 @@ __device__ __forceinline__ bool quad_scan_fast(const DevScene& sc, f3 o, f3 d, u
   if (prim != kNoHit) {
     const float D = __builtin_fmaxf(__builtin_fmaxf(fabs_w(d.x), fabs_w(d.y)), fabs_w(d.z));
     const float L = __builtin_fmaxf(__builtin_fmaxf(fabs_w(o.x), fabs_w(o.y)), fabs_w(o.z));
-    exact = qt * D < 0x1p64f;
+    exact = qt * D < 0x1p62f;
     if (prev != __builtin_inff()) {
       const float g = (prev - qt) - 0x1p-19f * (prev + qt);
       exact = exact && g * D > 0x1p-18f * L && prev * D >= 0x1p-49f;

@@ -44,17 +44,33 @@ WGT_HD void tri_box(f3 v0, f3 e1, f3 e2, f3& lo, f3& hi) {
   hi = f3{h[0], h[1], h[2]};
 }
 
-// 1/d with |d| < 1e-30 replaced by copysign(1e-30, d): finite, so slab values are never NaN.
+// The smallest |d| the slab's 1/d is taken of.  2^-87, not smaller (it was 1e-30):
+//   * |1/d'| <= 2^87, so the offset ot = -(o * (1/d')) is finite for every |o| < 2^41, which holds
+//     every origin under the limits (scene coordinates, camera and hit points within 2^40).  With
+//     1e-30 it overflowed from |o| > 3.4e8 on an axis the ray is parallel to: both planes of that
+//     axis then came out at the same infinity, the interval was empty and every triangle was missed.
+//     A caller ray (k_trace, k_occluded) parallel to an axis still overflows from |o| >= 2^41 there.
+//   * with ot finite every operand of fma(b, 1/d', ot) is finite, so a slab value is never NaN; where
+//     it overflows, the exact b/d' + ot is beyond 2^128 and ot's rounding moved it by at most 2^104:
+//     the infinity has the sign of (b - o)/d'.
+//   and not larger: on a clamped axis with the origin inside the box's unpadded extent the planes
+//   lie at least 0.99 pad * 2^87 >= 0.99e-6 * 2^87 = 1.53e20 > kRayMax on either side of t = 0
+//   (hi = fl(mx + pad) loses at most half an ulp of mx, under 0.6 % of pad >= 1e-5 |mx| + 1e-6),
+//   so the axis cannot narrow [near, far] inside the accepted range and the clamp of an accepted
+//   t to the interval (tri_test_rec) moves nothing.  2^-86 (7.7e19) would.
+constexpr float kSlabDirMin = 0x1p-87f;
+
+// 1/d with |d| < kSlabDirMin replaced by copysign(kSlabDirMin, d): finite and nonzero.
 WGT_HD float safe_inv(float x) {
-  if (fabs_w(x) < 1e-30f) x = __builtin_copysignf(1e-30f, x);
+  if (fabs_w(x) < kSlabDirMin) x = __builtin_copysignf(kSlabDirMin, x);
   return 1.0f / x;
 }
 
-// safe_inv by the short reciprocal (wgt_math.h div_by): the IEEE quotient for every 1e-30 <= |x| <=
+// safe_inv by the short reciprocal (wgt_math.h div_by): the IEEE quotient for every 2^-87 <= |x| <=
 // 2^34 (wgt_selftest_math tests each such bit pattern), which holds render rays' directions
-// (primary components within 2^32, scattered ones unit; the clamp gives |x| >= 1e-30)
+// (primary components within 2^32, scattered ones unit; the clamp gives |x| >= 2^-87)
 WGT_HD float safe_inv_short(float x) {
-  if (fabs_w(x) < 1e-30f) x = __builtin_copysignf(1e-30f, x);
+  if (fabs_w(x) < kSlabDirMin) x = __builtin_copysignf(kSlabDirMin, x);
   return div_by(1.0f, rcp_of(x));
 }
 

@@ -490,7 +490,7 @@ k_lpt_order(uint32_t* __restrict__ cost, uint32_t blocks, uint32_t* __restrict__
 //             the reciprocal 1 / det of Moller-Trumbore (mt_test<true>) for 2^-40 <=
 //             |det| < 2^95 (the render limits' range past the 1e-12 rejection): its bits;
 //   the short reciprocal of the traversal's 1/d (trav_init, render rays: safe_inv_short) on every
-//             bit pattern with 1e-30 <= |x| <= 2^34;
+//             bit pattern with 2^-87 <= |x| <= 2^34 (kSlabDirMin, wgt_geom.h);
 //   the compiler's own lowerings (__builtin_sqrtf, n / d) on the same inputs.
 // NaN equals NaN.  counts: [0] sqrt tests, [1] sqrt_rn bad, [2] div tests, [3]
 // div_rn bad, [4] sqrt_fast tests, [5] sqrt_fast bad, [6] compiler sqrt bad, [7]
@@ -524,7 +524,7 @@ __global__ void __launch_bounds__(256) k_selftest_math(uint32_t n, uint32_t seed
       ++n_f;
       bad_f += st_same(sqrt_fast(x), ref) ? 0u : 1u;
     }
-    if (mag >= __float_as_uint(1e-30f) && mag <= __float_as_uint(0x1p34f))
+    if (mag >= __float_as_uint(kSlabDirMin) && mag <= __float_as_uint(0x1p34f))
       bad_r += st_same(safe_inv_short(x), (float)(1.0 / (double)x)) ? 0u : 1u;
   }
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint32_t)stride) {

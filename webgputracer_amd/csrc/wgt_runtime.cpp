@@ -1031,10 +1031,10 @@ int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8
   WGT_HIP(ctx, hipMemcpyAsync(counts, ctx->prim.p, 64, hipMemcpyDeviceToHost, ctx->stream));
   WGT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   counts[0] = 1ull << 32;  // sqrt: every bit pattern
-  // n quad-distance quotients, n Moller-Trumbore reciprocals, and every pattern 1e-30 <= |x| <= 2^34
+  // n quad-distance quotients, n Moller-Trumbore reciprocals, and every pattern 2^-87 <= |x| <= 2^34
   // of the traversal's reciprocal
   uint32_t lo, hi;
-  const float flo = 1e-30f, fhi = 0x1p34f;
+  const float flo = kSlabDirMin, fhi = 0x1p34f;
   std::memcpy(&lo, &flo, 4);
   std::memcpy(&hi, &fhi, 4);
   counts[2] = 2ull * n + 2ull * (hi - lo + 1u);
