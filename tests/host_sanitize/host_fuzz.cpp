@@ -2,9 +2,10 @@
 // run by tests/test_host_sanitize.py): the BVH builder over random, degenerate and extreme
 // triangle sets, every stack budget and both collapses, with the device image of every tree it
 // builds, the OBJ parser over valid, malformed and random
-// text, the procedural meshes, and the host C-ABI entry points (Cornell scene, triangle
-// packing, OBJ and PNG writers).  Exits non-zero on a failed invariant; the sanitizers
-// abort on the first finding.
+// text, the procedural meshes, the host C-ABI entry points (Cornell scene, triangle
+// packing, OBJ and PNG writers), and the planning layer of the device calls (launch_plan.h: the
+// numeric limits, the frame constants and knobs, the kernel form, the scene's device layout).
+// Exits non-zero on a failed invariant; the sanitizers abort on the first finding.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 
 #include "../../include/wgt_api.h"
 #include "../../webgputracer_amd/csrc/host/bvh.h"
+#include "../../webgputracer_amd/csrc/host/launch_plan.h"
 #include "../../webgputracer_amd/csrc/host/obj_loader.h"
 #include "../../webgputracer_amd/csrc/host/procedural.h"
 
@@ -234,10 +236,244 @@ static void host_api() {
   CHECK(wgt_load_obj("/nonexistent/wgt.obj", col, nullptr, 0, nullptr, &n) == WGT_E_IO);
 }
 
+// ---- the planning layer (launch_plan.h) ----
+
+static bool starts(const std::string& msg, const char* prefix) { return msg.rfind(prefix, 0) == 0; }
+static uint32_t bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+static const char* const kKnobs[] = {"WGT_KERNEL", "WGT_PS_TO_TRAV", "WGT_PS_TO_SERVICE", "WGT_PS_SVC_FRAC",
+                                     "WGT_TRI_RATIO", "WGT_CNODE", "WGT_PQ_REFILL", "WGT_PQ_LPT", "WGT_PQ_SVC_COST",
+                                     "WGT_PQ_DEPTH", "WGT_PQ_LPT_ALL", "WGT_PS_WAVES", "WGT_PARK", "WGT_PS_CAP"};
+static void clear_knobs() {
+  for (const char* k : kKnobs) unsetenv(k);
+}
+
+struct Cornell {
+  wgt_quad l[8], q[64];
+  wgt_sphere sp[8];
+  uint32_t nl = 8, nq = 64, ns = 8;
+  Cornell() { CHECK(wgt_scene_cornell(l, &nl, q, &nq, sp, &ns) == WGT_OK); }
+};
+static std::vector<wgt_triangle> mesh500() {
+  uint32_t n = 0;
+  CHECK(wgt_procedural_mesh(0, 500, 1, nullptr, &n) == WGT_OK);
+  std::vector<wgt_triangle> t(n);
+  CHECK(wgt_procedural_mesh(0, 500, 1, t.data(), &n) == WGT_OK);
+  return t;
+}
+// the reference camera (camera.cpp:64-70), origin and target scaled by s
+static wgt_camera_param camera(float aspect, uint32_t spp, float s = 1.0f) {
+  return wgt_camera_param{{278.0f * s, 278.0f * s, -800.0f * s}, 0.0f, {278.0f * s, 278.0f * s, 0.0f}, 0.0f,
+                          aspect, 40.0f, spp, 0u};
+}
+
+// The limits of tests/test_gpu_numerics.py (test_render_limits_fail_cleanly,
+// test_spp_beyond_sample_index_range_rejected) and their boundaries, refusals by message prefix.
+static void plan_limits() {
+  const Cornell c;
+  const std::vector<wgt_triangle> mesh = mesh500();
+  const auto quads = [&](const wgt_quad& q) { return wgt::check_scene_limits(&q, 1, nullptr, 0, nullptr, 0); };
+  const auto tris = [&](const std::vector<wgt_triangle>& t) {
+    return wgt::check_scene_limits(nullptr, 0, nullptr, 0, t.data(), (uint32_t)t.size());
+  };
+  const char* const quad_coord = "quad 0: position, edges and plane offset must be finite and within 2^40";
+  CHECK(wgt::check_scene_limits(c.l, c.nl, c.sp, c.ns, mesh.data(), (uint32_t)mesh.size()).empty());
+  CHECK(wgt::check_scene_limits(c.q, c.nq, nullptr, 0, nullptr, 0).empty());
+  wgt_quad q = c.q[3];
+  q.pos[1] = 0x1p40f;  // exactly 2^40
+  CHECK(quads(q).empty());
+  q.pos[1] = std::nextafter(0x1p40f, INFINITY);
+  CHECK(starts(quads(q), quad_coord));
+  q = c.q[3];
+  q.pos[0] = NAN;
+  CHECK(starts(quads(q), quad_coord));
+  q = c.q[3];
+  q.d = -0x1p42f;  // the plane offset: up to 2^42
+  CHECK(quads(q).empty());
+  q.d = std::nextafter(0x1p42f, INFINITY);
+  CHECK(starts(quads(q), quad_coord));
+  q = c.q[3];
+  q.norm[1] = 2.0f;
+  CHECK(quads(q).empty());
+  q.norm[1] = 3.0f;
+  CHECK(starts(quads(q), "quad 0: normal components must be within 2 (a unit normal) or NaN"));
+  q.norm[0] = q.norm[1] = q.norm[2] = NAN;  // a degenerate quad
+  CHECK(quads(q).empty());
+  wgt_sphere s = c.sp[0];
+  s.radius = INFINITY;
+  CHECK(starts(wgt::check_scene_limits(nullptr, 0, &s, 1, nullptr, 0),
+               "sphere 0: center and radius must be finite and within 2^40"));
+  std::vector<wgt_triangle> t = mesh;
+  t[7].v0[1] = INFINITY;
+  CHECK(starts(tris(t), "triangle 7: vertices must be finite and within 2^40"));
+  t = mesh;
+  t[3].e2[2] = 0x1p30f;
+  CHECK(tris(t).empty());
+  t[3].e2[2] = 0x1p31f;
+  CHECK(starts(tris(t), "triangle 3: edge components must be within 2^30"));
+
+  const auto frame = [](const wgt_camera_param& cam, uint32_t W, uint32_t H) {
+    return wgt::check_frame_args(cam, W, H, 8, 4);
+  };
+  CHECK(frame(camera(1.0f, 1), 8, 8).empty());
+  CHECK(wgt::check_frame_args(camera(1.0f, 1), 0, 8, 8, 8) == "empty frame");
+  CHECK(wgt::check_frame_args(camera(1.0f, 1), 8, 8, 8, 0) == "empty tile");
+  wgt_camera_param cam = camera(1.0f, 1);
+  cam.origin[0] = NAN;
+  CHECK(starts(frame(cam, 8, 8), "camera origin and target must be finite and within 2^40"));
+  CHECK(starts(frame(camera(NAN, 1), 8, 8), "NaN camera parameter"));
+  CHECK(starts(frame(camera(1.0f, 1), 65536, 4), "frame width and height must be <= 65535"));
+  CHECK(frame(camera(1.0f, 1), 65535, 4).empty());
+  for (uint32_t spp : {0xFFFFFFFFu, 0xFFFFFF80u})
+    CHECK(starts(frame(camera(1.0f, spp), 8, 8), "spp too large (u32(sqrt(f32(spp))) must be <= 65535)"));
+  CHECK(starts(frame(camera(1.0f, 1, 0x1p24f), 8, 8), "camera: primary ray directions must be finite and within 2^32"));
+  CHECK(frame(camera(1.0f, 1, 0x1p20f), 8, 8).empty());
+}
+
+// make_frame: the reference camera's frame, and the knobs' defaults and clamps.
+static void plan_frame() {
+  clear_knobs();
+  const wgt::DevFrame fr = wgt::make_frame(camera(16.0f / 9.0f, 4), 48, 27);
+  // origin, pixel_origin, pixel_delta_u, pixel_delta_v, recip_sqrt_spp, fspp, inv_fspp, then sqrt_spp: make_frame of
+  // commit 545344f41999e1fc858e5f5cf0031f04c4872bf1 (wgt_runtime.cpp, the library's flags), printed by a program
+  const uint32_t want[15] = {0x438b0000u, 0x438b0000u, 0xc4480000u, 0x4444372eu, 0x440b9914u, 0x00000000u,
+                             0xc1ac8c80u, 0x00000000u, 0x00000000u, 0x80000000u, 0xc1ac8c80u, 0x80000000u,
+                             0x3f000000u, 0x40800000u, 0x3e800000u};
+  const float got[15] = {fr.ox,  fr.oy,  fr.oz,  fr.pox, fr.poy, fr.poz,         fr.dux,  fr.duy,
+                         fr.duz, fr.dvx, fr.dvy, fr.dvz, fr.recip_sqrt_spp, fr.fspp, fr.inv_fspp};
+  for (int i = 0; i < 15; ++i) CHECK(bits(got[i]) == want[i]);
+  CHECK(fr.sqrt_spp == 2u && fr.W == 48u && fr.H == 27u);
+  CHECK(fr.kernel == 2u && fr.ps_svc_frac == 16u && fr.tri_ratio == 100u && fr.cnode == 1u && fr.pq_lpt == 1u &&
+        fr.pq_svc_cost == 7u && fr.pq_depth == 6u && fr.pq_lpt_all == 1u);
+  CHECK(fr.ps_to_trav == 0u && fr.ps_to_service == 0u && fr.pq_refill == 0u);
+  const wgt::DevFrame tf = wgt::tile_frame(camera(16.0f / 9.0f, 4), 48, 27, 16, 8, 3);
+  CHECK(tf.tw == 16u && tf.th == 8u && tf.n_tiles == 3u && bits(tf.pox) == want[3]);
+  const auto with = [](const char* knob, const char* value) {
+    setenv(knob, value, 1);
+    const wgt::DevFrame f = wgt::make_frame(camera(1.0f, 1), 8, 8);
+    unsetenv(knob);
+    return f;
+  };
+  CHECK(with("WGT_TRI_RATIO", "0").tri_ratio == 1u);
+  CHECK(with("WGT_PQ_DEPTH", "0").pq_depth == 1u);
+  CHECK(with("WGT_PQ_DEPTH", "999").pq_depth == (uint32_t)wgt::kRayDepth);
+  CHECK(with("WGT_KERNEL", "").kernel == 2u && with("WGT_KERNEL", "1").kernel == 1u);
+}
+
+// ps_form_for and fill_bvh_info on trees whose counts are set by hand.
+static void plan_form() {
+  clear_knobs();
+  const auto form = [](uint32_t n_nodes, uint32_t n_tris, uint32_t stack_need) {
+    wgt::BvhOut b;
+    b.n_nodes = n_nodes;
+    b.stack_need = stack_need;
+    return wgt::ps_form_for(b, n_tris);
+  };
+  CHECK(form(100, 1000, 9).waves == 6u && form((1u << 16) - 1, (1u << 20) - 1, 9).waves == 6u);
+  CHECK(form(1u << 16, 1000, 9).waves == 5u && form(100, 1u << 20, 9).waves == 5u);
+  wgt::PsForm f = form(100, 1000, 9);
+  CHECK(f.tris && !f.park && f.cap == 10u);
+  CHECK(form(100, 1000, 0).cap == 2u);  // stack_entries: max(stack_need, 1) + 1
+  setenv("WGT_PS_WAVES", "5", 1);
+  CHECK(form(100, 1000, 9).waves == 5u);
+  unsetenv("WGT_PS_WAVES");
+  wgt::BvhOut none;
+  f = wgt::ps_form_for(none, 0);
+  CHECK(!f.tris && f.waves == (uint32_t)wgt::kPsWavesNoTris && !f.park);
+  wgt_scene_info in;
+  std::memset(&in, 0xff, sizeof in);
+  wgt::fill_bvh_info(none, 0, f, in);
+  CHECK(in.n_tris == 0 && in.bvh_nodes == 0 && in.bvh_width == 0 && in.bvh_stack == 0 && in.ps_waves == 0 &&
+        in.ps_park == 0 && in.ps_stack == 0 && in.bvh_compact == 0);
+  setenv("WGT_PARK", "1", 1);
+  for (uint32_t need : {1u, 2u, 9u, 17u, 18u, 30u})
+    for (uint32_t nodes : {100u, 1u << 16}) {
+      f = form(nodes, 1000, need);
+      const uint32_t whole = std::max(need, 1u) + 1u, room = wgt::ps_cap_max(f.waves);
+      CHECK(f.park && f.cap >= wgt::kMinPsCap && f.cap <= std::max(room, wgt::kMinPsCap));
+      CHECK(f.cap == std::max(std::min(whole, room), wgt::kMinPsCap));
+    }
+  setenv("WGT_PS_CAP", "3", 1);
+  CHECK(form(100, 1000, 30).cap == 8u);
+  setenv("WGT_PS_CAP", "12", 1);
+  CHECK(form(100, 1000, 30).cap == 12u);
+  setenv("WGT_PS_CAP", "99", 1);
+  CHECK(form(100, 1000, 30).cap == wgt::ps_cap_max(6));
+  clear_knobs();
+}
+
+// pack_scene and bind_scene: the layout, the image's bytes and the DevScene of an upload.
+static void check_pack(const Cornell& c, const std::vector<wgt_triangle>& tris) {
+  const uint32_t nt = (uint32_t)tris.size();
+  wgt::BvhOut bvh;
+  if (nt) {
+    const double ext = std::max(wgt::scene_extent(c.l, c.nl, c.sp, c.ns, tris.data(), nt),
+                                wgt::scene_extent(c.q, c.nq, nullptr, 0, nullptr, 0));
+    CHECK(wgt::build_bvh(tris.data(), nt, ext, bvh).empty());
+  }
+  const wgt::BvhImage im = wgt::DeviceImage(bvh);
+  const wgt::ScenePlan p = wgt::pack_scene(c.l, c.nl, c.q, c.nq, c.sp, c.ns, nt, bvh, im);
+  std::vector<char> lq((size_t)(c.nl + c.nq) * sizeof(wgt_quad));  // lights, then quads
+  std::memcpy(lq.data(), c.l, c.nl * sizeof(wgt_quad));
+  std::memcpy(lq.data() + c.nl * sizeof(wgt_quad), c.q, c.nq * sizeof(wgt_quad));
+  const struct { const void* src; size_t bytes; } part[wgt::kSceneParts] = {
+      {lq.data(), lq.size()},           {c.sp, c.ns * sizeof(wgt_sphere)},    {im.nodes.data(), im.nodes.size() * 4},
+      {bvh.tris.data(), bvh.tris.size() * 4}, {bvh.tshade.data(), bvh.tshade.size() * 4},
+      {im.crecs.data(), im.crecs.size() * 4}, {im.level.data(), im.level.size()}};
+  std::vector<char> covered(p.host.size(), 0);
+  size_t end = 0;
+  for (int i = 0; i < wgt::kSceneParts; ++i) {
+    CHECK(p.off[i] % 256 == 0 && p.off[i] >= end && p.off[i] + part[i].bytes <= p.host.size());
+    if (p.off[i] + part[i].bytes > p.host.size()) return;
+    end = p.off[i] + part[i].bytes;
+    if (part[i].bytes) CHECK(std::memcmp(p.host.data() + p.off[i], part[i].src, part[i].bytes) == 0);
+    std::fill(covered.begin() + p.off[i], covered.begin() + end, 1);
+  }
+  CHECK(nt ? part[wgt::kPartNodes].bytes > 0 && part[wgt::kPartLevel].bytes == bvh.n_nodes
+           : part[wgt::kPartNodes].bytes + part[wgt::kPartTris].bytes + part[wgt::kPartLevel].bytes == 0);
+  for (size_t i = 0; i < p.host.size(); ++i)
+    if (!covered[i]) CHECK(p.host[i] == 0);  // padding
+
+  wgt::DevScene sc = p.sc;
+  CHECK(!sc.quads && !sc.spheres && !sc.nodes && !sc.tris && !sc.tshade && !sc.cnodes && !sc.node_level);
+  std::vector<char> dev(p.host.size() + 1);  // stands for the device allocation
+  wgt::bind_scene(sc, p.off, dev.data());
+  const void* const bound[wgt::kSceneParts] = {sc.quads, sc.spheres, sc.nodes, sc.tris,
+                                               sc.tshade, sc.cnodes, sc.node_level};
+  for (int i = 0; i < wgt::kSceneParts; ++i) CHECK(bound[i] == dev.data() + p.off[i]);
+  CHECK(sc.n_lights == c.nl && sc.n_quads == c.nq && sc.n_spheres == c.ns && sc.n_tris == nt &&
+        sc.n_nodes == bvh.n_nodes);
+  CHECK(bits(sc.cstep) == bits(bvh.cstep) && bits(sc.cbound) == bits(bvh.cbound) && sc.rcstep == 1.0f / sc.cstep);
+  CHECK(sc.last_sphere_emissive == (c.sp[c.ns - 1].emissive > 0.0f ? 1u : 0u));
+  // the reference light (scene.cpp:17): 130 x 105, axis-aligned
+  CHECK(sc.light_area == 13650.0f);
+  CHECK(sc.stack == std::max(bvh.stack_need, 1u) + 1u);
+  const wgt::PsForm f = wgt::ps_form_for(bvh, nt), g = wgt::ps_form(sc);
+  CHECK(sc.ps_waves == f.waves && sc.ps_park == (f.park ? 1u : 0u) && sc.ps_cap == f.cap);
+  CHECK(g.tris == f.tris && g.waves == f.waves && g.park == f.park && g.cap == f.cap);
+  CHECK(sc.ps_waves == (nt ? 6u : (uint32_t)wgt::kPsWavesNoTris));
+}
+static void plan_pack() {
+  const Cornell c;
+  clear_knobs();
+  check_pack(c, {});  // no triangles: the tree's parts are empty, their sources null
+  check_pack(c, mesh500());
+  setenv("WGT_PARK", "1", 1);
+  check_pack(c, mesh500());
+  clear_knobs();
+}
+
 int main() {
   fuzz_bvh();
   fuzz_obj();
   host_api();
+  plan_limits();
+  plan_frame();
+  plan_form();
+  plan_pack();
   std::printf("host_fuzz: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);
   return g_fail ? 1 : 0;
 }

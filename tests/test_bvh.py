@@ -279,7 +279,7 @@ def stack24_roundtrip(v):
 def test_stack24_holds_every_ref(kind):
     """Every ref the 6-wave kernel can push survives the 3-byte stack entry: internal refs as the
     device's byte offsets into either node form (x 128 for 128-B nodes, x 80 for compact records)
-    and leaf refs as they are (wgt_runtime.cpp converts the device copies)."""
+    and leaf refs as they are (bvh.cpp DeviceImage converts the device copies)."""
     tris = w.procedural_mesh(kind)
     info, nodes, _ = w.bvh_build(tris)
     assert info["ps_waves"] == 6
@@ -294,7 +294,7 @@ def test_stack24_holds_every_ref(kind):
 def test_stack24_fit_rule():
     """6 waves per SIMD need every ref in a 3-byte stack entry: a tree of 2^20 triangles (leaf refs
     below -2^23) and > 2^16 nodes (128-B node offsets >= 2^23) falls back to 5 waves and 4-byte
-    entries (wgt_runtime.cpp ps_form_for,wgt_internal.h kStack24Nodes / kStack24Tris)."""
+    entries (host/launch_plan.cpp ps_form_for, wgt_internal.h kStack24Nodes / kStack24Tris)."""
     info, _, _ = w.bvh_build(random_soup(1 << 20, 7))
     assert info["n_tris"] == 1 << 20 and info["bvh_nodes"] >= 1 << 16
     assert info["ps_waves"] == 5

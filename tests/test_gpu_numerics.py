@@ -91,8 +91,8 @@ def test_scaled_mesh_vs_oracle(ctx, wgt, oracle, log2s, cnode, monkeypatch):
 def test_render_limits_fail_cleanly(ctx, wgt):
     """Outside the numeric limits that keep the quad distance's short division exact
     (scene coordinates and camera within 2^40, quad normals within 2 or NaN, triangle
-    edges within 2^30, primary directions within 2^32; wgt_runtime.cpp
-    check_scene_limits / check_render_args)
+    edges within 2^30, primary directions within 2^32; host/launch_plan.cpp
+    check_scene_limits / check_frame_args, applied by wgt_runtime.cpp)
     the calls return WGT_E_INVALID instead of rendering."""
     from webgputracer_amd._lib import WGT_E_INVALID, WgtError
 

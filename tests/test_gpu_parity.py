@@ -414,7 +414,7 @@ def test_stack_overflow_spill_and_refill(ctx, wgt, oracle, bunny, cap, cnode, mo
 @pytest.mark.parametrize("env", [{}, {"WGT_PARK": "1"}, {"WGT_PS_WAVES": "5"}, {"WGT_PARK": "1", "WGT_PS_CAP": "8"}])
 def test_scene_info_agrees_with_bvh_build(ctx, wgt, bunny, env, monkeypatch):
     """The host-only report (bvh_build) and the uploaded scene's (scene_info) state the same tree
-    and the same k_render_ps form (wgt_runtime.cpp ps_form_for, fill_bvh_info), under the knobs
+    and the same k_render_ps form (host/launch_plan.cpp ps_form_for, fill_bvh_info), under the knobs
     that select each form."""
     (L, Q, S, T), _ = bunny
     for k, v in env.items():

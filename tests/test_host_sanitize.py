@@ -1,4 +1,5 @@
-"""The product's host code (BVH builder, OBJ parser, procedural meshes, host C-ABI) built
+"""The product's host code (BVH builder, OBJ parser, procedural meshes, host C-ABI, and the
+planning layer of the device calls: limits, frame constants, kernel form, scene layout) built
 with AddressSanitizer + UBSan and run over random, degenerate and malformed inputs
 (tests/host_sanitize/host_fuzz.cpp).  CPU only: GPU sanitizers are not available on the
 GPU pool, and the device code is covered by the -m gpu parity suite instead."""
@@ -18,7 +19,7 @@ def test_host_code_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "host_fuzz")
     srcs = [os.path.join(ROOT, "tests", "host_sanitize", "host_fuzz.cpp")] + [
         os.path.join(HOST, f) for f in ("bvh.cpp", "obj_loader.cpp", "procedural.cpp", "host_api.cpp", "scene.cpp",
-                                        "objects.cpp")]
+                                        "objects.cpp", "launch_plan.cpp")]
     # host-only compile: each sanitizer flag directly after -Xarch_host
     cmd = [HIPCC, "-x", "c++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
            "-I/opt/rocm/include", "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",

@@ -13,7 +13,7 @@
 
 namespace wgt {
 
-// Every parameter of a build.  The defaults are the product's (wgt_runtime.cpp checks the
+// Every parameter of a build.  The defaults are the product's (launch_plan.cpp checks the
 // first two against wgt_internal.h); BvhOptionsFromEnv is the one reader of the knobs.
 struct BvhOptions {
   uint32_t max_depth = 24;  // of the SAH BVH2: bounds the BVH4's depth and so the traversal stack

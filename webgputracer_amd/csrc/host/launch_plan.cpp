@@ -1,0 +1,247 @@
+// launch_plan.cpp — the host arithmetic behind the C-ABI's device calls (launch_plan.h).
+#include "launch_plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+namespace wgt {
+
+bool finite_within(const float* v, int n, double lim) {
+  for (int i = 0; i < n; ++i)
+    if (!(std::fabs((double)v[i]) <= lim)) return false;  // NaN and inf fail too
+  return true;
+}
+
+std::string check_scene_limits(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns,
+                               const wgt_triangle* tr, uint32_t nt) {
+  for (uint32_t i = 0; i < nlq; ++i) {
+    const wgt_quad& q = lq[i];
+    if (!finite_within(q.pos, 3, kCoordLimit) || !finite_within(q.right, 3, kCoordLimit) ||
+        !finite_within(q.up, 3, kCoordLimit) || !finite_within(&q.d, 1, kCoordLimit * 4.0))
+      return "quad " + std::to_string(i) + ": position, edges and plane offset must be finite and within 2^40";
+    const bool nan_norm = q.norm[0] != q.norm[0] || q.norm[1] != q.norm[1] || q.norm[2] != q.norm[2];
+    if (!nan_norm && !finite_within(q.norm, 3, 2.0))
+      return "quad " + std::to_string(i) + ": normal components must be within 2 (a unit normal) or NaN";
+  }
+  for (uint32_t i = 0; i < ns; ++i)
+    if (!finite_within(sp[i].center, 3, kCoordLimit) || !finite_within(&sp[i].radius, 1, kCoordLimit))
+      return "sphere " + std::to_string(i) + ": center and radius must be finite and within 2^40";
+  for (uint32_t i = 0; i < nt; ++i) {
+    if (!finite_within(tr[i].v0, 3, kCoordLimit) || !finite_within(tr[i].e1, 3, kCoordLimit) ||
+        !finite_within(tr[i].e2, 3, kCoordLimit))
+      return "triangle " + std::to_string(i) + ": vertices must be finite and within 2^40";
+    // |det| <= |e1| |e2| |d| <= (sqrt(3) 2^30)^2 sqrt(3) 2^32 = 3 sqrt(3) 2^92 < 2^95 (edge components
+    // within 2^30, primary-direction components within 2^32): mt_test's short 1/det is exact
+    if (!finite_within(tr[i].e1, 3, kEdgeLimit) || !finite_within(tr[i].e2, 3, kEdgeLimit))
+      return "triangle " + std::to_string(i) + ": edge components must be within 2^30";
+  }
+  return "";
+}
+
+static double sq(double x) { return x * x; }
+
+std::string check_frame_args(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th) {
+  if (W == 0 || H == 0) return "empty frame";
+  if (tw == 0 || th == 0) return "empty tile";
+  if (!(cam.aspect == cam.aspect) || !(cam.fovy == cam.fovy)) return "NaN camera parameter";
+  // the kernels pack a sample's (s_i, s_j) into 16 bits each and count sqrt_spp^2
+  // samples in 32 bits: u32(sqrt(f32(spp))) must stay <= 65535 (spp < 2^32 - 2^8)
+  // the kernels keep a pixel's coordinates as 16-bit halves of one register (wgt_device.h Pixel)
+  if (W > 65535u || H > 65535u) return "frame width and height must be <= 65535";
+  if ((uint32_t)__builtin_sqrtf((float)cam.spp) > 65535u) return "spp too large (u32(sqrt(f32(spp))) must be <= 65535)";
+  if (!finite_within(cam.origin, 3, kCoordLimit) || !finite_within(cam.target, 3, kCoordLimit))
+    return "camera origin and target must be finite and within 2^40";
+  // primary directions: viewport point - origin, the viewport spanning [-1/2, W+1/2] x
+  // [-1/2, H+1/2] pixels around po (make_frame, setup_camera_ray)
+  const DevFrame fr = make_frame(cam, W, H);
+  const double po = std::sqrt(sq((double)fr.pox - fr.ox) + sq((double)fr.poy - fr.oy) + sq((double)fr.poz - fr.oz));
+  const double du = std::sqrt(sq((double)fr.dux) + sq((double)fr.duy) + sq((double)fr.duz));
+  const double dv = std::sqrt(sq((double)fr.dvx) + sq((double)fr.dvy) + sq((double)fr.dvz));
+  if (!(po + (W + 1.0) * du + (H + 1.0) * dv <= kPrimaryDirLimit))
+    return "camera: primary ray directions must be finite and within 2^32 (viewport and focal length out of range)";
+  return "";
+}
+
+double scene_extent(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns, const wgt_triangle* tr,
+                    uint32_t nt) {
+  double m = 0.0;
+  for (uint32_t i = 0; i < nlq; ++i)
+    for (int c = 0; c < 3; ++c) {
+      const double p = lq[i].pos[c], r = lq[i].right[c], u = lq[i].up[c];
+      m = std::max({m, std::fabs(p), std::fabs(p + r), std::fabs(p + u), std::fabs(p + r + u)});
+    }
+  for (uint32_t i = 0; i < ns; ++i)
+    for (int c = 0; c < 3; ++c) m = std::max(m, std::fabs((double)sp[i].center[c]) + std::fabs((double)sp[i].radius));
+  for (uint32_t i = 0; i < nt; ++i)
+    for (int c = 0; c < 3; ++c) {
+      const double v = tr[i].v0[c];
+      m = std::max({m, std::fabs(v), std::fabs(v + tr[i].e1[c]), std::fabs(v + tr[i].e2[c])});
+    }
+  return m;
+}
+
+uint32_t env_u32(const char* name, uint32_t dflt) {
+  const char* v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  return (uint32_t)std::strtoul(v, nullptr, 10);
+}
+
+DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
+  DevFrame fr{};
+  const float theta = radians_w(cam.fovy);
+  const f3 origin = f3{cam.origin[0], cam.origin[1], cam.origin[2]};
+  const f3 end = f3{cam.target[0], cam.target[1], cam.target[2]};
+  const float focal_length = length(origin - end);
+  const float h = tan_w(theta * 0.5f);
+  const float viewport_height = 2.0f * h * focal_length;
+  const float viewport_width = viewport_height * cam.aspect;
+  const f3 w = normalize(origin - end);
+  const f3 u = normalize(cross(f3{0.0f, 1.0f, 0.0f}, w));
+  const f3 v = cross(w, u);
+  const f3 viewport_u = viewport_width * u;
+  const f3 viewport_v = viewport_height * (-v);
+  const f3 du = viewport_u / (float)W;
+  const f3 dv = viewport_v / (float)H;
+  const f3 vul = ((origin - focal_length * w) - 0.5f * viewport_u) - 0.5f * viewport_v;
+  const f3 po = vul + 0.5f * (du + dv);
+  fr.ox = origin.x; fr.oy = origin.y; fr.oz = origin.z;
+  fr.pox = po.x; fr.poy = po.y; fr.poz = po.z;
+  fr.dux = du.x; fr.duy = du.y; fr.duz = du.z;
+  fr.dvx = dv.x; fr.dvy = dv.y; fr.dvz = dv.z;
+  fr.recip_sqrt_spp = 1.0f / __builtin_sqrtf((float)cam.spp);
+  fr.fspp = (float)cam.spp;
+  fr.inv_fspp = pow2_recip(cam.spp);
+  fr.sqrt_spp = (uint32_t)__builtin_sqrtf((float)cam.spp);
+  fr.W = W; fr.H = H;
+  fr.kernel = env_u32("WGT_KERNEL", 2);
+  // swept on the persistent BVH4 kernel with compact nodes (DESIGN.md §4.2,
+  // profiles/sweeps/r01_sweep_compact_knobs.jsonl)
+  // 0 = by the kernel's waves per SIMD: 18/16 at 5, 16/14 at 6 (PsForm::to_trav, to_service)
+  fr.ps_to_trav = env_u32("WGT_PS_TO_TRAV", 0);
+  fr.ps_to_service = env_u32("WGT_PS_TO_SERVICE", 0);
+  fr.ps_svc_frac = env_u32("WGT_PS_SVC_FRAC", 16);  // sweep: profiles/sweeps/r01_ps_svc_frac.jsonl
+  // >= 1: with 0 a wave whose lanes all hold a node but no open leaf would take triangle steps forever
+  fr.tri_ratio = std::max<uint32_t>(env_u32("WGT_TRI_RATIO", 100), 1u);
+  fr.cnode = env_u32("WGT_CNODE", 1);  // compact nodes (2: only once the 128-B tree outgrows an XCD's L2)
+  fr.pq_refill = env_u32("WGT_PQ_REFILL", 0);  // 0 = the default, 2 (launch_render)
+  // 0: block order (A/B); n: LPT order from an n*n-spp cost pre-pass (when spp > n*n)
+  fr.pq_lpt = env_u32("WGT_PQ_LPT", 1);
+  fr.pq_svc_cost = env_u32("WGT_PQ_SVC_COST", 7);
+  // the pre-pass's paths end at depth 6 (a cost estimate needs the path's first bounces, and
+  // the full 50-bounce tail set the pre-pass's own drain): sponza +0.4%, bunny +0.7%, the frame
+  // alone -0.6% against full paths, 3 rounds on one box (profiles/sweeps/r04_pq_depth.log)
+  fr.pq_depth = std::min<uint32_t>(std::max<uint32_t>(env_u32("WGT_PQ_DEPTH", 6), 1u), (uint32_t)kRayDepth);
+  fr.pq_lpt_all = env_u32("WGT_PQ_LPT_ALL", 1);  // sweep: all pixels -3% (sponza), -4% (bunny) at 256 spp
+  return fr;
+}
+
+DevFrame tile_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th, uint32_t n_tiles) {
+  DevFrame fr = make_frame(cam, W, H);
+  fr.tw = tw; fr.th = th; fr.n_tiles = n_tiles;
+  return fr;
+}
+
+uint32_t stack_entries(const BvhOut& bvh) { return std::max(bvh.stack_need, 1u) + 1u; }
+
+// Waves per SIMD: 6 with 3-byte stack entries when every ref fits them, else 5; WGT_PS_WAVES=5
+// forces 5 (sweeps); without triangles the kernel without traversal at its own budget (3-byte
+// entries in the launch and the occupancy query alike, ps_lds).  Parked traversal state
+// (opt-in: WGT_PARK=1; it removes the service phase's scratch stores but
+// measured 5 % slower, profiles/r04/): the LDS stack holds what fits beside the parked words at
+// the wave budget, or the whole stack when that is smaller; WGT_PS_CAP lowers it, down to
+// kMinPsCap, for tests.
+PsForm ps_form_for(const BvhOut& bvh, uint32_t n_tris) {
+  PsForm f{n_tris > 0, (uint32_t)kPsWavesNoTris, false, stack_entries(bvh)};
+  if (!f.tris) return f;
+  const bool fits24 = bvh.n_nodes < kStack24Nodes && n_tris < kStack24Tris;
+  f.waves = fits24 && env_u32("WGT_PS_WAVES", 0) != 5 ? 6u : 5u;
+  f.park = env_u32("WGT_PARK", 0) != 0;
+  if (f.park) {
+    const uint32_t c = std::min(f.cap, ps_cap_max(f.waves));
+    f.cap = std::max(std::min(c, std::max(env_u32("WGT_PS_CAP", c), kMinPsCap)), kMinPsCap);
+  }
+  return f;
+}
+
+void fill_bvh_info(const BvhOut& bvh, uint32_t n_tris, const PsForm& f, wgt_scene_info& in) {
+  in.n_tris = n_tris;
+  in.bvh_nodes = bvh.n_nodes;
+  in.bvh_leaves = bvh.n_leaves;
+  in.bvh_max_depth = bvh.max_depth;
+  in.bvh_max_leaf = bvh.max_leaf;
+  in.sah_cost = bvh.sah_cost;
+  in.bvh_width = f.tris ? (uint32_t)kBvhWidth : 0u;
+  in.bvh_stack = f.tris ? std::max(bvh.stack_need, 1u) : 0u;
+  in.bvh2_nodes = bvh.n_nodes2;
+  in.bvh2_depth = bvh.depth2;
+  in.bvh_compact = (size_t)bvh.n_nodes * kNode4Floats * 4 > kCompactNodeBytes ? 1u : 0u;
+  in.bvh_compact_step = bvh.cstep;
+  in.ps_waves = f.tris ? f.waves : 0u;
+  in.ps_park = f.park;
+  in.ps_stack = f.tris ? f.cap : 0u;
+}
+
+constexpr double kOriginBoundScale = 4.0;
+static_assert(BvhOptions{}.max_depth == kMaxBvhDepth && BvhOptions{}.stack_limit == kStackMax, "the builder's defaults");
+std::string build_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh) {
+  std::string err;
+  const BvhOptions opt = BvhOptionsFromEnv(kMaxBvhDepth, kStackMax, kStackNarrow, kOriginBoundScale * extent);
+  return BuildBvh(tris, n_tris, opt, bvh, err) ? "" : err;
+}
+std::string build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh) {
+  return build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh);
+}
+
+// the device triangle records (wgt_geom.h kTriRecordBytes): the builder's 64-B records
+static_assert(kTriRecordBytes == kTriRecordFloats * 4, "device and host triangle records");
+static_assert(sizeof(wgt_quad) == 96 && sizeof(wgt_sphere) == 32, "the reference's records (wgt_internal.h)");
+ScenePlan pack_scene(const wgt_quad* lights, uint32_t n_lights, const wgt_quad* quads, uint32_t n_quads,
+                     const wgt_sphere* spheres, uint32_t n_spheres, uint32_t n_tris, const BvhOut& bvh,
+                     const BvhImage& image) {
+  ScenePlan p{};
+  const size_t quad_bytes = (size_t)n_lights * sizeof(wgt_quad);
+  const struct { const void* src; size_t bytes; } part[kSceneParts] = {
+      {nullptr, quad_bytes + (size_t)n_quads * sizeof(wgt_quad)},  // two sources, copied below
+      {spheres, (size_t)n_spheres * sizeof(wgt_sphere)},
+      {image.nodes.data(), image.nodes.size() * 4},
+      {bvh.tris.data(), bvh.tris.size() * 4},
+      {bvh.tshade.data(), bvh.tshade.size() * 4},
+      {image.crecs.data(), image.crecs.size() * 4},
+      {image.level.data(), image.level.size()}};
+  size_t total = 0;
+  for (int i = 0; i < kSceneParts; ++i) {
+    p.off[i] = total;
+    total += (part[i].bytes + 255) & ~size_t(255);
+  }
+  p.host.assign(total, 0);
+  char* q = p.host.data() + p.off[kPartQuads];
+  std::memcpy(q, lights, quad_bytes);
+  if (n_quads) std::memcpy(q + quad_bytes, quads, (size_t)n_quads * sizeof(wgt_quad));
+  for (int i = kPartSpheres; i < kSceneParts; ++i)  // a scene without triangles has empty (null) tree parts
+    if (part[i].bytes) std::memcpy(p.host.data() + p.off[i], part[i].src, part[i].bytes);
+
+  const PsForm form = ps_form_for(bvh, n_tris);
+  DevScene& sc = p.sc;
+  sc.cstep = bvh.cstep; sc.cbound = bvh.cbound;
+  sc.rcstep = 1.0f / sc.cstep;  // a power of two: exact
+  sc.n_lights = n_lights; sc.n_quads = n_quads; sc.n_spheres = n_spheres; sc.n_tris = n_tris;
+  sc.n_nodes = bvh.n_nodes;
+  sc.last_sphere_emissive = spheres[n_spheres - 1].emissive > 0.0f ? 1u : 0u;
+  const f3 lr = f3{lights[0].right[0], lights[0].right[1], lights[0].right[2]};
+  const f3 lu = f3{lights[0].up[0], lights[0].up[1], lights[0].up[2]};
+  sc.light_area = length(cross(lr, lu));  // path_tracer.wgsl:205
+  sc.stack = stack_entries(bvh);
+  sc.ps_waves = form.waves; sc.ps_park = form.park; sc.ps_cap = form.cap;
+  return p;
+}
+
+void bind_scene(DevScene& sc, const size_t off[kSceneParts], const void* base) {
+  const auto at = [&](ScenePart i) { return (const float4*)((const char*)base + off[i]); };
+  sc.quads = at(kPartQuads); sc.spheres = at(kPartSpheres);
+  sc.nodes = at(kPartNodes); sc.tris = at(kPartTris); sc.tshade = at(kPartShade); sc.cnodes = at(kPartCNodes);
+  sc.node_level = (const uint8_t*)at(kPartLevel);
+}
+
+}  // namespace wgt

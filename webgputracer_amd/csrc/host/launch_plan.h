@@ -1,0 +1,76 @@
+// launch_plan.h — what the C-ABI (wgt_runtime.cpp) decides before it touches the device, as
+// functions that call no HIP runtime function: the numeric limits of scenes and cameras, the
+// frame constants and their tuning knobs, the k_render_ps form of a tree, and the device layout
+// of a scene.  tests/host_sanitize/host_fuzz.cpp runs them without a GPU.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "../wgt_internal.h"
+#include "bvh.h"
+
+namespace wgt {
+
+// Numeric limits under which the kernels' short division (wgt_math.h div_rn, the
+// quad plane distance) is exact wherever it decides anything:
+// scene coordinates and ray origins within 2^40, quad normals within 2 per
+// component (or NaN: a degenerate quad), triangle edge components within 2^30 (the
+// short 1/det of Moller-Trumbore), primary ray directions within 2^32
+// (scattered directions are unit).  Everything else in the kernels is exact for
+// any input.  Outside the limits the calls fail with WGT_E_INVALID.
+constexpr double kCoordLimit = 1099511627776.0;  // 2^40
+constexpr double kEdgeLimit = 1073741824.0;      // 2^30: triangle edges (Moller-Trumbore's short 1/det)
+constexpr double kPrimaryDirLimit = 4294967296.0;  // 2^32
+bool finite_within(const float* v, int n, double lim);  // NaN and inf fail too
+// The checks return their refusal's text, empty when fine: of a scene's primitives, and of the
+// camera and frame of a render or G-buffer call (check_render_args)
+std::string check_scene_limits(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns,
+                               const wgt_triangle* tr, uint32_t nt);
+std::string check_frame_args(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th);
+// Largest |coordinate| any point of the scene's primitives can have (quad corners,
+// sphere boxes, triangle vertices): hit points, i.e. secondary ray origins, lie
+// within it.  The compact nodes are built for ray origins within 4x this bound,
+// which holds the reference camera outside its Cornell box (BvhOptions::origin_bound).
+double scene_extent(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns, const wgt_triangle* tr,
+                    uint32_t nt);
+
+// Tuning knobs (read per launch; defaults are the measured best).
+uint32_t env_u32(const char* name, uint32_t dflt);
+// setup_camera_ray's frame-invariant terms (path_tracer.wgsl:239-257), same fp32
+// operations as the WGSL per-invocation evaluation, and the launch's knobs
+DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H);
+// ... of a launch of n_tiles tiles of tw x th pixels
+DevFrame tile_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th, uint32_t n_tiles);
+
+// The traversal stack of the built tree, entries per lane (DevScene::stack): + 1, the
+// speculative traversal parks a second leaf on the stack (wgt_device.h)
+uint32_t stack_entries(const BvhOut& bvh);
+// The k_render_ps form of a scene (PsForm), under WGT_PS_WAVES, WGT_PARK and WGT_PS_CAP
+PsForm ps_form_for(const BvhOut& bvh, uint32_t n_tris);
+// The BVH and kernel-form fields of the scene report, of wgt_bvh_build and of an upload alike
+// (a scene without triangles reports zeros)
+void fill_bvh_info(const BvhOut& bvh, uint32_t n_tris, const PsForm& f, wgt_scene_info& in);
+// The build with the kernels' limits and the environment's knobs (BvhOptionsFromEnv), for ray
+// origins within kOriginBoundScale x `extent` (scene_extent); returns the builder's refusal
+std::string build_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh);
+// wgt_bvh_build, wgt_bvh_build_compact: the tree exactly as an upload of these triangles alone builds it
+std::string build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh);
+
+// The scene's device layout, each part 256-B aligned: quads (lights first), spheres, then the
+// tree: both node forms stay resident (the compact one is 63% of the 128-B one; the launch
+// picks one per frame, DevFrame::cnode), the triangle and shading records, the node levels
+enum ScenePart { kPartQuads, kPartSpheres, kPartNodes, kPartTris, kPartShade, kPartCNodes, kPartLevel, kSceneParts };
+struct ScenePlan {
+  std::vector<char> host;   // the whole allocation's bytes, padding zero
+  size_t off[kSceneParts];  // of each part within it
+  DevScene sc;              // every field but the pointers (bind_scene)
+};
+// Of inputs that passed wgt_upload_scene's checks, their tree (empty without triangles) and its DeviceImage.
+ScenePlan pack_scene(const wgt_quad* lights, uint32_t n_lights, const wgt_quad* quads, uint32_t n_quads,
+                     const wgt_sphere* spheres, uint32_t n_spheres, uint32_t n_tris, const BvhOut& bvh,
+                     const BvhImage& image);
+// Points sc's seven parts into the allocation at `base`.
+void bind_scene(DevScene& sc, const size_t off[kSceneParts], const void* base);
+
+}  // namespace wgt

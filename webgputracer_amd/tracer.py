@@ -123,6 +123,18 @@ def camera_param(aspect: float, spp: int, seed: int, fovy: float = 40.0):
     return cam
 
 
+def _ray_soa(start, direction):
+    """The ray queries' input (6 planes of n floats: start xyz, then direction xyz) and n."""
+    start = np.asarray(start, np.float32).reshape(-1, 3)
+    direction = np.asarray(direction, np.float32).reshape(-1, 3)
+    return np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32), len(start)
+
+
+def _device_hit_buffers(*fields):
+    """wgt_hit_buffers of raw device addresses, in HIT_FIELDS' order (0 = field not written)."""
+    return WgtHitBuffers(*(f or None for f in fields))
+
+
 def build_id() -> str:
     """The loaded library's kernel build id (wgt_build_id: hash of the HIP sources and flags)."""
     return lib().wgt_build_id().decode()
@@ -225,10 +237,7 @@ class Context:
         return st.as_dict()
 
     def trace_rays(self, start, direction):
-        start = np.asarray(start, np.float32).reshape(-1, 3)
-        direction = np.asarray(direction, np.float32).reshape(-1, 3)
-        n = len(start)
-        soa = np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32)
+        soa, n = _ray_soa(start, direction)
         prim = np.zeros(n, np.uint32)
         dist = np.zeros(n, np.float32)
         self._check(self._L.wgt_trace_rays(self.h, ptr(soa), n, ptr(prim), ptr(dist)))
@@ -241,10 +250,7 @@ class Context:
     def occluded(self, start, direction, max_dist):
         """Any-hit query (wgt_occluded_rays): bool per ray, True iff trace_rays on it returns a
         primitive at a distance below max_dist (scene units; a scalar broadcasts)."""
-        start = np.asarray(start, np.float32).reshape(-1, 3)
-        direction = np.asarray(direction, np.float32).reshape(-1, 3)
-        n = len(start)
-        soa = np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32)
+        soa, n = _ray_soa(start, direction)
         lim = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float32), (n,)))
         out = np.zeros(n, np.uint8)
         self._check(self._L.wgt_occluded_rays(self.h, ptr(soa), ptr(lim), n, ptr(out)))
@@ -276,10 +282,7 @@ class Context:
         """Whole hit records (wgt_trace_hits): a dict of the fields in `want`; prim (n,) uint32 and
         dist (n,) as trace_rays, pos / norm / col (n, 3), flags (n,) uint8 (WGT_HIT_EMISSIVE |
         WGT_HIT_FRONT_FACE)."""
-        start = np.asarray(start, np.float32).reshape(-1, 3)
-        direction = np.asarray(direction, np.float32).reshape(-1, 3)
-        n = len(start)
-        soa = np.ascontiguousarray(np.concatenate([start.T, direction.T], axis=0), np.float32)
+        soa, n = _ray_soa(start, direction)
         arr, bufs = self._hit_arrays(want, (n,))
         self._check(self._L.wgt_trace_hits(self.h, ptr(soa), n, ctypes.byref(bufs)))
         return self._hit_dict(arr)
@@ -287,7 +290,7 @@ class Context:
     def trace_hits_async(self, d_rays, n, prim=0, dist=0, pos=0, norm=0, col=0, flags=0, stream=0):
         """Device-pointer launch (raw device addresses, 0 = field not written): pos / norm / col
         receive 3 planes of n floats."""
-        bufs = WgtHitBuffers(prim or None, dist or None, pos or None, norm or None, col or None, flags or None)
+        bufs = _device_hit_buffers(prim, dist, pos, norm, col, flags)
         self._check(self._L.wgt_trace_hits_async(self.h, ctypes.c_void_p(d_rays), n, ctypes.byref(bufs),
                                                  ctypes.c_void_p(stream or None)))
 
@@ -312,7 +315,7 @@ class Context:
         """Tile-list G-buffer launch with device buffers (raw device addresses, 0 = NULL): n =
         n_tiles * tw * th records at render_tiles_async's pixel offsets; d_rays: 6 planes of n floats."""
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
-        bufs = WgtHitBuffers(prim or None, dist or None, pos or None, norm or None, col or None, flags or None)
+        bufs = _device_hit_buffers(prim, dist, pos, norm, col, flags)
         self._check(self._L.wgt_render_gbuffer_async(self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles),
                                                      n_tiles, ctypes.byref(bufs), ctypes.c_void_p(d_rays or None),
                                                      ctypes.c_void_p(stream or None)))
