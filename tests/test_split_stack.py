@@ -38,8 +38,9 @@ def leaf_count(ref):
 
 
 class Tree:
-    def __init__(self, tris):
-        info, nodes, recs = w.bvh_build(tris)
+    def __init__(self, tris, built=None):
+        """built: the (info, nodes, recs) of an earlier w.bvh_build(tris), to spare a second build."""
+        info, nodes, recs = built if built is not None else w.bvh_build(tris)
         self.stack = info["bvh_stack"] + 1  # DevScene::stack (+ the parking entry)
         n = nodes.reshape(-1, 32)
         self.lo = np.stack([n[:, 0:4], n[:, 8:12], n[:, 16:20]], -1).astype(np.float64)   # (nodes, 4, 3)
