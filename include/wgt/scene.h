@@ -28,6 +28,12 @@ class Scene {
 
   // Scene::InitBuffers (scene.cpp:161-165): pack + upload (+ BVH).
   bool InitBuffers(wgt_ctx* ctx);
+  // Moves the uploaded mesh: repacks tris_ (edited in place since InitBuffers) and refits the
+  // resident BVH on the device (wgt_update_triangles) instead of rebuilding it.  Returns false
+  // with an error message when the scene was not uploaded to ctx, when tris_.size() changed since
+  // InitBuffers (an update moves triangles; call InitBuffers to add or remove) or when the call
+  // refuses the triangles.
+  bool UpdateTriangles(wgt_ctx* ctx);
   void Release();  // scene.cpp:41-50 (idempotent)
 
   // CreateQuadBuffer / CreateSphereBuffer / CreateTriangleBuffer packing
@@ -48,6 +54,7 @@ class Scene {
   bool LoadVertices(const char* file_path, std::vector<Vertex>& vertices);
   wgt_ctx* ctx_ = nullptr;
   bool uploaded_ = false;
+  size_t uploaded_tris_ = 0;  // tris_.size() at InitBuffers
 };
 
 }  // namespace wgt

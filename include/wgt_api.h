@@ -194,6 +194,41 @@ int wgt_bvh_build(const wgt_triangle *tris, uint32_t n_tris, float *nodes_out, u
 int wgt_bvh_build_compact(const wgt_triangle *tris, uint32_t n_tris, uint32_t *cnodes_out,
                           int32_t *crefs_out, uint32_t nodes_cap, float *step_out);
 
+/* ---- moving the triangles of an uploaded scene (no reference counterpart) -- */
+/* Synchronous: moves the scene's triangles to tris[0..n_tris) (a HOST array; triangle i keeps its
+ * primitive id, and its shading fields are taken from tris[i] too) by refitting the resident BVH
+ * on the device instead of rebuilding it: the tree keeps its topology, and every box, triangle
+ * record and compact code is recomputed as a build computes them.  Every render and query
+ * afterwards answers exactly as after wgt_upload_scene of the same scene with these triangles,
+ * bit for bit: the closest hit does not depend on the tree, whose boxes only have to be
+ * conservative (only wgt_stats' visit counters differ).  The tree's quality (sah_cost, which keeps
+ * the build's value) degrades as the mesh deforms; a full wgt_upload_scene restores it.
+ * Order of checks: WGT_E_NOSCENE before an upload; WGT_E_INVALID for NULL, for a scene without
+ * triangles and for n_tris other than the uploaded count; WGT_E_INVALID for a triangle beyond the
+ * scene limits (as wgt_upload_scene), which leaves the scene exactly as it was.  Then the call
+ * waits for every launch of the context, as an upload does, so launches queued before it see the
+ * old triangles and launches after it the new ones.
+ * A WGT_E_HIP failure during the refit itself leaves the tree undefined until the next upload.
+ * Out of scope: a device-pointer input (its limit checks would need a device pass); moving quads,
+ * lights and spheres; adding or removing triangles; any heuristic that rebuilds the tree. */
+int wgt_update_triangles(wgt_ctx *ctx, const wgt_triangle *tris, uint32_t n_tris);
+/* Diagnostic: the last wgt_update_triangles' time in milliseconds, split into its host part
+ * (checks, staging copy) and its device part (the refit kernels and two small readbacks, by
+ * hipEvents). */
+int wgt_update_timing(const wgt_ctx *ctx, float *host_ms, float *device_ms);
+/* Diagnostic (synchronous): copies the resident tree back in the export layouts of wgt_bvh_build
+ * (nodes_out: bvh_nodes x 32 floats, tris_out: n_tris x 16 floats) and wgt_bvh_build_compact
+ * (cnodes_out: bvh_nodes x 16 words, crefs_out: bvh_nodes x 4 refs, step_out), refs as indices.
+ * Any output may be NULL; nodes_cap must be >= bvh_nodes for the per-node outputs. */
+int wgt_bvh_read(wgt_ctx *ctx, float *nodes_out, uint32_t nodes_cap, float *tris_out,
+                 uint32_t *cnodes_out, int32_t *crefs_out, float *step_out);
+/* Host only: the tree that wgt_upload_scene of built_from[0..n_tris) alone followed by
+ * wgt_update_triangles to now[0..n_tris) must hold, in wgt_bvh_read's layouts (any output may be
+ * NULL; info is required, its sah_cost is the build's).  now is checked as the update checks it. */
+int wgt_bvh_refit(const wgt_triangle *built_from, const wgt_triangle *now, uint32_t n_tris,
+                  float *nodes_out, uint32_t nodes_cap, float *tris_out, uint32_t *cnodes_out,
+                  int32_t *crefs_out, float *step_out, wgt_scene_info *info);
+
 /* ---- rendering (replaces the compute pass of Renderer::OnRender) --------- */
 /* Synchronous: render the rectangle [x0,x0+tw) x [y0,y0+th) of a W x H frame
  * into caller-owned HOST buffers (row-major tw x th; any may be NULL):

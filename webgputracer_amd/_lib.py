@@ -83,6 +83,7 @@ EXPORTS = [
     "wgt_scene_cornell", "wgt_make_triangles", "wgt_load_obj", "wgt_procedural_mesh",
     "wgt_write_obj", "wgt_write_png", "wgt_bvh_build", "wgt_bvh_build_compact",
     "wgt_render_frames",
+    "wgt_update_triangles", "wgt_update_timing", "wgt_bvh_read", "wgt_bvh_refit",
 ]
 
 _lib = None
@@ -145,6 +146,10 @@ def lib():
         "wgt_write_png": (I, [ctypes.c_char_p, P, U32, U32]),
         "wgt_bvh_build": (I, [P, U32, P, U32, P, ctypes.POINTER(WgtSceneInfo)]),
         "wgt_render_frames": (I, [P, P, U32, U32, P, U32, P, P]),
+        "wgt_update_triangles": (I, [P, P, U32]),
+        "wgt_update_timing": (I, [P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+        "wgt_bvh_read": (I, [P, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float)]),
+        "wgt_bvh_refit": (I, [P, P, U32, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(WgtSceneInfo)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -6,6 +6,8 @@
 // boxes, so the BVH4 child boxes are exactly BVH2 node boxes.
 #include "bvh.h"
 
+#include "../wgt_compact.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -407,77 +409,15 @@ class DpCollapser {
   std::vector<double> area_;
 };
 
-// Compact form of one node (wgt_geom.h).  The kernel evaluates a child plane's slab
-// distance as fma(h, s/d, c) with c = fma(org/s, s/d, ot) per node and axis (one
-// fused step instead of decoding the plane first), so the codes keep a margin G
-// from the exact child bounds: a lo code's plane org' + h*s (org' = the stored
-// org/s times s) lies <= lo - G, a hi code's >= hi + G.  G = 2^-21 * M, with M
-// >= |org'| and >= |ray origin| (BvhOptions::origin_bound), covers the rounding of
-// c: every decoded interval then contains, bit for bit, the
-// slab interval fma(b, 1/d, ot) of every triangle box b below the child.  Codes
-// are the tightest binary16 values with the margin (non-negative half bit
-// patterns order like their values, so a binary search finds them).
-double CDecD(uint32_t h, double s, double orgd) { return orgd + (double)half_bits_to_float(h) * s; }
-void CompactNode(Node4T<const float> n, float s, double G, uint32_t* q) {
-  float orgs[3];
-  for (int a = 0; a < 3; ++a) {
-    double ulo = std::numeric_limits<double>::infinity();
-    for (int i = 0; i < kBvhWidth; ++i)
-      if (n.live(i)) ulo = std::min(ulo, (double)n.lo(a, i));
-    // org/s as a float whose value times s is <= ulo - G
-    const double target = (ulo - G) / (double)s;
-    float f = (float)target;
-    while ((double)f > target) f = std::nextafter(f, -kInf);
-    orgs[a] = f;
-    const double orgd = (double)f * (double)s;
-    uint32_t lo_h[kBvhWidth], hi_h[kBvhWidth];
-    for (int i = 0; i < kBvhWidth; ++i) {
-      lo_h[i] = hi_h[i] = 0x7c00u;  // an empty slot: +inf planes on every axis, never entered
-      if (!n.live(i)) continue;
-      const double blo = (double)n.lo(a, i) - G, bhi = (double)n.hi(a, i) + G;
-      uint32_t l = 0, r = 0x7bffu;  // largest h with plane <= blo (h = 0 is: orgd <= ulo - G)
-      while (l < r) {
-        const uint32_t m = (l + r + 1) / 2;
-        if (CDecD(m, s, orgd) <= blo) l = m; else r = m - 1;
-      }
-      lo_h[i] = l;
-      l = 0; r = 0x7bffu;  // smallest h with plane >= bhi (CompactStep guarantees h = 65504 is)
-      while (l < r) {
-        const uint32_t m = (l + r) / 2;
-        if (CDecD(m, s, orgd) >= bhi) r = m; else l = m + 1;
-      }
-      hi_h[i] = l;
-    }
-    q[4 + 4 * a + 0] = lo_h[0] | (lo_h[1] << 16);
-    q[4 + 4 * a + 1] = lo_h[2] | (lo_h[3] << 16);
-    q[4 + 4 * a + 2] = hi_h[0] | (hi_h[1] << 16);
-    q[4 + 4 * a + 3] = hi_h[2] | (hi_h[3] << 16);
-  }
-  std::memcpy(&q[0], orgs, 12);
-  q[3] = 0u;  // reserved
-}
-
-// The smallest power-of-two step with which code 65504 reaches every node's upper
-// bounds plus the margins (the origin sits up to G + one float step of org/s below
-// the lower bound).
+// The compact form's arithmetic is wgt_compact.h's (shared with the device refit).  The smallest
+// power-of-two step every node accepts (compact_step_ok); the predicate is monotone in the step,
+// so this is the largest of the nodes' own smallest steps (compact_node_exp).
 float CompactStep(const BvhOut& out, double G) {
-  int e = -24;
+  int e = kCompactMinExp;
   for (;;) {
     const float s = std::ldexp(1.0f, e);
     bool ok = true;
-    for (uint32_t k = 0; k < out.n_nodes && ok; ++k) {
-      const auto n = Node4(out.nodes, k);
-      for (int a = 0; a < 3 && ok; ++a) {
-        double ulo = std::numeric_limits<double>::infinity(), uhi = -ulo;
-        for (int i = 0; i < kBvhWidth; ++i)
-          if (n.live(i)) {
-            ulo = std::min(ulo, (double)n.lo(a, i));
-            uhi = std::max(uhi, (double)n.hi(a, i));
-          }
-        const double org_low = ulo - G - (std::fabs(ulo - G) * 0x1p-23 + (double)s * 0x1p-126);
-        ok = org_low + 65504.0 * (double)s >= uhi + G;
-      }
-    }
+    for (uint32_t k = 0; k < out.n_nodes && ok; ++k) ok = compact_step_ok(&out.nodes[(size_t)k * kNode4Floats], s, G);
     if (ok) return s;
     ++e;
   }
@@ -614,7 +554,7 @@ void CompactForm(double origin_bound, BvhOut& out) {
   out.cnodes.resize((size_t)out.n_nodes * kCNodeFloats);
   out.crefs.resize((size_t)out.n_nodes * kBvhWidth);
   for (uint32_t i = 0; i < out.n_nodes; ++i) {
-    CompactNode(Node4(nodes, i), out.cstep, G, &out.cnodes[(size_t)i * kCNodeFloats]);
+    compact_node(&nodes[(size_t)i * kNode4Floats], out.cstep, G, &out.cnodes[(size_t)i * kCNodeFloats]);
     for (int s = 0; s < kBvhWidth; ++s) out.crefs[(size_t)i * kBvhWidth + s] = Node4(nodes, i).ref(s);
   }
 }
@@ -692,6 +632,68 @@ bool BuildBvh(const wgt_triangle* tris, uint32_t n, const BvhOptions& opt, BvhOu
   return true;
 }
 
+// The refit keeps the topology, so whatever depends on it alone stays: refs, leaf order, n_nodes,
+// stack_need, the depths, and sah_cost (the build's value: it describes the tree as built).
+// Internal refs point forward (CheckRefs), so one pass from the last node to the root sees every
+// child before its parent.  Boxes are exact min/max unions, as the builder's, and tri_box never
+// yields -0, so a refit to the triangles of the build reproduces it bit for bit.
+bool RefitBvh(BvhOut& bvh, const wgt_triangle* tris, uint32_t n, double origin_bound, std::string& err) {
+  if (n == 0 || bvh.n_nodes == 0 || bvh.tris.size() != (size_t)n * kTriRecordFloats ||
+      bvh.nodes.size() != (size_t)bvh.n_nodes * kNode4Floats) {
+    err = "RefitBvh: the triangle count differs from the build's";
+    return false;
+  }
+  // the records, in the build's leaf order: the same fp32 operations as MakePrims and TriRecords
+  std::vector<float> recs(bvh.tris.size());
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t idx;
+    std::memcpy(&idx, &bvh.tris[(size_t)i * kTriRecordFloats + 3], 4);
+    if (idx >= n) { err = "RefitBvh: malformed triangle record " + std::to_string(i); return false; }
+    const wgt_triangle& t = tris[idx];
+    f3 lo, hi;
+    tri_box(f3{t.v0[0], t.v0[1], t.v0[2]}, f3{t.e1[0], t.e1[1], t.e1[2]}, f3{t.e2[0], t.e2[1], t.e2[2]}, lo, hi);
+    for (const float v : {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z})
+      if (!std::isfinite(v)) {
+        err = "RefitBvh: non-finite triangle " + std::to_string(idx);
+        return false;  // bvh is as it was
+      }
+    float* o = &recs[(size_t)i * kTriRecordFloats];
+    o[0] = t.v0[0]; o[1] = t.v0[1]; o[2] = t.v0[2];
+    std::memcpy(&o[3], &idx, 4);
+    o[4] = t.e1[0]; o[5] = t.e1[1]; o[6] = t.e1[2]; o[7] = lo.x;
+    o[8] = t.e2[0]; o[9] = t.e2[1]; o[10] = t.e2[2]; o[11] = lo.y;
+    o[12] = lo.z; o[13] = hi.x; o[14] = hi.y; o[15] = hi.z;
+  }
+  bvh.tris = std::move(recs);
+  for (uint32_t k = bvh.n_nodes; k-- > 0;) {
+    const auto node = Node4(bvh.nodes, k);
+    for (int s = 0; s < kBvhWidth; ++s) {
+      if (!node.live(s)) continue;  // empty slots stay as they are
+      Box b;
+      b.reset();
+      const int32_t r = node.ref(s);
+      if (r < 0) {
+        for (uint32_t j = leaf_first(r), end = j + leaf_count(r); j < end; ++j) {
+          const float* o = &bvh.tris[(size_t)j * kTriRecordFloats];
+          b.grow(Box{{o[7], o[11], o[12]}, {o[13], o[14], o[15]}});
+        }
+      } else {
+        const auto child = Node4(bvh.nodes, (size_t)r);
+        for (int c = 0; c < kBvhWidth; ++c)
+          if (child.live(c))
+            b.grow(Box{{child.lo(0, c), child.lo(1, c), child.lo(2, c)}, {child.hi(0, c), child.hi(1, c), child.hi(2, c)}});
+      }
+      for (int a = 0; a < 3; ++a) {
+        node.lo(a, s) = b.lo[a];
+        node.hi(a, s) = b.hi[a];
+      }
+    }
+  }
+  CompactForm(origin_bound, bvh);
+  ShadeRecords(tris, n, bvh);
+  return true;
+}
+
 BvhImage DeviceImage(const BvhOut& bvh) {
   constexpr size_t kRecWords = kCRecordFloat4s * 4;
   BvhImage im{bvh.nodes, std::vector<uint32_t>(bvh.n_nodes * kRecWords), std::vector<uint8_t>(bvh.n_nodes, 0)};
@@ -708,6 +710,27 @@ BvhImage DeviceImage(const BvhOut& bvh) {
     }
   }
   return im;
+}
+
+void ExportImage(const float* dev_nodes, const uint32_t* dev_crecs, uint32_t n_nodes, float* nodes_out,
+                 uint32_t* cnodes_out, int32_t* crefs_out) {
+  constexpr size_t kRecWords = kCRecordFloat4s * 4;
+  for (size_t i = 0; i < n_nodes; ++i) {
+    if (nodes_out) {
+      std::memcpy(&nodes_out[i * kNode4Floats], &dev_nodes[i * kNode4Floats], kNode4Floats * 4);
+      const Node4T<float> o{&nodes_out[i * kNode4Floats]};
+      for (int s = 0; s < kBvhWidth; ++s)
+        if (o.ref(s) >= 0) o.set_ref(s, o.ref(s) / (int32_t)(kNode4Floats * 4));
+    }
+    const uint32_t* rec = &dev_crecs[i * kRecWords];
+    if (cnodes_out) std::memcpy(&cnodes_out[i * kCNodeFloats], rec, kCNodeFloats * 4);
+    if (crefs_out)
+      for (int s = 0; s < kBvhWidth; ++s) {
+        int32_t c;
+        std::memcpy(&c, &rec[kCNodeFloats + s], 4);
+        crefs_out[i * kBvhWidth + s] = c >= 0 ? c / (int32_t)(kRecWords * 4) : c;
+      }
+  }
 }
 
 }  // namespace wgt

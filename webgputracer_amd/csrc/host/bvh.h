@@ -72,6 +72,14 @@ struct BvhOut {
 // Builds over n >= 1 triangles; on failure err says why.
 bool BuildBvh(const wgt_triangle* tris, uint32_t n, const BvhOptions& opt, BvhOut& out, std::string& err);
 
+// Refits a built tree to n moved triangles (triangle i keeps its index; n as built): the topology
+// stays (refs, leaf order, n_nodes, stack_need, depths), and tris, tshade, every live slot's box
+// and the compact form (cnodes, cstep, cbound, for ray origins within origin_bound) are recomputed
+// as the build computes them, so a refit to the build's own triangles reproduces it bit for bit.
+// sah_cost stays the build's value: it describes the tree as built, not the refit one.  On failure
+// (a non-finite triangle box, as in the build) err says why and bvh is unchanged.
+bool RefitBvh(BvhOut& bvh, const wgt_triangle* tris, uint32_t n, double origin_bound, std::string& err);
+
 // The tree as the kernels read it: internal refs are byte offsets (one add to the uniform
 // base instead of an index multiply), leaf refs are unchanged.
 struct BvhImage {
@@ -80,5 +88,9 @@ struct BvhImage {
   std::vector<uint8_t> level;    // each node's level: root 0, saturating at 255
 };
 BvhImage DeviceImage(const BvhOut& bvh);
+// The inverse for n_nodes nodes of a device image: the export layouts of wgt_bvh_build (nodes_out)
+// and wgt_bvh_build_compact (cnodes_out, crefs_out), refs as indices; any output may be null.
+void ExportImage(const float* dev_nodes, const uint32_t* dev_crecs, uint32_t n_nodes, float* nodes_out,
+                 uint32_t* cnodes_out, int32_t* crefs_out);
 
 }  // namespace wgt

@@ -194,6 +194,39 @@ std::string build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& 
   return build_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh);
 }
 
+std::string refit_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh) {
+  std::string err;
+  return RefitBvh(bvh, tris, n_tris, kOriginBoundScale * extent, err) ? "" : err;
+}
+std::string refit_for_export(const wgt_triangle* built_from, const wgt_triangle* now, uint32_t n_tris, BvhOut& bvh) {
+  const std::string err = build_for_export(built_from, n_tris, bvh);
+  if (!err.empty()) return err;
+  return refit_bvh(now, n_tris, scene_extent(nullptr, 0, nullptr, 0, now, n_tris), bvh);
+}
+
+double compact_bound(double extent, const float* root_node) {
+  double M = std::max(kOriginBoundScale * extent, 0x1p-60);
+  for (int i = 0; i < 6 * kBvhWidth; ++i)
+    if (root_node[i] != kEmptySlotCoord) M = std::max(M, 2.0 * std::fabs((double)root_node[i]));
+  return M;
+}
+
+std::string refit_levels(const uint8_t* level, uint32_t n_nodes, std::vector<uint32_t>& order,
+                         std::vector<uint32_t>& begin) {
+  uint32_t count[256] = {};
+  for (uint32_t i = 0; i < n_nodes; ++i) count[level[i]]++;
+  if (count[255]) return "refit: the tree is deeper than node levels are recorded for (255)";
+  uint32_t levels = 0;
+  for (uint32_t l = 0; l < 255; ++l)
+    if (count[l]) levels = l + 1;
+  begin.assign(levels + 1, 0u);
+  for (uint32_t l = 0; l < levels; ++l) begin[l + 1] = begin[l] + count[l];
+  order.resize(n_nodes);
+  std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+  for (uint32_t i = 0; i < n_nodes; ++i) order[at[level[i]]++] = i;
+  return "";
+}
+
 // the device triangle records (wgt_geom.h kTriRecordBytes): the builder's 64-B records
 static_assert(kTriRecordBytes == kTriRecordFloats * 4, "device and host triangle records");
 static_assert(sizeof(wgt_quad) == 96 && sizeof(wgt_sphere) == 32, "the reference's records (wgt_internal.h)");

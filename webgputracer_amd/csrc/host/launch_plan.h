@@ -57,6 +57,22 @@ std::string build_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, 
 // wgt_bvh_build, wgt_bvh_build_compact: the tree exactly as an upload of these triangles alone builds it
 std::string build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh);
 
+// The refit of a built tree to moved triangles (RefitBvh) under the same origin-bound rule:
+// `extent` is the scene's with the new triangles (and its unchanged quads, lights and spheres)
+std::string refit_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh);
+// wgt_bvh_refit: the tree an upload of `built_from` alone followed by an update to `now` holds
+std::string refit_for_export(const wgt_triangle* built_from, const wgt_triangle* now, uint32_t n_tris, BvhOut& bvh);
+// What the device refit (wgt_update_triangles) decides on the host.  The compact codes' bound M
+// for ray origins within kOriginBoundScale x `extent`, from the refit root node alone (32 floats):
+// every box of the tree nests in the root's slots exactly, so they hold the largest |coordinate|.
+// This is CompactForm's M.
+double compact_bound(double extent, const float* root_node);
+// The nodes of each level (BvhImage::level), levels in order: level l's nodes are order[begin[l],
+// begin[l + 1]).  A refit runs the levels deepest first, one launch each.  Returns a refusal when
+// a level is saturated (255: the tree is deeper than levels are recorded for), empty when fine.
+std::string refit_levels(const uint8_t* level, uint32_t n_nodes, std::vector<uint32_t>& order,
+                         std::vector<uint32_t>& begin);
+
 // The scene's device layout, each part 256-B aligned: quads (lights first), spheres, then the
 // tree: both node forms stay resident (the compact one is 63% of the 128-B one; the launch
 // picks one per frame, DevFrame::cnode), the triangle and shading records, the node levels

@@ -121,6 +121,7 @@ bool Scene::InitBuffers(wgt_ctx* ctx) {
     return false;
   }
   uploaded_ = true;
+  uploaded_tris_ = t.size();
   return true;
 }
 

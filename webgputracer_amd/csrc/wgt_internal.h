@@ -242,4 +242,18 @@ hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n
 hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
                           const wgt_hit_buffers& out, float* d_rays, hipStream_t stream);
 
+
+// Launchers implemented in wgt_refit.hip: the refit of the resident tree to moved triangles, in
+// this order on one stream, after every launch that reads the scene has ended.  They write the
+// scene's tree parts (the pointers of sc are const for every other kernel).
+// The records and shading records from the n_tris moved triangles (device array, original order).
+hipError_t launch_refit_tris(const DevScene& sc, const wgt_triangle* d_moved, hipStream_t stream);
+// The boxes of the `count` nodes d_order lists, one tree level (launch_plan.h refit_levels), after
+// the level below it.
+hipError_t launch_refit_nodes(const DevScene& sc, const uint32_t* d_order, uint32_t count, hipStream_t stream);
+// *d_max_exp (zeroed by the caller) = the scene's step exponent - kCompactMinExp for the margin G.
+hipError_t launch_refit_step(const DevScene& sc, double G, uint32_t* d_max_exp, hipStream_t stream);
+// The node part of every compact record for that step and margin.
+hipError_t launch_refit_compact(const DevScene& sc, float step, double G, hipStream_t stream);
+
 }  // namespace wgt

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -14,6 +16,7 @@
 
 #include "../../include/wgt_api.h"
 #include "host/launch_plan.h"
+#include "wgt_compact.h"
 #include "wgt_error.h"
 #include "wgt_internal.h"
 
@@ -41,11 +44,19 @@ struct wgt_ctx {
   void* scene_mem = nullptr;
   wgt_scene_info info{};
   uint32_t ps_resident = 0;
+  // wgt_update_triangles: the extent of the scene's lights, quads and spheres (they do not move), and
+  // what the first refit of a scene prepares (an upload's cost and layout do not change): the level
+  // lists of the tree (refit_levels) on the device, then one word for the step exponent
+  double fixed_extent = 0.0;
+  std::vector<uint32_t> level_begin;
+  DevBuf level_order;
+  float refit_host_ms = 0.0f, refit_device_ms = 0.0f;  // of the last update (wgt_update_timing)
   // scratch for the synchronous entry points: the renders' tile list, outputs and counters; the
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
-  // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays
+  // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
+  // a refit's moved triangles
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -192,6 +203,12 @@ const char* null_buffer(bool any) { return any ? "null buffer" : nullptr; }
 const char* bad_hits(const wgt_hit_buffers* b) {
   if (!b) return "null buffer";
   return !b->prim && !b->dist && !b->pos && !b->norm && !b->col && !b->flags ? "no hit field asked for" : nullptr;
+}
+
+// wgt_scene_info::node_form: the persistent kernel's node form for the reference camera.
+uint32_t reference_node_form(const DevScene& sc) {
+  const wgt_camera_param cam{{278.0f, 278.0f, -800.0f}, 0.0f, {278.0f, 278.0f, 0.0f}, 0.0f, 1.0f, 40.0f, 1u, 0u};
+  return sc.n_tris ? (uint32_t)node_form(sc, make_frame(cam, 1, 1)) : 0u;
 }
 
 // The wgt_stats field of each device counter, in the order of CNT_* (wgt_internal.h)
@@ -392,6 +409,7 @@ void wgt_destroy(wgt_ctx* ctx) {
     }
   if (ctx->scene_mem) (void)hipFree(ctx->scene_mem);
   for (DevBuf& b : ctx->buf) free_buf(b);
+  free_buf(ctx->level_order);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -482,9 +500,10 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   WGT_HIP(ctx, hipSetDevice(ctx->device));
 
   BvhOut bvh;
+  const double fixed_ext = std::max(scene_extent(lights, n_lights, spheres, n_spheres, nullptr, 0),
+                                    scene_extent(quads, n_quads, nullptr, 0, nullptr, 0));
   if (n_tris > 0) {
-    const double ext = std::max({scene_extent(lights, n_lights, spheres, n_spheres, tris, n_tris),
-                                 scene_extent(quads, n_quads, nullptr, 0, nullptr, 0)});
+    const double ext = std::max(fixed_ext, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris));
     bad = build_bvh(tris, n_tris, ext, bvh);
     if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   }
@@ -498,6 +517,9 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   ctx->has_scene = false;
   // a new scene: the workspaces' scheduling words are re-zeroed by the next launch's memset
   for (auto& sl : ctx->slots) sl.clean_nb = 0;
+  ctx->fixed_extent = fixed_ext;
+  ctx->level_begin.clear();  // the next refit prepares the new tree's level lists
+  free_buf(ctx->level_order);
   WGT_HIP(ctx, hipMalloc(&ctx->scene_mem, plan.host.size()));
   WGT_HIP(ctx, hipMemcpy(ctx->scene_mem, plan.host.data(), plan.host.size(), hipMemcpyHostToDevice));
   DevScene& sc = ctx->sc;
@@ -513,12 +535,124 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   fill_bvh_info(bvh, n_tris, ps_form(sc), in);
   in.n_lights = n_lights; in.n_quads = n_quads; in.n_spheres = n_spheres;
   in.device_bytes = plan.host.size();
-  {
-    const wgt_camera_param cam{{278.0f, 278.0f, -800.0f}, 0.0f, {278.0f, 278.0f, 0.0f}, 0.0f, 1.0f, 40.0f, 1u, 0u};
-    in.node_form = n_tris ? (uint32_t)node_form(sc, make_frame(cam, 1, 1)) : 0u;
-  }
+  in.node_form = reference_node_form(sc);
   in.ps_resident = ctx->ps_resident;
   ctx->has_scene = true;
+  return WGT_OK;
+}
+
+int wgt_update_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris) {
+  using clock = std::chrono::steady_clock;
+  const clock::time_point t0 = clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (!tris) return fail(ctx, WGT_E_INVALID, "null triangles");
+  if (ctx->sc.n_tris == 0) return fail(ctx, WGT_E_INVALID, "the scene has no triangles to update");
+  if (n_tris != ctx->sc.n_tris)
+    return fail(ctx, WGT_E_INVALID, "triangle count " + std::to_string(n_tris) + " differs from the uploaded " +
+                                        std::to_string(ctx->sc.n_tris) + " (an update moves triangles; upload to add or remove)");
+  // a refusal leaves the device untouched: under the limits every triangle box is finite
+  const std::string bad = check_scene_limits(nullptr, 0, nullptr, 0, tris, n_tris);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  const double extent = std::max(ctx->fixed_extent, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris));
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = use_drain(ctx))) return rc;  // no launch on any stream may still read the old tree
+  DevScene& sc = ctx->sc;
+  hipStream_t s = ctx->stream;
+  if (ctx->level_begin.empty()) {  // the first refit of this scene: its level lists
+    std::vector<uint8_t> level(sc.n_nodes);
+    WGT_HIP(ctx, hipMemcpy(level.data(), sc.node_level, level.size(), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> order, begin;
+    const std::string deep = refit_levels(level.data(), sc.n_nodes, order, begin);
+    if (!deep.empty()) return fail(ctx, WGT_E_INVALID, deep);
+    if ((rc = ensure(ctx, ctx->level_order, ((size_t)sc.n_nodes + 1) * 4))) return rc;
+    WGT_HIP(ctx, hipMemcpy(ctx->level_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+    ctx->level_begin = std::move(begin);
+  }
+  const uint32_t* d_order = (const uint32_t*)ctx->level_order.p;
+  uint32_t* d_max_exp = (uint32_t*)ctx->level_order.p + sc.n_nodes;
+  const wgt_triangle* d_moved;
+  if ((rc = stage(ctx, wgt_ctx::kMoved, tris, (size_t)n_tris * sizeof(wgt_triangle), d_moved))) return rc;
+  if ((rc = sync_stream(ctx))) return rc;  // the staging copy belongs to the host part's time
+  hipEvent_t e0 = pool_event(ctx, 0), e1 = pool_event(ctx, 1);
+  if (!e0 || !e1) return fail(ctx, WGT_E_HIP, "hipEventCreate failed");
+  const clock::time_point t1 = clock::now();
+  // from here on the resident tree changes: a HIP failure leaves it undefined until the next upload
+  for (auto& sl : ctx->slots) sl.clean_nb = 0;  // as an upload
+  WGT_HIP(ctx, hipEventRecord(e0, s));
+  WGT_HIP(ctx, hipMemsetAsync(d_max_exp, 0, 4, s));
+  WGT_HIP(ctx, launch_refit_tris(sc, d_moved, s));
+  for (size_t l = ctx->level_begin.size() - 1; l-- > 0;)
+    WGT_HIP(ctx, launch_refit_nodes(sc, d_order + ctx->level_begin[l], ctx->level_begin[l + 1] - ctx->level_begin[l], s));
+  float root[kNode4Floats];
+  if ((rc = fetch(ctx, root, sc.nodes, sizeof root)) || (rc = sync_stream(ctx))) return rc;
+  const double M = compact_bound(extent, root), G = std::ldexp(M, -21);
+  WGT_HIP(ctx, launch_refit_step(sc, G, d_max_exp, s));
+  uint32_t max_exp = 0;
+  if ((rc = fetch(ctx, &max_exp, d_max_exp, 4)) || (rc = sync_stream(ctx))) return rc;
+  const float step = pow2f(kCompactMinExp + (int)max_exp);
+  WGT_HIP(ctx, launch_refit_compact(sc, step, G, s));
+  WGT_HIP(ctx, hipEventRecord(e1, s));
+  WGT_HIP(ctx, hipEventSynchronize(e1));
+  WGT_HIP(ctx, hipEventElapsedTime(&ctx->refit_device_ms, e0, e1));
+  ctx->refit_host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  sc.cstep = step;
+  sc.rcstep = 1.0f / step;  // a power of two: exact
+  sc.cbound = (float)M;
+  ctx->info.bvh_compact_step = step;
+  ctx->info.node_form = reference_node_form(sc);
+  return WGT_OK;
+}
+
+int wgt_update_timing(const wgt_ctx* ctx, float* host_ms, float* device_ms) {
+  if (!ctx || !host_ms || !device_ms) return fail(nullptr, WGT_E_INVALID, "null argument");
+  *host_ms = ctx->refit_host_ms;
+  *device_ms = ctx->refit_device_ms;
+  return WGT_OK;
+}
+
+int wgt_bvh_read(wgt_ctx* ctx, float* nodes_out, uint32_t nodes_cap, float* tris_out, uint32_t* cnodes_out,
+                 int32_t* crefs_out, float* step_out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  const DevScene& sc = ctx->sc;
+  if (sc.n_tris == 0) return fail(ctx, WGT_E_INVALID, "the scene has no triangles, so no tree");
+  if ((nodes_out || cnodes_out || crefs_out) && nodes_cap < sc.n_nodes)
+    return fail(ctx, WGT_E_INVALID, "node capacity too small");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = use_drain(ctx)) return rc;
+  std::vector<float> nodes((size_t)sc.n_nodes * kNode4Floats);
+  std::vector<uint32_t> crecs((size_t)sc.n_nodes * kCRecordFloat4s * 4);
+  WGT_HIP(ctx, hipMemcpy(nodes.data(), sc.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+  WGT_HIP(ctx, hipMemcpy(crecs.data(), sc.cnodes, crecs.size() * 4, hipMemcpyDeviceToHost));
+  ExportImage(nodes.data(), crecs.data(), sc.n_nodes, nodes_out, cnodes_out, crefs_out);
+  if (tris_out)
+    WGT_HIP(ctx, hipMemcpy(tris_out, sc.tris, (size_t)sc.n_tris * kTriRecordBytes, hipMemcpyDeviceToHost));
+  if (step_out) *step_out = sc.cstep;
+  return WGT_OK;
+}
+
+int wgt_bvh_refit(const wgt_triangle* built_from, const wgt_triangle* now, uint32_t n_tris, float* nodes_out,
+                  uint32_t nodes_cap, float* tris_out, uint32_t* cnodes_out, int32_t* crefs_out, float* step_out,
+                  wgt_scene_info* info) {
+  if (!built_from || !now || n_tris == 0 || !info) return fail(nullptr, WGT_E_INVALID, "null triangles or info");
+  // what wgt_update_triangles refuses before it refits
+  const std::string bad = check_scene_limits(nullptr, 0, nullptr, 0, now, n_tris);
+  if (!bad.empty()) return fail(nullptr, WGT_E_INVALID, bad);
+  BvhOut bvh;
+  const std::string err = refit_for_export(built_from, now, n_tris, bvh);
+  if (!err.empty()) return fail(nullptr, WGT_E_INVALID, err);
+  *info = wgt_scene_info{};
+  fill_bvh_info(bvh, n_tris, ps_form_for(bvh, n_tris), *info);
+  info->device_bytes = (bvh.nodes.size() + bvh.tris.size() + bvh.tshade.size()) * 4;
+  if ((nodes_out || cnodes_out || crefs_out) && nodes_cap < bvh.n_nodes)
+    return fail(nullptr, WGT_E_INVALID, "node capacity too small");
+  if (nodes_out) std::memcpy(nodes_out, bvh.nodes.data(), bvh.nodes.size() * 4);
+  if (tris_out) std::memcpy(tris_out, bvh.tris.data(), bvh.tris.size() * 4);
+  if (cnodes_out) std::memcpy(cnodes_out, bvh.cnodes.data(), bvh.cnodes.size() * 4);
+  if (crefs_out) std::memcpy(crefs_out, bvh.crefs.data(), bvh.crefs.size() * 4);
+  if (step_out) *step_out = bvh.cstep;
   return WGT_OK;
 }
 

@@ -111,6 +111,30 @@ def bvh_build_compact(tris):
     return cn, cr, step.value
 
 
+def _tree_arrays(n_nodes, n_tris):
+    """Host arrays of a whole tree in the export layouts: nodes, leaf-ordered records, compact nodes, compact refs."""
+    return (np.zeros((n_nodes, 8, 4), np.float32), np.zeros((n_tris, 4, 4), np.float32),
+            np.zeros((n_nodes, 16), np.uint32), np.zeros((n_nodes, 4), np.int32))
+
+
+def bvh_refit(built_from, now):
+    """Host-only refit (wgt_bvh_refit): the tree an upload of `built_from` alone followed by
+    Context.update_triangles(now) must hold, as (info, nodes (n, 8, 4) f32, leaf-ordered tris (n_tris, 4, 4)
+    f32, cnodes (n, 16) u32, crefs (n, 4) i32, step): bvh_build's and bvh_build_compact's layouts."""
+    a = np.ascontiguousarray(built_from, TRI_DTYPE)
+    b = np.ascontiguousarray(now, TRI_DTYPE)
+    if len(a) != len(b):
+        raise ValueError(f"bvh_refit: {len(b)} triangles now, {len(a)} built from")
+    L = lib()
+    info = WgtSceneInfo()
+    step = ctypes.c_float(0.0)
+    check(L.wgt_bvh_refit(ptr(a), ptr(b), len(a), None, 0, None, None, None, ctypes.byref(step), ctypes.byref(info)))
+    nodes, recs, cn, cr = _tree_arrays(info.bvh_nodes, len(a))
+    check(L.wgt_bvh_refit(ptr(a), ptr(b), len(a), ptr(nodes), info.bvh_nodes, ptr(recs), ptr(cn), ptr(cr),
+                          ctypes.byref(step), ctypes.byref(info)))
+    return info.as_dict(), nodes, recs, cn, cr, step.value
+
+
 def camera_param(aspect: float, spp: int, seed: int, fovy: float = 40.0):
     """Camera::Update (camera.cpp:64-70) with an explicit seed instead of RandSeed()."""
     cam = np.zeros(1, CAMERA_DTYPE)
@@ -191,6 +215,29 @@ class Context:
         info = WgtSceneInfo()
         self._check(self._L.wgt_scene_info_get(self.h, ctypes.byref(info)))
         return info.as_dict()
+
+    def update_triangles(self, tris):
+        """Move the uploaded scene's triangles (wgt_update_triangles): the resident BVH is refit on the
+        device, not rebuilt.  Triangle i keeps its primitive id; len(tris) must be the uploaded count.
+        Synchronous; every render and query afterwards equals a fresh upload's, bit for bit."""
+        tris = np.ascontiguousarray(tris, TRI_DTYPE)
+        self._check(self._L.wgt_update_triangles(self.h, ptr(tris), len(tris)))
+
+    def update_timing(self):
+        """(host_ms, device_ms) of the last update_triangles (wgt_update_timing)."""
+        h, d = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._check(self._L.wgt_update_timing(self.h, ctypes.byref(h), ctypes.byref(d)))
+        return h.value, d.value
+
+    def bvh_read(self):
+        """The resident tree (wgt_bvh_read), in bvh_refit's layouts without the info:
+        (nodes, leaf-ordered tris, cnodes, crefs, step)."""
+        info = self.scene_info()
+        nodes, recs, cn, cr = _tree_arrays(info["bvh_nodes"], info["n_tris"])
+        step = ctypes.c_float(0.0)
+        self._check(self._L.wgt_bvh_read(self.h, ptr(nodes), info["bvh_nodes"], ptr(recs), ptr(cn), ptr(cr),
+                                         ctypes.byref(step)))
+        return nodes, recs, cn, cr, step.value
 
     def render_tile(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=("u8", "f32", "hit"), stats=False):
         tw = W if tw is None else tw
