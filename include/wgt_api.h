@@ -209,12 +209,46 @@ int wgt_bvh_build_compact(const wgt_triangle *tris, uint32_t n_tris, uint32_t *c
  * waits for every launch of the context, as an upload does, so launches queued before it see the
  * old triangles and launches after it the new ones.
  * A WGT_E_HIP failure during the refit itself leaves the tree undefined until the next upload.
- * Out of scope: a device-pointer input (its limit checks would need a device pass); moving quads,
- * lights and spheres; adding or removing triangles; any heuristic that rebuilds the tree. */
+ * Out of scope: moving quads, lights and spheres (indexed quads among them); adding or removing
+ * triangles; per-vertex shading data (normals, colours, texture coordinates: a triangle is shaded
+ * by its face normal and one colour); any heuristic that rebuilds the tree. */
 int wgt_update_triangles(wgt_ctx *ctx, const wgt_triangle *tris, uint32_t n_tris);
-/* Diagnostic: the last wgt_update_triangles' time in milliseconds, split into its host part
- * (checks, staging copy) and its device part (the refit kernels and two small readbacks, by
- * hipEvents). */
+/* The same update from DEVICE memory, so that a mesh a simulation, a skinning kernel or a tensor
+ * library moves on the device never leaves it.  Both calls are SYNCHRONOUS calls that take device
+ * pointers (unlike the _async calls, which return at once): the input is read after everything
+ * queued on `stream` before the call (NULL: the context's stream, a non-blocking stream that is
+ * not ordered after the legacy default stream), the call then waits for every
+ * launch of the context as wgt_update_triangles does, and it returns when the refit has ended, so
+ * the caller may overwrite the input at once.  The input is never written.  The result is that of
+ * wgt_update_triangles(ctx, T, n_tris) bit for bit (the resident tree, the scene report, every
+ * later render and query), where T is
+ *   wgt_update_triangles_device: the bytes of d_tris;
+ *   wgt_update_vertices_device:  T[i] = wgt_make_triangles(triangle i's three vertices, col_i,
+ *     emissive_i, translation = NULL), col_i and emissive_i the values triangle i was uploaded (or
+ *     last updated) with: the call carries no shading input and keeps them.  As there, a -0
+ *     coordinate becomes +0, and a zero-area triangle's face normal is NaN; which NaN (its sign and
+ *     payload) is unspecified and may differ from the host's.
+ * Order of checks, as wgt_update_triangles: NULL context; WGT_E_NOSCENE; then WGT_E_INVALID for a
+ * NULL d_tris or d_verts, for a scene without triangles, for n_tris other than the uploaded count,
+ * for a misaligned pointer, and for n_verts == 0 or, without indices, n_verts != 3 * n_tris.  Then
+ * a pass on the device checks every triangle against the scene limits (of the vertex form the
+ * record built from its vertices; an index >= n_verts is refused too, and no vertex is loaded
+ * through it): WGT_E_INVALID names the lowest-numbered such triangle in wgt_update_triangles'
+ * words.  A refusal leaves the scene exactly as it was.
+ * The pointers themselves are not validated: memory the device cannot read is the caller's error,
+ * as for every other device-pointer entry point. */
+/* d_tris: DEVICE array of n_tris wgt_triangle records, 16-byte aligned. */
+int wgt_update_triangles_device(wgt_ctx *ctx, const wgt_triangle *d_tris, uint32_t n_tris, void *stream);
+/* d_verts: DEVICE array of n_verts x 3 floats (4-byte aligned).
+ * d_index: DEVICE array of n_tris x 3 vertex indices.
+ * d_index == NULL means unindexed: triangle i uses vertices 3i, 3i+1, 3i+2,
+ * and n_verts must then be 3*n_tris. */
+int wgt_update_vertices_device(wgt_ctx *ctx, const float *d_verts, uint32_t n_verts,
+                               const uint32_t *d_index, uint32_t n_tris, void *stream);
+/* Diagnostic: the last update's time in milliseconds (of any of the three calls above), split into
+ * its host part, everything before the first refit kernel (checks; the staging copy of a host
+ * array; of the device forms the check pass on the device and its readback), and its device part
+ * (the refit kernels and two small readbacks, by hipEvents). */
 int wgt_update_timing(const wgt_ctx *ctx, float *host_ms, float *device_ms);
 /* Diagnostic (synchronous): copies the resident tree back in the export layouts of wgt_bvh_build
  * (nodes_out: bvh_nodes x 32 floats, tris_out: n_tris x 16 floats) and wgt_bvh_build_compact

@@ -84,6 +84,7 @@ EXPORTS = [
     "wgt_write_obj", "wgt_write_png", "wgt_bvh_build", "wgt_bvh_build_compact",
     "wgt_render_frames",
     "wgt_update_triangles", "wgt_update_timing", "wgt_bvh_read", "wgt_bvh_refit",
+    "wgt_update_triangles_device", "wgt_update_vertices_device",
 ]
 
 _lib = None
@@ -147,6 +148,8 @@ def lib():
         "wgt_bvh_build": (I, [P, U32, P, U32, P, ctypes.POINTER(WgtSceneInfo)]),
         "wgt_render_frames": (I, [P, P, U32, U32, P, U32, P, P]),
         "wgt_update_triangles": (I, [P, P, U32]),
+        "wgt_update_triangles_device": (I, [P, P, U32, P]),
+        "wgt_update_vertices_device": (I, [P, P, U32, P, U32, P]),
         "wgt_update_timing": (I, [P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_read": (I, [P, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_refit": (I, [P, P, U32, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(WgtSceneInfo)]),

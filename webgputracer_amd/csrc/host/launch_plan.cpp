@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 
@@ -29,14 +30,19 @@ std::string check_scene_limits(const wgt_quad* lq, uint32_t nlq, const wgt_spher
     if (!finite_within(sp[i].center, 3, kCoordLimit) || !finite_within(&sp[i].radius, 1, kCoordLimit))
       return "sphere " + std::to_string(i) + ": center and radius must be finite and within 2^40";
   for (uint32_t i = 0; i < nt; ++i) {
-    if (!finite_within(tr[i].v0, 3, kCoordLimit) || !finite_within(tr[i].e1, 3, kCoordLimit) ||
-        !finite_within(tr[i].e2, 3, kCoordLimit))
-      return "triangle " + std::to_string(i) + ": vertices must be finite and within 2^40";
-    // |det| <= |e1| |e2| |d| <= (sqrt(3) 2^30)^2 sqrt(3) 2^32 = 3 sqrt(3) 2^92 < 2^95 (edge components
-    // within 2^30, primary-direction components within 2^32): mt_test's short 1/det is exact
-    if (!finite_within(tr[i].e1, 3, kEdgeLimit) || !finite_within(tr[i].e2, 3, kEdgeLimit))
-      return "triangle " + std::to_string(i) + ": edge components must be within 2^30";
+    const std::string bad = check_triangle_limits(tr[i], i);
+    if (!bad.empty()) return bad;
   }
+  return "";
+}
+
+std::string check_triangle_limits(const wgt_triangle& t, uint32_t i) {
+  if (!finite_within(t.v0, 3, kCoordLimit) || !finite_within(t.e1, 3, kCoordLimit) || !finite_within(t.e2, 3, kCoordLimit))
+    return "triangle " + std::to_string(i) + ": vertices must be finite and within 2^40";
+  // |det| <= |e1| |e2| |d| <= (sqrt(3) 2^30)^2 sqrt(3) 2^32 = 3 sqrt(3) 2^92 < 2^95 (edge components
+  // within 2^30, primary-direction components within 2^32): mt_test's short 1/det is exact
+  if (!finite_within(t.e1, 3, kEdgeLimit) || !finite_within(t.e2, 3, kEdgeLimit))
+    return "triangle " + std::to_string(i) + ": edge components must be within 2^30";
   return "";
 }
 
@@ -202,6 +208,63 @@ std::string refit_for_export(const wgt_triangle* built_from, const wgt_triangle*
   const std::string err = build_for_export(built_from, n_tris, bvh);
   if (!err.empty()) return err;
   return refit_bvh(now, n_tris, scene_extent(nullptr, 0, nullptr, 0, now, n_tris), bvh);
+}
+
+std::string check_update_count(uint32_t scene_tris, uint32_t n_tris) {
+  if (scene_tris == 0) return "the scene has no triangles to update";
+  if (n_tris != scene_tris)
+    return "triangle count " + std::to_string(n_tris) + " differs from the uploaded " + std::to_string(scene_tris) +
+           " (an update moves triangles; upload to add or remove)";
+  return "";
+}
+
+static bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+std::string check_update_records(const void* d_tris, uint32_t scene_tris, uint32_t n_tris) {
+  if (!d_tris) return "null triangles";
+  const std::string bad = check_update_count(scene_tris, n_tris);
+  if (!bad.empty()) return bad;
+  if (!aligned_to(d_tris, 16)) return "misaligned triangles: device wgt_triangle records must be 16-byte aligned";
+  return "";
+}
+
+std::string check_update_vertices(const void* d_verts, uint32_t n_verts, const void* d_index, uint32_t scene_tris,
+                                  uint32_t n_tris) {
+  if (!d_verts) return "null vertices";
+  const std::string bad = check_update_count(scene_tris, n_tris);
+  if (!bad.empty()) return bad;
+  if (!aligned_to(d_verts, 4) || !aligned_to(d_index, 4))
+    return "misaligned vertices or indices: device floats and indices must be 4-byte aligned";
+  if (n_verts == 0) return "vertex count 0";
+  if (!d_index && (uint64_t)n_verts != 3ull * n_tris)
+    return "vertex count " + std::to_string(n_verts) + " is not 3 x " + std::to_string(n_tris) +
+           " triangles (unindexed vertices: three per triangle)";
+  return "";
+}
+
+void triangle_of_vertices(const float* verts, wgt_triangle& t) {
+  t = wgt_triangle{};
+  for (int c = 0; c < 3; ++c) {
+    const float v0 = verts[c] + 0.0f, v1 = verts[3 + c] + 0.0f, v2 = verts[6 + c] + 0.0f;
+    t.v0[c] = v0;
+    t.e1[c] = v1 - v0;
+    t.e2[c] = v2 - v0;
+  }
+}
+
+std::string check_vertex_index(const uint32_t index[3], uint32_t n_verts, uint32_t i) {
+  for (int c = 0; c < 3; ++c)
+    if (index[c] >= n_verts)
+      return "triangle " + std::to_string(i) + ": vertex index " + std::to_string(index[c]) +
+             " is not below the vertex count " + std::to_string(n_verts);
+  return "";
+}
+
+double checked_extent(const RefitCheck& r) {
+  double m;
+  static_assert(sizeof m == sizeof r.extent_bits, "a double's bits");
+  std::memcpy(&m, &r.extent_bits, sizeof m);
+  return m;
 }
 
 double compact_bound(double extent, const float* root_node) {

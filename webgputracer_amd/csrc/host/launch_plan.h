@@ -19,14 +19,16 @@ namespace wgt {
 // short 1/det of Moller-Trumbore), primary ray directions within 2^32
 // (scattered directions are unit).  Everything else in the kernels is exact for
 // any input.  Outside the limits the calls fail with WGT_E_INVALID.
-constexpr double kCoordLimit = 1099511627776.0;  // 2^40
-constexpr double kEdgeLimit = 1073741824.0;      // 2^30: triangle edges (Moller-Trumbore's short 1/det)
+// kCoordLimit (2^40) and kEdgeLimit (2^30) are in wgt_internal.h: the device check of moved
+// triangles (wgt_refit.hip) applies them too.
 constexpr double kPrimaryDirLimit = 4294967296.0;  // 2^32
 bool finite_within(const float* v, int n, double lim);  // NaN and inf fail too
 // The checks return their refusal's text, empty when fine: of a scene's primitives, and of the
 // camera and frame of a render or G-buffer call (check_render_args)
 std::string check_scene_limits(const wgt_quad* lq, uint32_t nlq, const wgt_sphere* sp, uint32_t ns,
                                const wgt_triangle* tr, uint32_t nt);
+// ... of one triangle, which the refusal names as triangle i
+std::string check_triangle_limits(const wgt_triangle& t, uint32_t i);
 std::string check_frame_args(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th);
 // Largest |coordinate| any point of the scene's primitives can have (quad corners,
 // sphere boxes, triangle vertices): hit points, i.e. secondary ray origins, lie
@@ -62,6 +64,24 @@ std::string build_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& 
 std::string refit_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh);
 // wgt_bvh_refit: the tree an upload of `built_from` alone followed by an update to `now` holds
 std::string refit_for_export(const wgt_triangle* built_from, const wgt_triangle* now, uint32_t n_tris, BvhOut& bvh);
+// The argument checks of the updates, in the calls' order after the context and the scene; each
+// returns the refusal's text, empty when fine.  wgt_update_triangles: the count alone.
+std::string check_update_count(uint32_t scene_tris, uint32_t n_tris);
+// wgt_update_triangles_device: null, the count, then the alignment rule: 16 bytes (the kernels read
+// the records as float4s).
+std::string check_update_records(const void* d_tris, uint32_t scene_tris, uint32_t n_tris);
+// wgt_update_vertices_device: null vertices, the count, 4-byte alignment of the vertices and of the
+// indices (may be null: unindexed), then n_verts: not 0, and 3 x n_tris when unindexed.
+std::string check_update_vertices(const void* d_verts, uint32_t n_verts, const void* d_index, uint32_t scene_tris,
+                                  uint32_t n_tris);
+// Wording the device check's refusal (RefitCheck::first_bad = i) from that one triangle read back:
+// check_triangle_limits on a record; of the vertex form first check_vertex_index on the triangle's
+// three indices, then check_triangle_limits on triangle_of_vertices of its gathered 9 floats (v0, e1,
+// e2 as wgt_make_triangles without a translation builds them, which is what the device checked).
+void triangle_of_vertices(const float* verts, wgt_triangle& t);
+std::string check_vertex_index(const uint32_t index[3], uint32_t n_verts, uint32_t i);
+// The triangles' term of scene_extent that the device check reduced (no triangle was refused).
+double checked_extent(const RefitCheck& r);
 // What the device refit (wgt_update_triangles) decides on the host.  The compact codes' bound M
 // for ray origins within kOriginBoundScale x `extent`, from the refit root node alone (32 floats):
 // every box of the tree nests in the root's slots exactly, so they hold the largest |coordinate|.

@@ -242,12 +242,44 @@ hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n
 hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
                           const wgt_hit_buffers& out, float* d_rays, hipStream_t stream);
 
+// The scene limits of coordinates and of triangle edge components (host/launch_plan.h states why),
+// here because the device check of moved triangles applies them as the host's check_scene_limits does.
+constexpr double kCoordLimit = 1099511627776.0;  // 2^40
+constexpr double kEdgeLimit = 1073741824.0;      // 2^30: triangle edges (Moller-Trumbore's short 1/det)
+
+// Moved triangles as vertices on the device (wgt_update_vertices_device): n_verts x 3 floats;
+// triangle i uses vertices index[3i .. 3i + 2], or 3i .. 3i + 2 when index is null.
+struct MovedVerts {
+  const float* verts;
+  uint32_t n_verts;
+  const uint32_t* index;
+  uint32_t n_tris;
+};
+// What the device check of moved triangles reduces (launch_check_tris, launch_check_verts): both
+// reductions are exact, so their results do not depend on the order of waves.
+struct RefitCheck {
+  unsigned long long extent_bits;  // max, over the triangles within the limits, of their scene_extent term:
+                                   // a non-negative double's bits, which order as the values do
+  uint32_t first_bad;              // min index of a triangle beyond the limits; kNoBadTriangle: none
+  uint32_t pad;
+};
+constexpr uint32_t kNoBadTriangle = 0xffffffffu;  // every byte 0xff: one memset over first_bad and pad
 
 // Launchers implemented in wgt_refit.hip: the refit of the resident tree to moved triangles, in
 // this order on one stream, after every launch that reads the scene has ended.  They write the
 // scene's tree parts (the pointers of sc are const for every other kernel).
 // The records and shading records from the n_tris moved triangles (device array, original order).
 hipError_t launch_refit_tris(const DevScene& sc, const wgt_triangle* d_moved, hipStream_t stream);
+// The same from moved vertices (MovedVerts): each record as wgt_make_triangles builds it from the
+// triangle's three vertices; the shading records keep their colour and emissive flag.
+hipError_t launch_refit_verts(const DevScene& sc, const MovedVerts& in, hipStream_t stream);
+// The device pass of wgt_update_triangles_device and wgt_update_vertices_device, before any of the
+// above: *d_out (extent_bits 0 and first_bad kNoBadTriangle before the launch) = the lowest-numbered triangle beyond the scene
+// limits (launch_plan.h check_triangle_limits; of the vertex form also one with an index >= n_verts,
+// through which nothing is loaded) and the triangles' term of scene_extent.  They read the input
+// alone, so they need no order with the launches that read the scene.
+hipError_t launch_check_tris(const wgt_triangle* d_moved, uint32_t n_tris, RefitCheck* d_out, hipStream_t stream);
+hipError_t launch_check_verts(const MovedVerts& in, RefitCheck* d_out, hipStream_t stream);
 // The boxes of the `count` nodes d_order lists, one tree level (launch_plan.h refit_levels), after
 // the level below it.
 hipError_t launch_refit_nodes(const DevScene& sc, const uint32_t* d_order, uint32_t count, hipStream_t stream);

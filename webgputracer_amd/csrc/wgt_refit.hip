@@ -5,12 +5,16 @@
 // coordinates is recomputed with the host builder's own operations (host/bvh.cpp RefitBvh is the
 // specification, and tests compare the device tree with it bit for bit):
 //   k_refit_tris     the 64-B records (tri_box, wgt_geom.h) and the 32-B shading records
+//   k_refit_verts    the same from moved vertices (wgt_update_vertices_device): the records and face normals
+//                    as wgt_make_triangles builds them, the shading records' colour and emissive flag kept
 //   k_refit_nodes    the 128-B nodes' boxes, one launch per tree level, deepest first: exact
 //                    min/max unions, so neither the order of lanes nor of operands matters
 //   k_refit_step     each node's smallest feasible step exponent (wgt_compact.h), one integer max
 //   k_refit_compact  the 64-B node part of the 80-B records, wgt_compact.h's f64 arithmetic
 // The runtime reads the root node back between the node and step kernels (the codes' margin
 // follows from it, launch_plan.h compact_bound) and the exponent before the last one.
+// Moved triangles in device memory are checked first by k_check_tris or k_check_verts: the host's
+// limit check and scene_extent as two exact reductions, before any resident word is written.
 #include "wgt_compact.h"
 #include "wgt_internal.h"
 
@@ -50,6 +54,120 @@ k_refit_tris(float4* __restrict__ tris, float4* __restrict__ tshade, const float
   rec[3] = make_float4(lo.z, hi.x, hi.y, hi.z);
   tshade[(size_t)idx * 2] = make_float4(fn.x, fn.y, fn.z, ce.w);
   tshade[(size_t)idx * 2 + 1] = make_float4(ce.x, ce.y, ce.z, 0.0f);
+}
+
+// The Moller-Trumbore inputs of triangle t of moved vertices, as the host builds them
+// (wgt_make_triangles without a translation: Vertex::Translate adds +0, which turns a -0
+// coordinate into +0; then triangle.cpp's e1 = v1 - v0, e2 = v2 - v0).  False, and no vertex
+// loaded, when an index is not below n_verts; t < n_tris.  The 36-B stride is read as dwords.
+__device__ __forceinline__ bool gather_tri(const MovedVerts& in, uint32_t t, f3& v0, f3& e1, f3& e2) {
+  uint32_t k[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint64_t at = (uint64_t)t * 3u + (uint32_t)c;
+    const uint64_t v = in.index ? (uint64_t)in.index[at] : at;
+    if (v >= in.n_verts) return false;
+    k[c] = (uint32_t)v;
+  }
+  f3 p[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* v = in.verts + (size_t)k[c] * 3;
+    p[c] = f3{v[0] + 0.0f, v[1] + 0.0f, v[2] + 0.0f};
+  }
+  v0 = p[0];
+  e1 = p[1] - p[0];
+  e2 = p[2] - p[0];
+  return true;
+}
+
+// Lane i rewrites leaf-ordered record i as k_refit_tris does, from the vertices of its triangle idx,
+// and the first half of that triangle's shading record: the face normal in include/wgt/vec.h's
+// operations and order (glm::normalize(glm::cross(e1, e2)): cross, dot, 1 / sqrt, scale; a
+// zero-area triangle's is NaN) beside the emissive flag it read there.  The colour half stays.
+__global__ void __launch_bounds__(kRefitBlock)
+k_refit_verts(float4* __restrict__ tris, float4* __restrict__ tshade, MovedVerts in) {
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  if (i >= in.n_tris) return;
+  float4* rec = tris + (size_t)i * kTriFloat4s;
+  const uint32_t idx = __float_as_uint(rec[0].w);
+  if (idx >= in.n_tris) return;  // never: the upload's records hold a permutation of 0..n_tris-1
+  f3 v0, e1, e2;
+  if (!gather_tri(in, idx, v0, e1, e2)) return;  // never: the check pass refused such an index
+  f3 lo, hi;
+  tri_box(v0, e1, e2, lo, hi);
+  const f3 c = cross(e1, e2);
+  const float inv = 1.0f / sqrt_rn(dot(c, c));
+  rec[0] = make_float4(v0.x, v0.y, v0.z, __uint_as_float(idx));
+  rec[1] = make_float4(e1.x, e1.y, e1.z, lo.x);
+  rec[2] = make_float4(e2.x, e2.y, e2.z, lo.y);
+  rec[3] = make_float4(lo.z, hi.x, hi.y, hi.z);
+  float4* sh = tshade + (size_t)idx * 2;
+  const float emissive = sh[0].w;
+  sh[0] = make_float4(c.x * inv, c.y * inv, c.z * inv, emissive);
+}
+
+// The check of moved triangles before a refit from device memory.  One triangle's terms: bad = its
+// index when check_scene_limits refuses it (v0, e1, e2 finite and within 2^40, edge components
+// within 2^30; NaN fails every comparison), else kNoBadTriangle; ext = the bits of its term of
+// scene_extent in f64, 0 for a refused one (the extent is not used then).
+__device__ __forceinline__ unsigned long long abs_bits(double x) {
+  return (unsigned long long)__double_as_longlong(__builtin_fabs(x));
+}
+__device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ void check_term(uint32_t i, f3 v0, f3 e1, f3 e2, uint32_t& bad, unsigned long long& ext) {
+  const float v[3] = {v0.x, v0.y, v0.z}, a[3] = {e1.x, e1.y, e1.z}, b[3] = {e2.x, e2.y, e2.z};
+  const float coord = (float)kCoordLimit, edge = (float)kEdgeLimit;  // powers of two: exact
+  bool ok = true;
+  unsigned long long m = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ok = ok && __builtin_fabsf(v[c]) <= coord && __builtin_fabsf(a[c]) <= edge && __builtin_fabsf(b[c]) <= edge;
+    const double d = v[c];
+    m = max_u64(max_u64(m, abs_bits(d)), max_u64(abs_bits(d + a[c]), abs_bits(d + b[c])));
+  }
+  bad = ok ? kNoBadTriangle : i;
+  ext = ok ? m : 0ull;
+}
+// ... reduced over the wave, then one vector atomic each per wave that has something to say:
+// an integer min and an integer max, so the result does not depend on any order.  Every lane of
+// the block calls it (lanes past the end with kNoBadTriangle and 0).
+__device__ __forceinline__ void check_reduce(uint32_t bad, unsigned long long ext, RefitCheck* __restrict__ out) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    bad = min(bad, (uint32_t)__shfl_xor((int)bad, off, 64));
+    ext = max_u64(ext, __shfl_xor(ext, off, 64));
+  }
+  if ((threadIdx.x & 63u) == 0u) {
+    if (bad != kNoBadTriangle) atomicMin(&out->first_bad, bad);
+    if (ext != 0ull) atomicMax(&out->extent_bits, ext);
+  }
+}
+
+__global__ void __launch_bounds__(kRefitBlock)
+k_check_tris(const float4* __restrict__ moved, uint32_t n_tris, RefitCheck* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  uint32_t bad = kNoBadTriangle;
+  unsigned long long ext = 0;
+  if (i < n_tris) {
+    const float4* t = moved + (size_t)i * 5;
+    const float4 v0 = t[0], e1 = t[1], e2 = t[2];
+    check_term(i, f3{v0.x, v0.y, v0.z}, f3{e1.x, e1.y, e1.z}, f3{e2.x, e2.y, e2.z}, bad, ext);
+  }
+  check_reduce(bad, ext, out);
+}
+
+// The vertex form checks the record k_refit_verts will build; an index not below n_verts fails too.
+__global__ void __launch_bounds__(kRefitBlock) k_check_verts(MovedVerts in, RefitCheck* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  uint32_t bad = kNoBadTriangle;
+  unsigned long long ext = 0;
+  if (i < in.n_tris) {
+    f3 v0, e1, e2;
+    if (gather_tri(in, i, v0, e1, e2)) check_term(i, v0, e1, e2, bad, ext);
+    else bad = i;
+  }
+  check_reduce(bad, ext, out);
 }
 
 // Lane j refits node order[j] of one level: a leaf slot's box is the union of its triangles'
@@ -149,6 +267,25 @@ hipError_t launch_refit_tris(const DevScene& sc, const wgt_triangle* d_moved, hi
   if (sc.n_tris == 0) return hipSuccess;
   k_refit_tris<<<refit_grid(sc.n_tris), kRefitBlock, 0, stream>>>((float4*)sc.tris, (float4*)sc.tshade,
                                                                   (const float4*)d_moved, sc.n_tris);
+  return hipGetLastError();
+}
+
+hipError_t launch_refit_verts(const DevScene& sc, const MovedVerts& in, hipStream_t stream) {
+  if (in.n_tris != sc.n_tris) return hipErrorInvalidValue;  // never: the call's argument checks
+  if (sc.n_tris == 0) return hipSuccess;
+  k_refit_verts<<<refit_grid(sc.n_tris), kRefitBlock, 0, stream>>>((float4*)sc.tris, (float4*)sc.tshade, in);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_tris(const wgt_triangle* d_moved, uint32_t n_tris, RefitCheck* d_out, hipStream_t stream) {
+  if (n_tris == 0) return hipSuccess;
+  k_check_tris<<<refit_grid(n_tris), kRefitBlock, 0, stream>>>((const float4*)d_moved, n_tris, d_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_verts(const MovedVerts& in, RefitCheck* d_out, hipStream_t stream) {
+  if (in.n_tris == 0) return hipSuccess;
+  k_check_verts<<<refit_grid(in.n_tris), kRefitBlock, 0, stream>>>(in, d_out);
   return hipGetLastError();
 }
 

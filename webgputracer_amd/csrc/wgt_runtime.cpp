@@ -54,9 +54,9 @@ struct wgt_ctx {
   // scratch for the synchronous entry points: the renders' tile list, outputs and counters; the
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
   // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
-  // a refit's moved triangles
+  // a refit's moved triangles; the device check's result (RefitCheck)
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kMoved, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kCheck, kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -541,21 +541,22 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   return WGT_OK;
 }
 
-int wgt_update_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris) {
-  using clock = std::chrono::steady_clock;
-  const clock::time_point t0 = clock::now();
-  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
-  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
-  if (!tris) return fail(ctx, WGT_E_INVALID, "null triangles");
-  if (ctx->sc.n_tris == 0) return fail(ctx, WGT_E_INVALID, "the scene has no triangles to update");
-  if (n_tris != ctx->sc.n_tris)
-    return fail(ctx, WGT_E_INVALID, "triangle count " + std::to_string(n_tris) + " differs from the uploaded " +
-                                        std::to_string(ctx->sc.n_tris) + " (an update moves triangles; upload to add or remove)");
-  // a refusal leaves the device untouched: under the limits every triangle box is finite
-  const std::string bad = check_scene_limits(nullptr, 0, nullptr, 0, tris, n_tris);
-  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
-  const double extent = std::max(ctx->fixed_extent, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris));
-  WGT_HIP(ctx, hipSetDevice(ctx->device));
+namespace {
+
+using refit_clock = std::chrono::steady_clock;
+
+// The moved triangles of an update whose checks have passed: host records (staged here), device
+// records, or device vertices (verts.verts non-null).
+struct MovedInput {
+  const wgt_triangle* host_tris;
+  const wgt_triangle* d_tris;
+  MovedVerts verts;
+};
+
+// The refit that the three updates share, after their checks: `extent` is the scene's with the new
+// triangles, t0 the call's start (the host part of wgt_update_timing ends at the first refit
+// kernel).  The entry points differ only in how the records get written.
+int refit_resident(wgt_ctx* ctx, refit_clock::time_point t0, double extent, const MovedInput& in) {
   int rc;
   if ((rc = use_drain(ctx))) return rc;  // no launch on any stream may still read the old tree
   DevScene& sc = ctx->sc;
@@ -572,17 +573,20 @@ int wgt_update_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris
   }
   const uint32_t* d_order = (const uint32_t*)ctx->level_order.p;
   uint32_t* d_max_exp = (uint32_t*)ctx->level_order.p + sc.n_nodes;
-  const wgt_triangle* d_moved;
-  if ((rc = stage(ctx, wgt_ctx::kMoved, tris, (size_t)n_tris * sizeof(wgt_triangle), d_moved))) return rc;
-  if ((rc = sync_stream(ctx))) return rc;  // the staging copy belongs to the host part's time
+  const wgt_triangle* d_moved = in.d_tris;
+  if (in.host_tris) {
+    if ((rc = stage(ctx, wgt_ctx::kMoved, in.host_tris, (size_t)sc.n_tris * sizeof(wgt_triangle), d_moved))) return rc;
+    if ((rc = sync_stream(ctx))) return rc;  // the staging copy belongs to the host part's time
+  }
   hipEvent_t e0 = pool_event(ctx, 0), e1 = pool_event(ctx, 1);
   if (!e0 || !e1) return fail(ctx, WGT_E_HIP, "hipEventCreate failed");
-  const clock::time_point t1 = clock::now();
+  const refit_clock::time_point t1 = refit_clock::now();
   // from here on the resident tree changes: a HIP failure leaves it undefined until the next upload
   for (auto& sl : ctx->slots) sl.clean_nb = 0;  // as an upload
   WGT_HIP(ctx, hipEventRecord(e0, s));
   WGT_HIP(ctx, hipMemsetAsync(d_max_exp, 0, 4, s));
-  WGT_HIP(ctx, launch_refit_tris(sc, d_moved, s));
+  if (in.verts.verts) WGT_HIP(ctx, launch_refit_verts(sc, in.verts, s));
+  else WGT_HIP(ctx, launch_refit_tris(sc, d_moved, s));
   for (size_t l = ctx->level_begin.size() - 1; l-- > 0;)
     WGT_HIP(ctx, launch_refit_nodes(sc, d_order + ctx->level_begin[l], ctx->level_begin[l + 1] - ctx->level_begin[l], s));
   float root[kNode4Floats];
@@ -603,6 +607,92 @@ int wgt_update_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris
   ctx->info.bvh_compact_step = step;
   ctx->info.node_form = reference_node_form(sc);
   return WGT_OK;
+}
+
+// The device check of moved triangles in device memory, on the caller's stream `s` (so after
+// everything queued there), and its result read back; the stream has drained when it returns, so
+// the refit on the context's stream may read the input.  It writes a scratch word of the
+// context's alone: a refusal leaves the scene as it was.
+int check_on_device(wgt_ctx* ctx, hipStream_t s, const wgt_triangle* d_tris, const MovedVerts& verts, RefitCheck& out) {
+  RefitCheck* d_check;
+  if (int rc = scratch(ctx, wgt_ctx::kCheck, sizeof(RefitCheck), d_check)) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(&d_check->extent_bits, 0, sizeof d_check->extent_bits, s));
+  WGT_HIP(ctx, hipMemsetAsync(&d_check->first_bad, 0xff, 2 * sizeof(uint32_t), s));  // kNoBadTriangle
+  if (verts.verts) WGT_HIP(ctx, launch_check_verts(verts, d_check, s));
+  else WGT_HIP(ctx, launch_check_tris(d_tris, ctx->sc.n_tris, d_check, s));
+  WGT_HIP(ctx, hipMemcpyAsync(&out, d_check, sizeof out, hipMemcpyDeviceToHost, s));
+  WGT_HIP(ctx, hipStreamSynchronize(s));
+  return WGT_OK;
+}
+
+}  // namespace
+
+int wgt_update_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris) {
+  const refit_clock::time_point t0 = refit_clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (!tris) return fail(ctx, WGT_E_INVALID, "null triangles");
+  std::string bad = check_update_count(ctx->sc.n_tris, n_tris);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  // a refusal leaves the device untouched: under the limits every triangle box is finite
+  bad = check_scene_limits(nullptr, 0, nullptr, 0, tris, n_tris);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  const double extent = std::max(ctx->fixed_extent, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris));
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  return refit_resident(ctx, t0, extent, MovedInput{tris, nullptr, MovedVerts{}});
+}
+
+int wgt_update_triangles_device(wgt_ctx* ctx, const wgt_triangle* d_tris, uint32_t n_tris, void* stream) {
+  const refit_clock::time_point t0 = refit_clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  std::string bad = check_update_records(d_tris, ctx->sc.n_tris, n_tris);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream_or_own(ctx, stream);
+  RefitCheck chk;
+  if (int rc = check_on_device(ctx, s, d_tris, MovedVerts{}, chk)) return rc;
+  if (chk.first_bad != kNoBadTriangle) {
+    if (chk.first_bad >= n_tris) return fail(ctx, WGT_E_HIP, "the device check named a triangle past the end");
+    wgt_triangle t;
+    WGT_HIP(ctx, hipMemcpy(&t, d_tris + chk.first_bad, sizeof t, hipMemcpyDeviceToHost));
+    bad = check_triangle_limits(t, chk.first_bad);
+    return fail(ctx, WGT_E_INVALID, bad.empty() ? "triangle " + std::to_string(chk.first_bad) + ": beyond the scene limits" : bad);
+  }
+  const double extent = std::max(ctx->fixed_extent, checked_extent(chk));
+  return refit_resident(ctx, t0, extent, MovedInput{nullptr, d_tris, MovedVerts{}});
+}
+
+int wgt_update_vertices_device(wgt_ctx* ctx, const float* d_verts, uint32_t n_verts, const uint32_t* d_index,
+                               uint32_t n_tris, void* stream) {
+  const refit_clock::time_point t0 = refit_clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  std::string bad = check_update_vertices(d_verts, n_verts, d_index, ctx->sc.n_tris, n_tris);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream_or_own(ctx, stream);
+  const MovedVerts verts{d_verts, n_verts, d_index, n_tris};
+  RefitCheck chk;
+  if (int rc = check_on_device(ctx, s, nullptr, verts, chk)) return rc;
+  if (chk.first_bad != kNoBadTriangle) {  // read that triangle back and word the refusal as the host form does
+    const uint32_t i = chk.first_bad;
+    if (i >= n_tris) return fail(ctx, WGT_E_HIP, "the device check named a triangle past the end");
+    uint32_t k[3] = {3u * i, 3u * i + 1u, 3u * i + 2u};  // unindexed: within n_verts = 3 n_tris
+    if (d_index) WGT_HIP(ctx, hipMemcpy(k, d_index + (size_t)3 * i, sizeof k, hipMemcpyDeviceToHost));
+    bad = check_vertex_index(k, n_verts, i);
+    if (bad.empty()) {
+      float v[9];
+      for (int c = 0; c < 3; ++c)
+        WGT_HIP(ctx, hipMemcpy(v + 3 * c, d_verts + (size_t)3 * k[c], 3 * sizeof(float), hipMemcpyDeviceToHost));
+      wgt_triangle t;
+      triangle_of_vertices(v, t);
+      bad = check_triangle_limits(t, i);
+    }
+    return fail(ctx, WGT_E_INVALID, bad.empty() ? "triangle " + std::to_string(i) + ": beyond the scene limits" : bad);
+  }
+  const double extent = std::max(ctx->fixed_extent, checked_extent(chk));
+  return refit_resident(ctx, t0, extent, MovedInput{nullptr, nullptr, verts});
 }
 
 int wgt_update_timing(const wgt_ctx* ctx, float* host_ms, float* device_ms) {

@@ -223,8 +223,24 @@ class Context:
         tris = np.ascontiguousarray(tris, TRI_DTYPE)
         self._check(self._L.wgt_update_triangles(self.h, ptr(tris), len(tris)))
 
+    def update_triangles_device(self, d_tris, n_tris, stream=0):
+        """update_triangles from device memory (wgt_update_triangles_device): d_tris is the raw device
+        address of n_tris TRI_DTYPE records, 16-byte aligned.  Synchronous: the records are read after
+        everything queued on `stream` (0 = the context's), and may be overwritten once it returns."""
+        self._check(self._L.wgt_update_triangles_device(self.h, ctypes.c_void_p(d_tris or None), n_tris,
+                                                        ctypes.c_void_p(stream or None)))
+
+    def update_vertices_device(self, d_verts, n_verts, n_tris, d_index=0, stream=0):
+        """The same from moved vertices (wgt_update_vertices_device): d_verts is the raw device address of
+        n_verts x 3 float32, d_index that of n_tris x 3 uint32 vertex indices (0 = unindexed: triangle i
+        uses vertices 3i .. 3i + 2, and n_verts must be 3 * n_tris).  Each triangle becomes what
+        make_triangles builds from its vertices and keeps its colour and emissive flag."""
+        self._check(self._L.wgt_update_vertices_device(self.h, ctypes.c_void_p(d_verts or None), n_verts,
+                                                       ctypes.c_void_p(d_index or None), n_tris,
+                                                       ctypes.c_void_p(stream or None)))
+
     def update_timing(self):
-        """(host_ms, device_ms) of the last update_triangles (wgt_update_timing)."""
+        """(host_ms, device_ms) of the last update, of any form (wgt_update_timing)."""
         h, d = ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._L.wgt_update_timing(self.h, ctypes.byref(h), ctypes.byref(d)))
         return h.value, d.value
