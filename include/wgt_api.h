@@ -379,6 +379,47 @@ int wgt_render_gbuffer_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t
                              uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
                              const wgt_hit_buffers *d_out, float *d_rays, void *stream);
 
+/* ---- denoising (no reference counterpart) --------------------------------- */
+/* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered W x H image, guided
+ * by the first-hit G-buffer of the same pixels and demodulated by its albedo; no colour-distance
+ * weight (DESIGN.md §4.7 states the arithmetic operation by operation; tests/denoise_restatement.py
+ * is the same in numpy, and the result equals it bit for bit).  A pixel is filtered when it hit a
+ * primitive that is not emissive and its guides and colour are finite and within 2^100; every other
+ * pixel (lights, misses, NaN) passes through bit for bit and is never averaged into a neighbour.
+ * Guides whose normals are far from unit length can overflow a weight to NaN in a filtered pixel; the
+ * sign and payload of such a NaN are unspecified. */
+#define WGT_DENOISE_DEMODULATE 1u
+typedef struct {
+  uint32_t iterations;   /* 1..8 (default 5): pass i (from 0) taps at a step of 2^i pixels */
+  uint32_t normal_power; /* 0..10 (default 7): the normal weight max0(n.n') is squared this many times */
+  float sigma_pos;       /* finite, > 0 (default 1.0): scene units per pixel of step, along the normal */
+  uint32_t flags;        /* WGT_DENOISE_DEMODULATE (default): filter colour / albedo, multiply back after */
+} wgt_denoise_params;    /* 16 bytes */
+int wgt_denoise_defaults(wgt_denoise_params *out);
+/* Bytes of device scratch wgt_denoise_async needs for a W x H image (a multiple of 256: 64 per
+ * pixel); 0 for a size it refuses. */
+size_t wgt_denoise_workspace_bytes(uint32_t W, uint32_t H);
+/* rgba32f_in: W x H x 4 floats, row-major, the rgba32f output of wgt_render_tile (or of one full-frame
+ * tile of wgt_render_tiles_async); guides: the planar records of the same W x H pixels as
+ * wgt_render_gbuffer writes them, of which prim, pos, norm, col and flags are required and dist is
+ * ignored.  Outputs: rgba32f_out (alpha is the input's) and rgba8_out (the renderer's rgba8unorm
+ * store of the same rgb, alpha 255); one of the two may be NULL.  params NULL = the defaults.
+ * No scene is needed.  Order of checks, each WGT_E_INVALID naming the argument, nothing launched:
+ * NULL context; NULL input or guides; a NULL required guide; both outputs NULL; W or H 0 or above
+ * 32768, or W * H above 2^25; parameters out of range; (async) NULL workspace, one not 256-byte
+ * aligned, workspace_bytes below wgt_denoise_workspace_bytes(W, H).
+ * Synchronous, HOST pointers; allocates and frees its own device workspace. */
+int wgt_denoise(wgt_ctx *ctx, const wgt_denoise_params *params, uint32_t W, uint32_t H, const float *rgba32f_in,
+                const wgt_hit_buffers *guides, float *rgba32f_out, uint8_t *rgba8_out);
+/* DEVICE pointers (d_guides: a host struct of device pointers), ordered on `stream` (NULL = the
+ * context's), returns once queued.  The input and the guides are never written.  d_rgba32f_out may
+ * equal d_rgba32f_in: the input is consumed into the workspace before anything is written.  The
+ * workspace is the caller's and holds nothing between calls: two calls on two streams with two
+ * workspaces may overlap. */
+int wgt_denoise_async(wgt_ctx *ctx, const wgt_denoise_params *params, uint32_t W, uint32_t H,
+                      const float *d_rgba32f_in, const wgt_hit_buffers *d_guides, void *d_workspace,
+                      size_t workspace_bytes, float *d_rgba32f_out, void *d_rgba8_out, void *stream);
+
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,
  * sqrt_fast, div_rn) against correctly rounded results (the f64 operation rounded

@@ -38,6 +38,15 @@ class WgtHitBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in HIT_FIELDS]
 
 
+WGT_DENOISE_DEMODULATE = 1  # wgt_denoise_params.flags
+
+
+class WgtDenoiseParams(ctypes.Structure):
+    """wgt_denoise_params (16 bytes); wgt_denoise_defaults fills the defaults."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("normal_power", ctypes.c_uint32), ("sigma_pos", ctypes.c_float),
+                ("flags", ctypes.c_uint32)]
+
+
 class WgtStats(ctypes.Structure):
     _fields_ = [("queries", ctypes.c_uint64), ("traced_rays", ctypes.c_uint64), ("samples", ctypes.c_uint64),
                 ("nan_rays", ctypes.c_uint64), ("node_visits", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64),
@@ -85,6 +94,7 @@ EXPORTS = [
     "wgt_render_frames",
     "wgt_update_triangles", "wgt_update_timing", "wgt_bvh_read", "wgt_bvh_refit",
     "wgt_update_triangles_device", "wgt_update_vertices_device",
+    "wgt_denoise_defaults", "wgt_denoise_workspace_bytes", "wgt_denoise", "wgt_denoise_async",
 ]
 
 _lib = None
@@ -153,6 +163,11 @@ def lib():
         "wgt_update_timing": (I, [P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_read": (I, [P, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_refit": (I, [P, P, U32, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(WgtSceneInfo)]),
+        "wgt_denoise_defaults": (I, [ctypes.POINTER(WgtDenoiseParams)]),
+        "wgt_denoise_workspace_bytes": (ctypes.c_size_t, [U32, U32]),
+        "wgt_denoise": (I, [P, ctypes.POINTER(WgtDenoiseParams), U32, U32, P, ctypes.POINTER(WgtHitBuffers), P, P]),
+        "wgt_denoise_async": (I, [P, ctypes.POINTER(WgtDenoiseParams), U32, U32, P, ctypes.POINTER(WgtHitBuffers), P,
+                                  ctypes.c_size_t, P, P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -340,4 +340,72 @@ void bind_scene(DevScene& sc, const size_t off[kSceneParts], const void* base) {
   sc.node_level = (const uint8_t*)at(kPartLevel);
 }
 
+wgt_denoise_params denoise_defaults() { return wgt_denoise_params{5u, 7u, 1.0f, WGT_DENOISE_DEMODULATE}; }
+
+static bool denoise_size_ok(uint32_t W, uint32_t H) {
+  return W != 0 && H != 0 && W <= kDenoiseMaxDim && H <= kDenoiseMaxDim && (uint64_t)W * H <= kDenoiseMaxPixels;
+}
+static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+size_t denoise_workspace_bytes(uint32_t W, uint32_t H) {
+  if (!denoise_size_ok(W, H)) return 0;
+  const size_t n = (size_t)W * H;
+  return align_up(n * 32, kDenoiseAlign) + 2 * align_up(n * 16, kDenoiseAlign);
+}
+
+std::string check_denoise_args(const wgt_denoise_params* params, uint32_t W, uint32_t H, const void* in,
+                               const wgt_hit_buffers* guides, const void* out32, const void* out8) {
+  if (!in) return "null input image";
+  if (!guides) return "null guides";
+  if (!guides->prim) return "null guides.prim";
+  if (!guides->pos) return "null guides.pos";
+  if (!guides->norm) return "null guides.norm";
+  if (!guides->col) return "null guides.col";
+  if (!guides->flags) return "null guides.flags";
+  if (!out32 && !out8) return "null outputs: rgba32f_out and rgba8_out are both null";
+  if (!denoise_size_ok(W, H))
+    return "image size " + std::to_string(W) + " x " + std::to_string(H) + ": W and H must be 1.." +
+           std::to_string(kDenoiseMaxDim) + " and W * H at most " + std::to_string(kDenoiseMaxPixels);
+  if (params) {
+    if (params->iterations < 1 || params->iterations > kDenoiseMaxIterations)
+      return "params.iterations " + std::to_string(params->iterations) + " is not in 1.." +
+             std::to_string(kDenoiseMaxIterations);
+    if (params->normal_power > kDenoiseMaxNormalPower)
+      return "params.normal_power " + std::to_string(params->normal_power) + " is not in 0.." +
+             std::to_string(kDenoiseMaxNormalPower);
+    if (!(params->sigma_pos > 0.0f) || !std::isfinite(params->sigma_pos)) return "params.sigma_pos must be finite and > 0";
+    if (params->flags & ~WGT_DENOISE_DEMODULATE) return "params.flags has bits other than WGT_DENOISE_DEMODULATE";
+  }
+  return "";
+}
+
+std::string check_denoise_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H) {
+  if (!ws) return "null workspace";
+  if (!aligned_to(ws, kDenoiseAlign)) return "misaligned workspace: it must be 256-byte aligned";
+  const size_t need = denoise_workspace_bytes(W, H);
+  if (ws_bytes < need)
+    return "workspace_bytes " + std::to_string(ws_bytes) + " is below the " + std::to_string(need) +
+           " that wgt_denoise_workspace_bytes asks for";
+  return "";
+}
+
+DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t H) {
+  DenoisePlan p{};
+  p.W = W; p.H = H;
+  p.iterations = params.iterations;
+  p.normal_power = params.normal_power;
+  p.demodulate = params.flags & WGT_DENOISE_DEMODULATE;
+  p.tiled_max_step = std::min(env_u32("WGT_DENOISE_TILED_STEP", kDenoiseTiledStep), kDenoiseMaxTiledStep);
+  // two roundings, then an exact power of four (which may round once more among the denormals):
+  // the restatement's kz0 * f32(4.0 ** -i)
+  const float kz0 = 1.0f / (params.sigma_pos * params.sigma_pos);
+  for (uint32_t i = 0; i < kDenoiseMaxIterations; ++i) p.kz[i] = kz0 * std::ldexp(1.0f, -2 * (int)i);
+  const size_t n = (size_t)W * H;
+  p.off_rec = 0;
+  p.off_it0 = align_up(n * 32, kDenoiseAlign);
+  p.off_it1 = p.off_it0 + align_up(n * 16, kDenoiseAlign);
+  p.bytes = p.off_it1 + align_up(n * 16, kDenoiseAlign);
+  return p;
+}
+
 }  // namespace wgt

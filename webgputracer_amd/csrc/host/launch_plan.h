@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../wgt_denoise.h"
 #include "../wgt_internal.h"
 #include "bvh.h"
 
@@ -108,5 +109,19 @@ ScenePlan pack_scene(const wgt_quad* lights, uint32_t n_lights, const wgt_quad* 
                      const BvhImage& image);
 // Points sc's seven parts into the allocation at `base`.
 void bind_scene(DevScene& sc, const size_t off[kSceneParts], const void* base);
+
+// The denoiser (wgt_denoise, wgt_denoise_async).  Its defaults; the workspace of a
+// W x H image in bytes, 0 for a size the calls refuse (DenoisePlan states the layout); and the calls'
+// checks after the context, in their order, each returning the refusal's text, empty when fine:
+// null input, guides and required guide fields, both outputs null, the size, the parameters (null:
+// the defaults); then of the async form the workspace: null, alignment, size.
+wgt_denoise_params denoise_defaults();
+size_t denoise_workspace_bytes(uint32_t W, uint32_t H);
+std::string check_denoise_args(const wgt_denoise_params* params, uint32_t W, uint32_t H, const void* in,
+                               const wgt_hit_buffers* guides, const void* out32, const void* out8);
+std::string check_denoise_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H);
+// Of arguments that passed the checks: the workspace layout, each pass's kz in the fp32 operations of
+// the specification, and the largest step that runs LDS-tiled (WGT_DENOISE_TILED_STEP, at most 16).
+DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t H);
 
 }  // namespace wgt

@@ -940,6 +940,70 @@ int wgt_render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, ui
   return sync_stream(ctx);
 }
 
+int wgt_denoise_defaults(wgt_denoise_params* out) {
+  if (!out) return fail(nullptr, WGT_E_INVALID, "null params");
+  *out = denoise_defaults();
+  return WGT_OK;
+}
+
+size_t wgt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return denoise_workspace_bytes(W, H); }
+
+int wgt_denoise_async(wgt_ctx* ctx, const wgt_denoise_params* params, uint32_t W, uint32_t H, const float* d_rgba32f_in,
+                      const wgt_hit_buffers* d_guides, void* d_workspace, size_t workspace_bytes, float* d_rgba32f_out,
+                      void* d_rgba8_out, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  std::string bad = check_denoise_args(params, W, H, d_rgba32f_in, d_guides, d_rgba32f_out, d_rgba8_out);
+  if (bad.empty()) bad = check_denoise_workspace(d_workspace, workspace_bytes, W, H);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const DenoisePlan plan = plan_denoise(params ? *params : denoise_defaults(), W, H);
+  // no scene is read: the launches are ordered by the stream alone
+  WGT_HIP(ctx, launch_denoise(plan, (const float4*)d_rgba32f_in, *d_guides, d_workspace, (float4*)d_rgba32f_out,
+                              (uchar4*)d_rgba8_out, stream_or_own(ctx, stream)));
+  return WGT_OK;
+}
+
+int wgt_denoise(wgt_ctx* ctx, const wgt_denoise_params* params, uint32_t W, uint32_t H, const float* rgba32f_in,
+                const wgt_hit_buffers* guides, float* rgba32f_out, uint8_t* rgba8_out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  const std::string bad = check_denoise_args(params, W, H, rgba32f_in, guides, rgba32f_out, rgba8_out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  // one allocation of the call's own, freed before it returns: the image (filtered in place), the
+  // guides' planes (prim, pos, norm, col, flags), the rgba8 output, the workspace
+  const size_t n = (size_t)W * H, ws_bytes = denoise_workspace_bytes(W, H);
+  const size_t part[] = {n * 16, n * 4, n * 12, n * 12, n * 12, n, n * 4, ws_bytes};
+  const void* src[] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->col, guides->flags};
+  size_t off[9] = {0};
+  for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
+  struct Alloc {
+    char* p = nullptr;
+    ~Alloc() {
+      if (p) (void)hipFree(p);
+    }
+  } mem;
+  if (hipMalloc((void**)&mem.p, off[8]) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[8]) + " bytes failed");
+  }
+  for (int k = 0; k < 6; ++k)
+    WGT_HIP(ctx, hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream));
+  wgt_hit_buffers dev{};
+  dev.prim = (uint32_t*)(mem.p + off[1]);
+  dev.pos = (float*)(mem.p + off[2]);
+  dev.norm = (float*)(mem.p + off[3]);
+  dev.col = (float*)(mem.p + off[4]);
+  dev.flags = (uint8_t*)(mem.p + off[5]);
+  float* const d_img = (float*)mem.p;
+  void* const d_out8 = rgba8_out ? mem.p + off[6] : nullptr;
+  int rc = wgt_denoise_async(ctx, params, W, H, d_img, &dev, mem.p + off[7], ws_bytes, rgba32f_out ? d_img : nullptr,
+                             d_out8, ctx->stream);
+  if (rc == WGT_OK && rgba32f_out) rc = fetch(ctx, rgba32f_out, d_img, n * 16);
+  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, d_out8, n * 4);
+  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
+  return rc != WGT_OK ? rc : rs;
+}
+
 int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8]) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
   if (!counts) return fail(ctx, WGT_E_INVALID, "null counts");

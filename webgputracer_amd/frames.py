@@ -21,6 +21,8 @@ single-frame render.
 
 `--gbuffer` also writes NNN_gbuffer.npz next to each NNN.png: the first-hit G-buffer of the frame
 (Context.render_gbuffer with the frame's camera and seed), the guides a denoiser asks for.
+`--denoise` also writes NNN_denoised.png: the frame through wgt_denoise (an edge-avoiding a-trous
+filter guided by that G-buffer), computed on the device on the batch's stream.
 
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -86,16 +88,23 @@ class FrameRenderer:
         return {"prim": g["prim"], "depth": g["dist"], "pos": g["pos"], "normal": g["norm"], "albedo": g["col"],
                 "flags": g["flags"]}
 
-    def stream(self, frame_batches, depth: int = 2):
+    def stream(self, frame_batches, depth: int = 2, denoised=None):
         """Yield (batch, {frame: (H, W, 4) uint8}) for each batch of `frame_batches`, in
         order.  Batch k renders on pipeline stream k % depth into buffer set k % depth;
         it is issued before batch k-1 is handed out, so the device always has the next
         launch queued behind the running one.  Host copies are made on the batch's own
         stream once its launch is done (no pinned buffers: torch's host allocator would
-        outlive the context's streams)."""
+        outlive the context's streams).
+
+        denoised: a dict that receives {frame: (H, W, 4) uint8} of each batch as it is handed out,
+        the frame through wgt_denoise with the default parameters.  The batch's launch then also
+        fills a device rgba32f buffer, and each of its frames gets, on the batch's stream, its
+        G-buffer (render_gbuffer_async with the frame's one tile) and denoise_async to a device
+        rgba8 buffer; nothing leaves the device but the two rgba8 images."""
         import torch
 
         from ._lib import TILE_DTYPE
+        from .tracer import denoise_workspace_bytes
 
         dev = torch.device("cuda", self.ctx.device)
         W, H = self.W, self.H
@@ -104,11 +113,21 @@ class FrameRenderer:
             return
         streams = [torch.cuda.ExternalStream(self.ctx.pipeline_stream(i), device=dev) for i in range(depth)]
         d_out = [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
+        d_dn = None
+        if denoised is not None:
+            n, ws_bytes = W * H, denoise_workspace_bytes(W, H)
+            d_f32 = [torch.empty((nmax, H, W, 4), dtype=torch.float32, device=dev) for _ in range(depth)]
+            d_dn = [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
+            # per set: one frame's guides (reused frame after frame in stream order) and the workspace
+            d_vec = [torch.empty((3, 3, n), dtype=torch.float32, device=dev) for _ in range(depth)]
+            d_prim = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(depth)]
+            d_flags = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(depth)]
+            d_ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(depth)]
         pending = []
         for k, b in enumerate(frame_batches):
             j = k % depth
             if len(pending) == depth:  # the oldest batch in flight holds set j: hand it out first
-                yield self._finish(pending.pop(0), streams, d_out)
+                yield self._finish(pending.pop(0), streams, d_out, d_dn, denoised)
             s = streams[j]
             t = np.zeros(len(b), TILE_DTYPE)  # one full-frame tile per frame (wgt_render_frames' list)
             t["seed"] = np.asarray(b, np.uint32)
@@ -116,20 +135,32 @@ class FrameRenderer:
             with torch.cuda.stream(s):
                 d_tiles = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
                 self.ctx.render_tiles_async(self.cam, W, H, W, H, d_tiles.data_ptr(), len(b),
-                                            d_u8=d_out[j].data_ptr(), stream=s.cuda_stream)
+                                            d_u8=d_out[j].data_ptr(),
+                                            d_f32=d_f32[j].data_ptr() if d_dn else 0, stream=s.cuda_stream)
+                for i in range(len(b) if d_dn else 0):
+                    guides = {"prim": d_prim[j].data_ptr(), "pos": d_vec[j][0].data_ptr(),
+                              "norm": d_vec[j][1].data_ptr(), "col": d_vec[j][2].data_ptr(),
+                              "flags": d_flags[j].data_ptr()}
+                    self.ctx.render_gbuffer_async(self.cam, W, H, W, H, d_tiles.data_ptr() + i * TILE_DTYPE.itemsize, 1,
+                                                  stream=s.cuda_stream, **guides)
+                    self.ctx.denoise_async(W, H, d_f32[j][i].data_ptr(), d_ws[j].data_ptr(), ws_bytes,
+                                           d_u8_out=d_dn[j][i].data_ptr(), stream=s.cuda_stream, **guides)
                 d_tiles.record_stream(s)
             pending.append((k, b))
         while pending:
-            yield self._finish(pending.pop(0), streams, d_out)
+            yield self._finish(pending.pop(0), streams, d_out, d_dn, denoised)
 
     @staticmethod
-    def _finish(kb, streams, d_out):
+    def _finish(kb, streams, d_out, d_dn=None, denoised=None):
         import torch
 
         k, b = kb
         j = k % len(streams)
         with torch.cuda.stream(streams[j]):  # ordered after batch k's launch on its stream
             imgs = d_out[j][:len(b)].cpu().numpy()
+            if d_dn is not None:
+                dn = d_dn[j][:len(b)].cpu().numpy()
+                denoised.update({f: dn[i] for i, f in enumerate(b)})
         return b, {f: imgs[i] for i, f in enumerate(b)}
 
 
@@ -150,9 +181,14 @@ def main(argv=None):
     ap.add_argument("--gbuffer", action="store_true",
                     help="also write NNN_gbuffer.npz next to each NNN.png: prim, depth, pos, normal, albedo, flags "
                          "of each pixel's first hit (guides for a denoiser)")
+    ap.add_argument("--denoise", action="store_true",
+                    help="also write NNN_denoised.png next to each NNN.png: the frame through the edge-avoiding "
+                         "a-trous filter (wgt_denoise, default parameters), guided by its G-buffer on the device")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
         ap.error("--gbuffer needs --out")
+    if a.denoise and not a.out:
+        ap.error("--denoise needs --out")
     if a.frame[0] < 1 or a.frame[1] < a.frame[0]:
         ap.error("bad frame range")  # the C++ CLI's check (csrc/main.cpp)
     if not 1 <= a.pipeline <= 4:
@@ -185,10 +221,14 @@ def main(argv=None):
     pool = ThreadPoolExecutor(max_workers=workers) if a.out else None
     pending = collections.deque()
     t0 = time.perf_counter()
-    for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline):
+    denoised = {} if a.denoise else None
+    for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised):
         if a.out:
             for f in b:  # render.cpp:494-497
                 pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
+                if a.denoise:
+                    pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_denoised.png"),
+                                               denoised.pop(f)))
                 if a.gbuffer:
                     np.savez(os.path.join(a.out, f"{f:03d}_gbuffer.npz"), **fr.gbuffer(f))
             while len(pending) > 4 * workers:

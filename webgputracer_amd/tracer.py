@@ -16,8 +16,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtHitBuffers,
-                   WgtSceneInfo, WgtStats, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+                   WgtHitBuffers, WgtSceneInfo, WgtStats, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -162,6 +162,18 @@ def _device_hit_buffers(*fields):
 def build_id() -> str:
     """The loaded library's kernel build id (wgt_build_id: hash of the HIP sources and flags)."""
     return lib().wgt_build_id().decode()
+
+
+def denoise_defaults():
+    """wgt_denoise_defaults: a WgtDenoiseParams of the library's defaults."""
+    p = WgtDenoiseParams()
+    check(lib().wgt_denoise_defaults(ctypes.byref(p)))
+    return p
+
+
+def denoise_workspace_bytes(W: int, H: int) -> int:
+    """Bytes of device scratch Context.denoise_async needs for a W x H image (0: a size it refuses)."""
+    return int(lib().wgt_denoise_workspace_bytes(W, H))
 
 
 def device_count() -> int:
@@ -382,6 +394,59 @@ class Context:
         self._check(self._L.wgt_render_gbuffer_async(self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles),
                                                      n_tiles, ctypes.byref(bufs), ctypes.c_void_p(d_rays or None),
                                                      ctypes.c_void_p(stream or None)))
+
+    @staticmethod
+    def _denoise_params(iterations, normal_power, sigma_pos, demodulate):
+        """wgt_denoise_params: the library's defaults, with the arguments that are not None over them."""
+        p = denoise_defaults()
+        if iterations is not None:
+            p.iterations = iterations
+        if normal_power is not None:
+            p.normal_power = normal_power
+        if sigma_pos is not None:
+            p.sigma_pos = sigma_pos
+        p.flags = _lib.WGT_DENOISE_DEMODULATE if demodulate else 0
+        return p
+
+    def denoise(self, color, guides, iterations=None, normal_power=None, sigma_pos=None, demodulate=True,
+                want=("f32", "u8")):
+        """Edge-avoiding a-trous filter (wgt_denoise) of `color`, the (H, W, 4) float32 radiance of
+        render_tile, guided by `guides`, the dict render_gbuffer returns for the same pixels (prim, pos,
+        norm, col and flags are read).  None for a parameter takes the library's default (5 iterations,
+        normal_power 7, sigma_pos 1.0).  Returns {"f32": (H, W, 4) float32, "u8": (H, W, 4) uint8}, None
+        for an output not in `want`.  Lights, misses and non-finite pixels pass through unchanged."""
+        color = np.ascontiguousarray(color, np.float32)
+        if color.ndim != 3 or color.shape[2] != 4:
+            raise ValueError(f"denoise: color must be (H, W, 4), got {color.shape}")
+        H, W = color.shape[:2]
+        missing = [k for k in ("prim", "pos", "norm", "col", "flags") if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"denoise: guides lack {missing}")
+        planar = {k: np.ascontiguousarray(np.moveaxis(np.asarray(guides[k], np.float32).reshape(H, W, 3), -1, 0))
+                  for k in ("pos", "norm", "col")}
+        planar["prim"] = np.ascontiguousarray(guides["prim"], np.uint32).reshape(H, W)
+        planar["flags"] = np.ascontiguousarray(guides["flags"], np.uint8).reshape(H, W)
+        bufs = WgtHitBuffers(**{k: a.ctypes.data for k, a in planar.items()})
+        f32 = np.zeros((H, W, 4), np.float32) if "f32" in want else None
+        u8 = np.zeros((H, W, 4), np.uint8) if "u8" in want else None
+        p = self._denoise_params(iterations, normal_power, sigma_pos, demodulate)
+        self._check(self._L.wgt_denoise(self.h, ctypes.byref(p), W, H, ptr(color), ctypes.byref(bufs), ptr(f32),
+                                        ptr(u8)))
+        return {"f32": f32, "u8": u8}
+
+    def denoise_async(self, W, H, d_f32_in, d_workspace, workspace_bytes, prim=0, pos=0, norm=0, col=0, flags=0,
+                      d_f32_out=0, d_u8_out=0, iterations=None, normal_power=None, sigma_pos=None, demodulate=True,
+                      stream=0):
+        """Device-pointer launch (wgt_denoise_async; raw device addresses, 0 = NULL): the W x H rgba32f
+        image at d_f32_in, the G-buffer planes of render_gbuffer_async's single full-frame tile, a
+        workspace of denoise_workspace_bytes(W, H) bytes that is the caller's, and the outputs, of
+        which d_f32_out may equal d_f32_in.  Ordered on `stream` (0 = the context's)."""
+        bufs = _device_hit_buffers(prim, 0, pos, norm, col, flags)
+        p = self._denoise_params(iterations, normal_power, sigma_pos, demodulate)
+        self._check(self._L.wgt_denoise_async(self.h, ctypes.byref(p), W, H, ctypes.c_void_p(d_f32_in or None),
+                                              ctypes.byref(bufs), ctypes.c_void_p(d_workspace or None),
+                                              workspace_bytes, ctypes.c_void_p(d_f32_out or None),
+                                              ctypes.c_void_p(d_u8_out or None), ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
