@@ -1,11 +1,11 @@
 """Hit-record queries (wgt_trace_hits_async, wgt_render_gbuffer_async) against the closest-hit query
-(wgt_trace_rays_async, k_trace), on device-resident buffers, timed with device events.  Needs a GPU.
+(wgt_trace_rays_async: k_trace_hits with two fields), on device-resident buffers, timed with device events.  Needs a GPU.
 Workload, per mesh stand-in at default size: the ambient-occlusion rays of scripts/occlusion_probe.py
 (origins = the first hits of a 1920x1080 camera frame, cosine-hemisphere directions, seeded numpy).
 Sides:
-  baseline       wgt_trace_rays_async (k_trace)
-  hits_prim_dist wgt_trace_hits_async with prim and dist only: k_trace's outputs, the quad hit rebuilt
-                 after the traversal instead of before it
+  baseline       wgt_trace_rays_async (k_trace_hits with prim and dist only)
+  hits_prim_dist wgt_trace_hits_async with prim and dist only: the same launch through the other entry
+                 point (until k_trace was retired the baseline was that kernel)
   hits_all       wgt_trace_hits_async with all six fields (41 bytes more written per ray, 24 read)
   gbuffer_1080p  wgt_render_gbuffer_async, one 1920x1080 tile, 1 spp, all fields and the rays (its own
                  rays: the camera's, so its time compares with the others only per ray)
@@ -123,7 +123,7 @@ def measure(ctx, scene, o, d):
     for side, go, _ in sides:  # warm-up, and K per side from one timed launch
         timed(stream, go, 2)
         k[side] = max(1, math.ceil(500.0 / (reps * timed(stream, go, 3))))
-    for b in (pd, full):  # the new kernel's prim and dist are k_trace's
+    for b in (pd, full):  # every side's prim and dist are the closest-hit query's
         assert torch.equal(b["prim"], d_prim) and torch.equal(b["dist"].view(torch.int32), d_dist.view(torch.int32))
     ms = {side: [] for side, _, _ in sides}
     for _ in range(reps):  # alternating

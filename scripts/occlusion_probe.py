@@ -1,14 +1,14 @@
 """Occlusion queries (wgt_occluded_rays_async) against today's only other way to get the answer,
-the closest-hit query (wgt_trace_rays_async, k_trace) followed by a compare, on device-resident
+the closest-hit query (wgt_trace_rays_async: k_trace_hits with two fields) followed by a compare, on device-resident
 buffers, timed with device events.  Needs a GPU.  Workloads, per mesh stand-in at default size:
   A  ambient occlusion: origins = the first hits of a 1920x1080 camera frame (trace_rays),
      cosine-hemisphere directions (seeded numpy), max_dist = 50
   B  the same rays, max_dist = +inf
   C  point-to-point visibility between random pairs of points in the box, max_dist = |b - a|
 Each side runs `reps` (>= 10) alternating repetitions of K back-to-back launches, K sized so that a
-side does >= 0.5 s of work in all; the figure is the median repetition.  Prints one JSON line per
-workload and side (baseline, occluded): rays/s, the ratio to the
-baseline's rays/s and the share of occluded rays.
+side does >= 0.5 s of work in all; the figure is the median repetition, with the minimum and maximum
+beside it (the baseline's spread is the noise band).  Prints one JSON line per workload and side
+(baseline, occluded): rays/s, the ratio to the baseline's rays/s and the share of occluded rays.
   python scripts/occlusion_probe.py [scenes=sponza,bunny] [reps=10]"""
 import json
 import math
@@ -126,6 +126,7 @@ def measure(ctx, scene, name, o, d, lim):
     med = {side: float(np.median(v)) for side, v in ms.items()}
     for side, _ in sides:
         print(json.dumps({"scene": scene, "workload": name, "side": side, "rays": n, "ms": round(med[side], 4),
+                          "ms_min": round(min(ms[side]), 4), "ms_max": round(max(ms[side]), 4),
                           "rays_per_s": round(n / (med[side] * 1e-3)), "vs_baseline": round(med["baseline"] / med[side], 3),
                           "occluded_share": round(share, 4), "reps": reps, "launches_per_rep": k[side],
                           "build_id": w.build_id()}), flush=True)

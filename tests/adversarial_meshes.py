@@ -181,7 +181,7 @@ NOREF = 0x7FFFFFFF
 
 def push_walk(tree, o, d):
     """tests/test_split_stack.py's Lane with the whole stack in LDS (the default, unparked
-    k_render_ps: node_step, trav_resolve, tri_step of wgt_device.h), for all rays at once in numpy
+    k_render_ps: node_step, trav_resolve, tri_step of wgt_trav_ps.h), for all rays at once in numpy
     float64 over a test_split_stack.Tree.  A ray with a node to visit takes a node step, a ray with
     only an open leaf tests that leaf; any order is exact.  Checks on the way that every stack
     write lands below DevScene::stack (tree.stack).  Returns per ray:

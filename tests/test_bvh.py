@@ -267,7 +267,7 @@ def test_wave_budget_and_narrow_tree(monkeypatch):
 
 
 def stack24_roundtrip(v):
-    """Stack24 (wgt_device.h): a ref stored as its low 16 bits and its bits 16..23 as a signed byte,
+    """Stack24 (wgt_trav_ps.h): a ref stored as its low 16 bits and its bits 16..23 as a signed byte,
     read back as (int8 << 16) | uint16."""
     v = np.asarray(v, np.int64)
     lo = (v & 0xFFFF).astype(np.uint16)

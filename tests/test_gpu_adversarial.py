@@ -1,5 +1,5 @@
 """The kernels on the meshes of tests/adversarial_meshes.py: the trees tests/test_bvh_adversarial.py
-checks on the CPU, through the ray queries (k_trace, k_trace_hits, k_occluded), the render kernels
+checks on the CPU, through the ray queries (k_trace_hits, k_occluded), the render kernels
 in every stack form (k_render_ps unparked at 6 and 5 waves, parked with the default and the
 smallest LDS stack, on both node forms and on the narrow tree; the simple k_render) and the
 G-buffer pass.  Every other GPU test runs benign trees; these reach the builder's depth limit and

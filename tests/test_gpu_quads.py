@@ -1,4 +1,4 @@
-"""GPU parity of the quad scan without per-quad distances (wgt_device.h quad_scan_fast, DESIGN.md
+"""GPU parity of the quad scan without per-quad distances (wgt_hit.h quad_scan_fast, DESIGN.md
 §3.2 "quad distance") where it matters: rays whose two nearest quads tie, or almost tie, in the
 rounded distance the reference compares (path_tracer.wgsl:314-338).  The scene doubles the back
 wall one ulp nearer the camera (later in scan order), so every ray that reaches the back wall
@@ -38,7 +38,7 @@ def test_double_wall_render_parity(ctx, wgt, oracle, kernel, tris, monkeypatch):
 
 @pytest.mark.parametrize("kind", ["double_wall", "edges"])
 def test_quad_ties_trace_rays(ctx, wgt, oracle, kind):
-    """wgt_trace_rays (k_trace, the IEEE quad distance t) on rays aimed at the doubled back wall or
+    """wgt_trace_rays (k_trace_hits, the IEEE quad distance t) on rays aimed at the doubled back wall or
     at the lines where two walls meet (exactly and a few ulps off): prim ids and distances
     bit-exact against the oracle's reference scan."""
     L, Q, S = wgt.cornell_scene()

@@ -309,7 +309,7 @@ def test_occlusion_bound_covered_box(ctx, wgt, oracle):
 def _case_overflow(wgt, oracle):
     """Finite rays whose intermediates overflow.  (a) |d| = 2^59 from inside the box, with a
     sphere 1e6 away: h^2 and a c are both infinite, the discriminant is NaN, the reference
-    accepts the sphere with a NaN distance and k_occluded must answer from sample_hit.  (b) one
+    accepts the sphere with a NaN distance and k_occluded must answer from closest_hit.  (b) one
     huge direction component beside ordinary ones (2^100 to 2^126): t d overflows, o + t d is
     infinite, the quad coordinates are NaN, the distance infinite (inside the scans: with a
     direction this long the far sphere's discriminant is NaN too, and it is the answer).  (c) |d| = 2^70 to 2^120:

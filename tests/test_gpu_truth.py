@@ -3,7 +3,7 @@ and not through the oracle: the input sets of tests/test_truth_f64.py, the same 
 the same bounds.  Every other GPU test demands the oracle's bits, so a rule that the oracle, the
 restatements and the kernels all state wrongly passes them together; these do not.
 
-The ray queries (k_trace, k_trace_hits, k_occluded) read the 128-B nodes whatever WGT_CNODE says;
+The ray queries (k_trace_hits, k_occluded) read the 128-B nodes whatever WGT_CNODE says;
 the node forms and both kernel families are covered by the renders at the end.  Each test
 uploads its scene once and prints its share of decided rays and the largest error / E_t.
 """

@@ -1,4 +1,4 @@
-"""The persistent kernel's quad scan without per-quad distances (wgt_device.h quad_scan_fast,
+"""The persistent kernel's quad scan without per-quad distances (wgt_hit.h quad_scan_fast,
 DESIGN.md §3.2 "quad distance"), restated in numpy float32 and checked on the CPU against the
 oracle's reference scan (path_tracer.wgsl:314-338 over every quad, oracle/wgt_oracle.c) on rays
 built to make distance ties: a second back wall one ulp in front of the first (its rays hit both

@@ -1,7 +1,7 @@
 """CPU model of the parked persistent kernel's split traversal stack.
 
 k_render_ps keeps DevScene::ps_cap stack entries per lane in LDS and moves the rest to a
-per-lane global stack in its service passes (wgt_device.h park_fix): a lane leaves its
+per-lane global stack in its service passes (wgt_trav_ps.h park_fix): a lane leaves its
 traversal phase when a node step leaves it fewer than 4 free LDS entries, or when its LDS
 part runs empty while the global part still holds entries.  This restates that control flow
 per ray, in Python over the tree wgt_bvh_build exports (the uploaded tree), and checks on the
@@ -101,7 +101,7 @@ class Lane:
     def depth(self):
         return self.sp + len(self.glob)
 
-    # -- wgt_device.h trav_resolve
+    # -- wgt_trav_ps.h trav_resolve
     def resolve(self, cand):
         for _ in range(3):
             if cand == NOREF:

@@ -1,4 +1,4 @@
-"""slot_setup's division by host-computed multipliers (wgt_device.h udiv_by, round 6): q = mulhi(x, m)
+"""slot_setup's division by host-computed multipliers (wgt_pixel.h udiv_by, round 6): q = mulhi(x, m)
 with m = (2^32 - 1) / d is x / d or up to two less, and two correction steps make it exact.  The
 arithmetic restated in numpy uint64 and checked against x // d on random, extreme and near-multiple
 dividends for every divisor shape the launch produces (8x8 blocks per tile row and per tile)."""

@@ -54,7 +54,7 @@ std::string check_frame_args(const wgt_camera_param& cam, uint32_t W, uint32_t H
   if (!(cam.aspect == cam.aspect) || !(cam.fovy == cam.fovy)) return "NaN camera parameter";
   // the kernels pack a sample's (s_i, s_j) into 16 bits each and count sqrt_spp^2
   // samples in 32 bits: u32(sqrt(f32(spp))) must stay <= 65535 (spp < 2^32 - 2^8)
-  // the kernels keep a pixel's coordinates as 16-bit halves of one register (wgt_device.h Pixel)
+  // the kernels keep a pixel's coordinates as 16-bit halves of one register (wgt_pixel.h Pixel)
   if (W > 65535u || H > 65535u) return "frame width and height must be <= 65535";
   if ((uint32_t)__builtin_sqrtf((float)cam.spp) > 65535u) return "spp too large (u32(sqrt(f32(spp))) must be <= 65535)";
   if (!finite_within(cam.origin, 3, kCoordLimit) || !finite_within(cam.target, 3, kCoordLimit))

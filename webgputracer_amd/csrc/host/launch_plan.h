@@ -47,7 +47,7 @@ DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H);
 DevFrame tile_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th, uint32_t n_tiles);
 
 // The traversal stack of the built tree, entries per lane (DevScene::stack): + 1, the
-// speculative traversal parks a second leaf on the stack (wgt_device.h)
+// speculative traversal parks a second leaf on the stack (wgt_trav_ps.h)
 uint32_t stack_entries(const BvhOut& bvh);
 // The k_render_ps form of a scene (PsForm), under WGT_PS_WAVES, WGT_PARK and WGT_PS_CAP
 PsForm ps_form_for(const BvhOut& bvh, uint32_t n_tris);

@@ -17,7 +17,7 @@
 // staged as not valid (the tile).  No atomics, no scratch.
 #include "wgt_denoise.h"
 
-#include "wgt_device.h"
+#include "wgt_pixel.h"
 
 namespace wgt {
 

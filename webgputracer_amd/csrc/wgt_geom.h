@@ -49,7 +49,7 @@ WGT_HD void tri_box(f3 v0, f3 e1, f3 e2, f3& lo, f3& hi) {
 //     every origin under the limits (scene coordinates, camera and hit points within 2^40).  With
 //     1e-30 it overflowed from |o| > 3.4e8 on an axis the ray is parallel to: both planes of that
 //     axis then came out at the same infinity, the interval was empty and every triangle was missed.
-//     A caller ray (k_trace, k_occluded) parallel to an axis still overflows from |o| >= 2^41 there.
+//     A caller ray (k_trace_hits, k_occluded) parallel to an axis still overflows from |o| >= 2^41 there.
 //   * with ot finite every operand of fma(b, 1/d', ot) is finite, so a slab value is never NaN; where
 //     it overflows, the exact b/d' + ot is beyond 2^128 and ot's rounding moved it by at most 2^104:
 //     the infinity has the sign of (b - o)/d'.
@@ -99,7 +99,7 @@ WGT_HD f3 slab_offset(f3 o, f3 inv) { return f3{-(o.x * inv.x), -(o.y * inv.y), 
 // 2^100.  A |det| < 1e-12 is rejected whatever inv_det is, and for render rays |det| <=
 // |e1| |e2| |d| <= 3 sqrt(3) 2^92 < 2^95 (triangle edge components within 2^30, wgt_runtime.cpp
 // check_scene_limits; primary-direction components within 2^32, scattered ones unit), so the
-// result is the IEEE one; caller-supplied rays (k_trace) use IEEE.
+// result is the IEEE one; caller-supplied rays (the ray queries) use IEEE.
 template <bool SHORT = false>
 WGT_HD bool mt_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& tout) {
   f3 pvec = cross(d, e2);
@@ -130,7 +130,7 @@ constexpr int kTriRecordFloats = 16;  // the host / exported record (wgt_bvh_bui
 // float4 fewer per test but recompute the box (tri_box) for a candidate: slower on both
 // scenes, removed.
 constexpr uint32_t kTriRecordBytes = 64;
-// triangles tested per triangle step of the phase-split kernel (wgt_device.h tri_step): two
+// triangles tested per triangle step of the phase-split kernel (wgt_trav_ps.h tri_step): two
 // measured -1.6% on sponza, -1.3% on bunny at 1080p/256 spp; three and four +6%/+13% on sponza
 // (profiles/sweeps/r03_ab_tri_per_step.log)
 #ifndef WGT_TRI_PER_STEP

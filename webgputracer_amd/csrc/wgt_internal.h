@@ -35,7 +35,7 @@ constexpr int kStackNarrow = 25;
 constexpr int kPsWavesNoTris = 8;
 constexpr uint32_t kStack24Nodes = 1u << 16;  // 128-B node byte offsets < 2^23
 constexpr uint32_t kStack24Tris = 1u << 20;   // leaf refs ~(first << 3 | count - 1) >= -2^23
-// Parked traversal state per lane (wgt_device.h Park): 1/d (3), slab offsets (3), best t,
+// Parked traversal state per lane (wgt_trav_ps.h Park): 1/d (3), slab offsets (3), best t,
 // best index, node ref, stack top | global depth << 16, open leaf (offset | count)
 constexpr uint32_t kParkWords = 11;
 // The smallest LDS stack the parked kernel runs with: a node step needs 4 free entries
@@ -44,7 +44,7 @@ constexpr uint32_t kParkWords = 11;
 // past it
 constexpr uint32_t kMinPsCap = 8;
 
-// Dynamic LDS bytes of a traversal kernel launch (k_render, k_trace: 4-byte entries).
+// Dynamic LDS bytes of a traversal kernel launch (k_render and the ray queries: 4-byte entries).
 constexpr size_t stack_lds_bytes(uint32_t stack) { return (size_t)stack * kBlock * sizeof(int); }
 
 // The launch form of k_render_ps for a scene (ps_form): with the frame's node form (node_form)
@@ -165,7 +165,7 @@ struct DevFrame {
   int* ps_spill;
   uint32_t ps_spill_stride;
   // (2^32 - 1) / d for the 8x8 blocks per tile row (bx) and per tile (bx * by) of the launch
-  // (launch_render): slot_setup's divisions by them (wgt_device.h udiv_by)
+  // (launch_render, launch_gbuffer): slot_setup's divisions by them (wgt_pixel.h tile_grid, udiv_by)
   uint32_t div_bx, div_bpt;
 };
 
@@ -223,18 +223,19 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
 int node_form(const DevScene& sc, const DevFrame& fr);
 // Waves of k_render_ps resident on the whole device for this scene's LDS stack.
 hipError_t ps_resident_waves(const DevScene& sc, int device, uint32_t& waves);
+
+// Launcher implemented in wgt_selftest.hip (wgt_selftest_math)
 hipError_t launch_selftest_math(uint32_t n, uint32_t seed, unsigned long long* d_counts, hipStream_t stream);
-hipError_t launch_trace(const DevScene& sc, const float* d_rays, uint32_t n, uint32_t* prim,
-                        float* dist, hipStream_t stream);
 
 // Launcher implemented in wgt_occlusion.hip
-// out[i] = ray i hits a primitive closer than max_dist[i] (k_occluded; rays as launch_trace's).
+// out[i] = ray i hits a primitive closer than max_dist[i] (k_occluded; rays as launch_trace_hits').
 hipError_t launch_occluded(const DevScene& sc, const float* d_rays, const float* d_max_dist, uint32_t n,
                            uint8_t* d_out, hipStream_t stream);
 
 // Launchers implemented in wgt_hits.hip
-// Record i = the whole closest hit of ray i (k_trace_hits; rays as launch_trace's); out: device
-// pointers, a null field is not written.
+// Record i = the whole closest hit of ray i (k_trace_hits; d_rays: six planes of n floats, origin
+// x, y, z then direction x, y, z); out: device pointers, a null field is not written.  With prim
+// and dist alone this is the closest-hit query (wgt_trace_rays).
 hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n, const wgt_hit_buffers& out,
                              hipStream_t stream);
 // The record of sample 0's camera ray of every pixel of the tile list (k_gbuffer; fr as

@@ -1,4 +1,7 @@
-// wgt_kernels.hip — the MI355X (gfx950) path-tracing kernels.
+// wgt_kernels.hip — the MI355X (gfx950) render kernels: k_render, k_render_ps, the LPT order
+// of the persistent kernel's pixel queue (k_lpt_order) and their launch (launch_render).  The
+// ray queries are wgt_hits.hip and wgt_occlusion.hip; the device functions are wgt_hit.h,
+// wgt_trav.h, wgt_trav_ps.h and wgt_pixel.h.
 //
 // One lane per pixel, one wave (64 lanes = 8x8 pixels) per block.  Each lane runs
 // its pixel's whole compute_sample (path_tracer.wgsl:374-398); the per-pixel RNG
@@ -10,9 +13,9 @@
 // stack of 4-byte entries, or 3-byte ones in k_render_ps at 6 waves per SIMD;
 // Moller-Trumbore in fp32, wgt_geom.h), then the sphere scan.
 //
-// Two kernels compute bit-identical results:
-//  * k_render (simple, WGT_KERNEL=1): a flat per-lane loop, one closest-hit query +
-//    one shading step per iteration.
+// The two render kernels compute bit-identical results:
+//  * k_render (simple, WGT_KERNEL=1): a flat per-lane loop, one closest-hit query
+//    (closest_hit, wgt_trav.h) + one shading step per iteration.
 //  * k_render_ps (persistent, the default): the wave alternates a
 //    SERVICE phase (finalise the hit of lanes whose traversal ended, shade, start
 //    the next ray: camera ray or bounce, quad scan, root-node test) and a
@@ -33,7 +36,10 @@
 // the Cornell box.
 #include <type_traits>
 
-#include "wgt_device.h"
+#include "wgt_hit.h"
+#include "wgt_pixel.h"
+#include "wgt_trav.h"
+#include "wgt_trav_ps.h"
 
 namespace wgt {
 
@@ -45,7 +51,7 @@ k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* _
   extern __shared__ int s_stack[];  // sc.stack entries per lane (stack_lds_bytes)
   uint32_t po;
   Pixel px;
-  if (!pixel_setup(fr, tiles, po, px)) return;
+  if (!slot_setup(fr, tiles, blockIdx.x, threadIdx.x, po, px)) return;  // one pixel per lane
   int* lds = s_stack + threadIdx.x;
   const Light L{xyz(sc.quads[0]), xyz(sc.quads[1]), xyz(sc.quads[2])};
   const uint32_t nsamp = fr.sqrt_spp * fr.sqrt_spp;
@@ -68,7 +74,7 @@ k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* _
       continue;
     }
     Hit h;
-    sample_hit<TRIS, STATS>(sc, ro, rd, lds, h, st);
+    closest_hit<TRIS, STATS>(sc, ro, rd, lds, h, st);
     if (STATS) {
       ++c.q;
       if (nanray) ++c.nan; else ++c.tr;
@@ -310,7 +316,7 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
           // the root node is tested here: rays that miss every root child never
           // enter the traversal phase
           if (TRIS) {
-            WGT_REGION(cr_root, root_step<STATS, CN>(sc, t, lds, st));
+            WGT_REGION(cr_root, node_step<STATS, CN, STK, true>(sc, t, lds, st));
             if (PK) {
               park_put(P, t);
               P.st(9, (uint32_t)t.sp);  // a new ray's global stack is empty
@@ -424,22 +430,6 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
   }
 }
 
-template <bool TRIS>
-__global__ void __launch_bounds__(kBlock)
-k_trace(DevScene sc, const float* __restrict__ rays, uint32_t n, uint32_t* __restrict__ prim,
-        float* __restrict__ dist) {
-  extern __shared__ int s_stack[];  // sc.stack entries per lane (stack_lds_bytes)
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const f3 o = f3{rays[i], rays[(size_t)n + i], rays[2 * (size_t)n + i]};
-  const f3 d = f3{rays[3 * (size_t)n + i], rays[4 * (size_t)n + i], rays[5 * (size_t)n + i]};
-  Hit h;
-  TravStats st{};
-  sample_hit<TRIS, false, true>(sc, o, d, s_stack + threadIdx.x, h, st);  // any caller ray: IEEE t
-  prim[i] = h.prim;
-  dist[i] = h.dist;
-}
-
 // LPT order of the pixel blocks from the pre-pass costs, one workgroup: bucket
 // by the float bits of the cost (exponent + 3 mantissa bits: 8 buckets per
 // octave), most expensive bucket first (order within a bucket is arbitrary: the
@@ -474,87 +464,6 @@ k_lpt_order(uint32_t* __restrict__ cost, uint32_t blocks, uint32_t* __restrict__
     cost[i] = 0u;
     perm[atomicAdd(&s_cnt[lpt_bucket(c)], 1u)] = i;
   }
-}
-
-// wgt_selftest_math: the kernels' sqrt / division forms (wgt_math.h) against
-// correctly rounded results: the f64 operation rounded to f32, exact for sqrt and
-// division because f64 has more than 2*24 + 2 bits (double rounding is innocuous).
-//   sqrt_rn   on all 2^32 bit patterns;
-//   sqrt_fast on every pattern of its domain (all but 0 < x < 2^-96 and negative
-//             denormals);
-//   div_rn    on n pseudo-random (numerator, denominator) pairs from the quad plane
-//             distance's range under the render limits: |n| <= 2^44 of any exponent
-//             (zeros and denormals included), 2^-10 <= |d| < 2^35 (|d| >= kRayMin is
-//             tested before the division): the accept decision t in [kRayMin,
-//             kRayMax] must equal the IEEE one, and an accepted t its bits; and
-//             the reciprocal 1 / det of Moller-Trumbore (mt_test<true>) for 2^-40 <=
-//             |det| < 2^95 (the render limits' range past the 1e-12 rejection): its bits;
-//   the short reciprocal of the traversal's 1/d (trav_init, render rays: safe_inv_short) on every
-//             bit pattern with 2^-87 <= |x| <= 2^34 (kSlabDirMin, wgt_geom.h);
-//   the compiler's own lowerings (__builtin_sqrtf, n / d) on the same inputs.
-// NaN equals NaN.  counts: [0] sqrt tests, [1] sqrt_rn bad, [2] div tests, [3]
-// div_rn bad, [4] sqrt_fast tests, [5] sqrt_fast bad, [6] compiler sqrt bad, [7]
-// compiler div bad.
-__device__ __forceinline__ uint32_t st_hash(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-// sign and mantissa from h, biased exponent field uniform in [fmin, fmax]
-__device__ __forceinline__ float st_float(uint32_t h, uint32_t fmin, uint32_t fmax) {
-  const uint32_t e = fmin + (h >> 9) % (fmax - fmin + 1u);
-  return __uint_as_float((h & 0x80000000u) | (e << 23) | (st_hash(h) & 0x7fffffu));
-}
-__device__ __forceinline__ bool st_same(float a, float b) {
-  return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-}
-__device__ __forceinline__ bool st_accept(float t) { return !(t < kRayMin || kRayMax < t); }
-__global__ void __launch_bounds__(256) k_selftest_math(uint32_t n, uint32_t seed, unsigned long long* counts) {
-  uint32_t bad_s = 0, bad_f = 0, n_f = 0, bad_d = 0, bad_sc = 0, bad_dc = 0;
-  uint32_t bad_r = 0;  // the traversal reciprocal's failures
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += stride) {
-    const uint32_t bits = (uint32_t)i;
-    const float x = __uint_as_float(bits);
-    const float ref = (float)__builtin_sqrt((double)x);
-    bad_s += st_same(sqrt_rn(x), ref) ? 0u : 1u;
-    bad_sc += st_same(__builtin_sqrtf(x), ref) ? 0u : 1u;
-    const uint32_t mag = bits & 0x7fffffffu;
-    const bool fast_domain = mag == 0u || mag >= 0x0f800000u || (bits >> 31 && mag >= 0x00800000u);
-    if (fast_domain) {
-      ++n_f;
-      bad_f += st_same(sqrt_fast(x), ref) ? 0u : 1u;
-    }
-    if (mag >= __float_as_uint(kSlabDirMin) && mag <= __float_as_uint(0x1p34f))
-      bad_r += st_same(safe_inv_short(x), (float)(1.0 / (double)x)) ? 0u : 1u;
-  }
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint32_t)stride) {
-    const uint32_t h = st_hash(seed * 0x9e3779b9u + i), h2 = st_hash(h ^ 0x5bd1e995u);
-    const float nn = st_float(h, 0u, 127u + 44u);             // |n| <= 2^45 (zeros, denormals)
-    const float dd = st_float(h2, 127u - 10u, 127u + 34u);    // 2^-10 <= |d| < 2^35 (bound 2*sqrt(3)*2^32)
-    const float ref = (float)((double)nn / (double)dd);
-    const float q = div_rn(nn, dd);
-    const bool acc = st_accept(ref);
-    bad_d += (acc != st_accept(q) || (acc && !st_same(q, ref))) ? 1u : 0u;
-    bad_dc += st_same(nn / dd, ref) ? 0u : 1u;
-    // Moller-Trumbore's 1/det (mt_test<true>): every det the render limits admit past
-    // the |det| >= 1e-12 rejection, 2^-40 <= |det| < 2^95, must give the IEEE bits
-    const float det = st_float(st_hash(h2 ^ 0x2545f491u), 127u - 40u, 127u + 94u);
-    const float rref = (float)(1.0 / (double)det);
-    bad_d += st_same(div_rn(1.0f, det), rref) ? 0u : 1u;
-    bad_dc += st_same(1.0f / det, rref) ? 0u : 1u;
-  }
-  bad_d += bad_r;
-  atomicAdd(&counts[1], (unsigned long long)bad_s);
-  atomicAdd(&counts[3], (unsigned long long)bad_d);
-  atomicAdd(&counts[4], (unsigned long long)n_f);
-  atomicAdd(&counts[5], (unsigned long long)bad_f);
-  atomicAdd(&counts[6], (unsigned long long)bad_sc);
-  atomicAdd(&counts[7], (unsigned long long)bad_dc);
-}
-
-hipError_t launch_selftest_math(uint32_t n, uint32_t seed, unsigned long long* d_counts, hipStream_t stream) {
-  k_selftest_math<<<2048, 256, 0, stream>>>(n, seed, d_counts);
-  return hipGetLastError();
 }
 
 // The k_render_ps instantiation of a pass (STATS: counting, COST: the pre-pass) for the scene's
@@ -602,22 +511,18 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
                          uchar4* out8, float4* out32, uint32_t* outhit,
                          unsigned long long* counters, uint32_t resident, void* ws, size_t ws_cap,
                          hipStream_t stream, uint32_t& ws_clean_nb) {
-  const uint32_t bx = (fr.tw + 7u) / 8u, by = (fr.th + 7u) / 8u;
-  const uint64_t blocks = (uint64_t)bx * by * fr.n_tiles;
-  if (blocks == 0) return hipSuccess;
-  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-  DevFrame fm = fr;  // + slot_setup's division multipliers
-  fm.div_bx = 0xffffffffu / bx;
-  fm.div_bpt = 0xffffffffu / (bx * by);
+  uint32_t blocks;
+  DevFrame fm;  // + slot_setup's division multipliers
+  const hipError_t eg = tile_grid(fr, blocks, fm);
+  if (eg != hipSuccess || blocks == 0) return eg;
   const dim3 block(kBlock);
   const size_t lds = stack_lds_bytes(sc.stack);
-  const bool tris = sc.n_tris > 0;
   if (fr.kernel == 2) {
     const PsForm form = ps_form(sc);
     const size_t plds = ps_lds(form).total;
     if (blocks * 64ull > 0xffffffffull || resident == 0) return hipErrorInvalidValue;
     if (!ws || ws_cap < render_ws_bytes(sc, fr, resident)) return hipErrorInvalidValue;
-    const uint32_t nb = (uint32_t)blocks;
+    const uint32_t nb = blocks;
     const dim3 grid(nb < resident ? nb : resident);
     // workspace (the context's, used in stream order): [0] pre-pass queue,
     // [1] queue | cost[nb] | perm[nb]
@@ -661,14 +566,11 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
     ws_clean_nb = e == hipSuccess && lpt ? nb : 0u;
     return e;
   }
-  const dim3 grid((uint32_t)blocks);
-  if (counters) {
-    if (tris) k_render<true, true><<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, counters);
-    else k_render<false, true><<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, counters);
-  } else {
-    if (tris) k_render<true, false><<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, nullptr);
-    else k_render<false, false><<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, nullptr);
-  }
+  const dim3 grid(blocks);
+  using Kernel = void (*)(DevScene, DevFrame, const wgt_tile*, uchar4*, float4*, uint32_t*, unsigned long long*);
+  static constexpr Kernel k[2][2] = {{k_render<false, false>, k_render<false, true>},  // [triangles][counting]
+                                     {k_render<true, false>, k_render<true, true>}};
+  k[sc.n_tris > 0][counters != nullptr]<<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, counters);
   return hipGetLastError();
 }
 
@@ -688,15 +590,6 @@ hipError_t ps_resident_waves(const DevScene& sc, int device, uint32_t& waves) {
   if (e != hipSuccess) return e;
   waves = (uint32_t)((per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1));
   return hipSuccess;
-}
-
-hipError_t launch_trace(const DevScene& sc, const float* d_rays, uint32_t n, uint32_t* prim,
-                        float* dist, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-  if (sc.n_tris > 0) k_trace<true><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, n, prim, dist);
-  else k_trace<false><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, n, prim, dist);
-  return hipGetLastError();
 }
 
 }  // namespace wgt

@@ -2,12 +2,12 @@
 // distance limit (wgt_occluded_rays), in a translation unit of their own,
 // away from the render kernels and their register budgets.
 //
-// occluded[i] = 1 iff the closest-hit query (k_trace) on ray i returns a primitive and a
+// occluded[i] = 1 iff the closest-hit query (closest_hit, wgt_trav.h) on ray i returns a primitive and a
 // distance below max_dist[i].  The closest hit's distance is the minimum of ray_dist over
 // the accepted primitives, and every primitive's accept decision and ray_dist are computed
 // per primitive, whatever the scan or traversal order, so "some accepted primitive has
 // ray_dist < max_dist" is the same statement as long as
-//   (a) each primitive is tested by the code k_trace tests it with (isect_quad<true>,
+//   (a) each primitive is tested by the code closest_hit tests it with (isect_quad<true>,
 //       tri_test<false> with its own-box check, isect_sphere, the IEEE safe_inv), and
 //   (b) culling is conservative (the node boxes' nesting, and t_hi below).
 // A lane therefore stops at the first such primitive, a node step has no sorting network,
@@ -17,10 +17,11 @@
 // reference accept whatever it scans next, so its answer depends on the scan order.  A
 // ray with a NaN or infinite component, and a ray for which a quad or sphere yields a NaN
 // distance (a quad with a NaN normal, an overflowing sphere discriminant), is answered by
-// the closest-hit code itself (sample_hit) in its lane: the definition, verbatim.  A
+// the closest-hit code itself (closest_hit) in its lane: the definition, verbatim.  A
 // triangle never yields a NaN distance for a finite ray (its accepted t is finite, so
 // o + t d - o is finite or infinite).
-#include "wgt_device.h"
+#include "wgt_hit.h"
+#include "wgt_trav.h"
 
 namespace wgt {
 
@@ -110,8 +111,7 @@ __device__ __forceinline__ bool occ_start(const DevScene& sc, const float* __res
   }
   if (fallback) {
     Hit h;
-    TravStats st{};
-    sample_hit<TRIS, false, true>(sc, o, d, lds, h, st);
+    closest_hit<TRIS, true>(sc, o, d, lds, h);
     out[i] = (h.prim != kNoHit && h.dist < m) ? 1 : 0;
     return false;
   }
@@ -140,7 +140,7 @@ __device__ __forceinline__ int occ_step(const DevScene& sc, f3 o, f3 d, float li
   if (t.lf < t.le) {
     float tt;
     uint32_t idx;
-    // accepted exactly as k_trace accepts it (bi = kNoHit: t <= bt = t_hi), then the exact decision
+    // accepted exactly as trav_step accepts it (bi = kNoHit: t <= bt = t_hi), then the exact decision
     if (tri_test<false>(sc.tris, t.lf, o, d, t.ot, t.inv, t.bt, kNoHit, tt, idx)) {
       if (distance(o + tt * d, o) < lim) return 1;
     }
@@ -162,20 +162,10 @@ __device__ __forceinline__ int occ_step(const DevScene& sc, f3 o, f3 d, float li
     next = h0 ? r0 : (h1 ? r1 : (h2 ? r2 : r3));
     pop = !(p3 || h3);
   }
-  if (pop) {
-    if (t.sp == 0) return 2;
-    --t.sp;
-    next = lds[t.sp * kBlock];
-  }
-  const bool leaf = next < 0;
-  const uint32_t lfirst = leaf_first(next) * kTriRecordBytes;
-  t.lf = leaf ? lfirst : t.lf;
-  t.le = leaf ? lfirst + leaf_count(next) * kTriRecordBytes : t.le;
-  t.ref = leaf ? t.ref : next;
-  return 0;
+  return trav_next(t, lds, pop, next) ? 2 : 0;
 }
 
-// Launch lane i runs ray i (the flat form, as k_trace): each answer depends on its ray alone.
+// Launch lane i runs ray i (the flat form, as k_trace_hits): each answer depends on its ray alone.
 // A persistent form (a resident grid whose lanes refill from a launch-wide ray queue by ballot /
 // mbcnt, as k_render_ps refills pixels) was built and measured against this one and removed: it
 // was 1.4 to 5 times slower on every workload at every setting tried.
@@ -205,8 +195,8 @@ hipError_t launch_occluded(const DevScene& sc, const float* d_rays, const float*
                            uint8_t* d_out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-  if (sc.n_tris > 0) k_occluded<true><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, d_max_dist, n, d_out);
-  else k_occluded<false><<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, d_max_dist, n, d_out);
+  (sc.n_tris > 0 ? k_occluded<true> : k_occluded<false>)
+      <<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, d_rays, d_max_dist, n, d_out);
   return hipGetLastError();
 }
 

@@ -297,9 +297,6 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, ucha
 
 // The queries' launches on stream s; the asynchronous entry points are these behind their checks,
 // the synchronous ones stage their inputs, call the same, fetch and synchronise.
-int trace_launch(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t* d_prim, float* d_dist, hipStream_t s) {
-  return launch_on(ctx, s, "launch_trace", [&] { return launch_trace(ctx->sc, d_rays, n, d_prim, d_dist, s); });
-}
 int occluded_launch(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n, uint8_t* d_out,
                     hipStream_t s) {
   return launch_on(ctx, s, "launch_occluded", [&] { return launch_occluded(ctx->sc, d_rays, d_max_dist, n, d_out, s); });
@@ -852,7 +849,9 @@ int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint3
 int wgt_trace_rays_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t* d_prim_id,
                          float* d_dist, void* stream) {
   WGT_BEGIN(query_begin(ctx, n, null_buffer(!d_rays || !d_prim_id || !d_dist)));
-  return trace_launch(ctx, d_rays, n, d_prim_id, d_dist, stream_or_own(ctx, stream));
+  // the closest-hit query is the hit-record one with two fields
+  const wgt_hit_buffers dev{d_prim_id, d_dist, nullptr, nullptr, nullptr, nullptr};
+  return hits_launch(ctx, d_rays, n, dev, stream_or_own(ctx, stream));
 }
 
 int wgt_trace_rays(wgt_ctx* ctx, const float* rays, uint32_t n, uint32_t* prim_id, float* dist) {
@@ -864,7 +863,7 @@ int wgt_trace_rays(wgt_ctx* ctx, const float* rays, uint32_t n, uint32_t* prim_i
   int rc;
   if ((rc = stage_hits(ctx, out, n, dev))) return rc;
   if ((rc = stage(ctx, wgt_ctx::kRays, rays, (size_t)n * 24, d_rays))) return rc;
-  if ((rc = trace_launch(ctx, d_rays, n, dev.prim, dev.dist, ctx->stream))) return rc;
+  if ((rc = hits_launch(ctx, d_rays, n, dev, ctx->stream))) return rc;
   if ((rc = fetch_hits(ctx, out, dev, n))) return rc;
   return sync_stream(ctx);
 }
