@@ -21,6 +21,7 @@
  *   (none: sample_hit's dist < a limit)               wgt_occluded_rays (any-hit query)
  *   HitInfo after sample_hit path_tracer.wgsl:27-36   wgt_trace_hits (the whole hit record)
  *   (none: HitInfo of a pixel's first camera ray)     wgt_render_gbuffer (first-hit G-buffer)
+ *   (none: history reprojected frame to frame)        wgt_temporal_accumulate (temporal accumulation)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -419,6 +420,68 @@ int wgt_denoise(wgt_ctx *ctx, const wgt_denoise_params *params, uint32_t W, uint
 int wgt_denoise_async(wgt_ctx *ctx, const wgt_denoise_params *params, uint32_t W, uint32_t H,
                       const float *d_rgba32f_in, const wgt_hit_buffers *d_guides, void *d_workspace,
                       size_t workspace_bytes, float *d_rgba32f_out, void *d_rgba8_out, void *stream);
+
+/* ---- temporal accumulation (no reference counterpart) ---------------------- */
+/* Carries radiance from one frame to the next by reprojection, the first half of SVGF-style
+ * denoising and the natural input of wgt_denoise: each pixel of the current frame projects its
+ * first-hit position with both cameras, gathers the previous frame's accumulated radiance around
+ * where it lay there (bilinear, four taps, a tap accepted by its normal, its distance to the pixel's
+ * plane and optionally its primitive), and blends the current colour in with weight 1 / history
+ * length (DESIGN.md §4.8 states the arithmetic operation by operation; tests/temporal_restatement.py
+ * is the same in numpy, and the result equals it bit for bit).  The library keeps no state: the
+ * caller owns the history and alternates two wgt_temporal_state sets and two G-buffers.  A pixel
+ * accumulates when it hit a primitive that is not emissive and its guides and colour are finite and
+ * within 2^100; every other pixel (lights, misses, NaN) passes through bit for bit with len = 0 and
+ * moments = 0, and is never a tap.  Known limit: there are no per-primitive motion vectors, so a
+ * moved triangle fails the plane test and restarts its history, while a triangle sliding in its own
+ * plane keeps a history that is not its own. */
+#define WGT_TEMPORAL_MATCH_PRIM 1u
+typedef struct {
+  uint32_t max_history; /* 1..65536 (default 32): the history length is capped here; 1 = no accumulation */
+  float normal_min;     /* finite, -1..1 (default 0.9): a history tap needs dot(n, n_tap) >= this */
+  float plane_tol;      /* finite, >= 0 (default 1.0): ... and |dot(n, pos_tap - pos)| <= this, scene units */
+  uint32_t flags;       /* WGT_TEMPORAL_MATCH_PRIM (default off): ... and the same primitive id */
+} wgt_temporal_params;  /* 16 bytes */
+
+typedef struct {
+  float *rgba32f;  /* W x H x 4: the accumulated radiance (alpha: the current frame's) */
+  float *len;      /* W x H: history length, 0 for a pixel that is not accumulated */
+  float *moments;  /* 2 planes of W x H, may be NULL: running mean of luminance and of luminance^2 */
+} wgt_temporal_state; /* 24 bytes */
+
+int wgt_temporal_defaults(wgt_temporal_params *out);
+/* rgba32f_in and guides: the current frame's radiance and planar G-buffer records, as for
+ * wgt_denoise (prim, pos, norm and flags are required; dist and col are ignored); cam: the camera
+ * they were rendered with.  prev, guides_prev, cam_prev: the previous call's `out`, and the previous
+ * frame's G-buffer and camera; all three NULL is the first frame, in which every accumulated pixel
+ * starts a history of length 1.  spp and seed of both cameras are ignored.  out: the new state;
+ * moments must be NULL or not in prev and out alike.  rgba8_out (may be NULL): the renderer's
+ * rgba8unorm store of out's rgb, alpha 255.  params NULL = the defaults.  No scene is needed.
+ * out->rgba32f may equal rgba32f_in (a pixel reads only its own current colour), but out->rgba32f,
+ * out->len and out->moments must not overlap the prev buffer of the same name: the gather reads the
+ * previous frame's neighbours.  rgba32f buffers are 16-byte aligned.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context; NULL
+ * input, camera, guides, out, out->rgba32f or out->len; a NULL required guide; prev, guides_prev and
+ * cam_prev not all NULL or all set, then a NULL prev->rgba32f, prev->len or required previous guide,
+ * and moments in only one of prev and out; W or H 0 or above 32768, or W * H above 2^25; parameters
+ * out of range (NaN is refused); a camera that a render would refuse for reasons other than its spp;
+ * an out buffer overlapping its prev buffer.  A degenerate camera (origin equal to target, or looking
+ * along the up axis) is no error: no pixel finds history.
+ * Synchronous, HOST pointers; stages through one device allocation of its own and frees it. */
+int wgt_temporal_accumulate(wgt_ctx *ctx, const wgt_temporal_params *params, uint32_t W, uint32_t H,
+                            const wgt_camera_param *cam, const wgt_camera_param *cam_prev,
+                            const float *rgba32f_in, const wgt_hit_buffers *guides,
+                            const wgt_temporal_state *prev, const wgt_hit_buffers *guides_prev,
+                            const wgt_temporal_state *out, uint8_t *rgba8_out);
+/* DEVICE pointers inside host structs (the cameras are host structs), ordered on `stream` (NULL = the
+ * context's), returns once queued.  The inputs and the previous state are never written.  One pass,
+ * no workspace: calls that alternate two state sets on one stream need no synchronisation between
+ * them, and independent sequences on two streams may overlap. */
+int wgt_temporal_accumulate_async(wgt_ctx *ctx, const wgt_temporal_params *params, uint32_t W, uint32_t H,
+                                  const wgt_camera_param *cam, const wgt_camera_param *cam_prev,
+                                  const float *d_rgba32f_in, const wgt_hit_buffers *d_guides,
+                                  const wgt_temporal_state *d_prev, const wgt_hit_buffers *d_guides_prev,
+                                  const wgt_temporal_state *d_out, void *d_rgba8_out, void *stream);
 
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,

@@ -47,6 +47,20 @@ class WgtDenoiseParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+WGT_TEMPORAL_MATCH_PRIM = 1  # wgt_temporal_params.flags
+
+
+class WgtTemporalParams(ctypes.Structure):
+    """wgt_temporal_params (16 bytes); wgt_temporal_defaults fills the defaults."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("normal_min", ctypes.c_float), ("plane_tol", ctypes.c_float),
+                ("flags", ctypes.c_uint32)]
+
+
+class WgtTemporalState(ctypes.Structure):
+    """wgt_temporal_state (24 bytes): the history the caller owns (None / 0 = NULL)."""
+    _fields_ = [("rgba32f", ctypes.c_void_p), ("len", ctypes.c_void_p), ("moments", ctypes.c_void_p)]
+
+
 class WgtStats(ctypes.Structure):
     _fields_ = [("queries", ctypes.c_uint64), ("traced_rays", ctypes.c_uint64), ("samples", ctypes.c_uint64),
                 ("nan_rays", ctypes.c_uint64), ("node_visits", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64),
@@ -95,6 +109,7 @@ EXPORTS = [
     "wgt_update_triangles", "wgt_update_timing", "wgt_bvh_read", "wgt_bvh_refit",
     "wgt_update_triangles_device", "wgt_update_vertices_device",
     "wgt_denoise_defaults", "wgt_denoise_workspace_bytes", "wgt_denoise", "wgt_denoise_async",
+    "wgt_temporal_defaults", "wgt_temporal_accumulate", "wgt_temporal_accumulate_async",
 ]
 
 _lib = None
@@ -168,6 +183,13 @@ def lib():
         "wgt_denoise": (I, [P, ctypes.POINTER(WgtDenoiseParams), U32, U32, P, ctypes.POINTER(WgtHitBuffers), P, P]),
         "wgt_denoise_async": (I, [P, ctypes.POINTER(WgtDenoiseParams), U32, U32, P, ctypes.POINTER(WgtHitBuffers), P,
                                   ctypes.c_size_t, P, P, P]),
+        "wgt_temporal_defaults": (I, [ctypes.POINTER(WgtTemporalParams)]),
+        "wgt_temporal_accumulate": (I, [P, ctypes.POINTER(WgtTemporalParams), U32, U32, P, P, P,
+                                        ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState),
+                                        ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState), P]),
+        "wgt_temporal_accumulate_async": (I, [P, ctypes.POINTER(WgtTemporalParams), U32, U32, P, P, P,
+                                              ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState),
+                                              ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState), P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

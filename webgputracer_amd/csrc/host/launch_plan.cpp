@@ -408,4 +408,105 @@ DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t 
   return p;
 }
 
+wgt_temporal_params temporal_defaults() { return wgt_temporal_params{32u, 0.9f, 1.0f, 0u}; }
+
+// [a, a + na) and [b, b + nb) share a byte (no pointer arithmetic: the addresses as integers)
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x >= y ? x - y < nb : y - x < na;
+}
+
+static const char* null_temporal_guide(const wgt_hit_buffers& g, bool prev) {
+  if (!g.prim) return prev ? "null guides_prev.prim" : "null guides.prim";
+  if (!g.pos) return prev ? "null guides_prev.pos" : "null guides.pos";
+  if (!g.norm) return prev ? "null guides_prev.norm" : "null guides.norm";
+  if (!g.flags) return prev ? "null guides_prev.flags" : "null guides.flags";
+  return nullptr;
+}
+
+std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
+                                const wgt_camera_param* cam_prev, const void* in, const wgt_hit_buffers* guides,
+                                const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                const wgt_temporal_state* out) {
+  if (!in) return "null input image";
+  if (!cam) return "null camera";
+  if (!guides) return "null guides";
+  if (!out) return "null out";
+  if (!out->rgba32f) return "null out.rgba32f";
+  if (!out->len) return "null out.len";
+  if (const char* bad = null_temporal_guide(*guides, false)) return bad;
+  const bool first = !prev && !guides_prev && !cam_prev;
+  if (!first) {
+    if (!prev || !guides_prev || !cam_prev)
+      return "first-frame arguments: prev, guides_prev and cam_prev must be all null (the first frame) or all set";
+    if (!prev->rgba32f) return "null prev.rgba32f";
+    if (!prev->len) return "null prev.len";
+    if (const char* bad = null_temporal_guide(*guides_prev, true)) return bad;
+    if (!prev->moments != !out->moments) return "moments must be null or set in prev and out alike";
+  }
+  if (!denoise_size_ok(W, H))
+    return "image size " + std::to_string(W) + " x " + std::to_string(H) + ": W and H must be 1.." +
+           std::to_string(kDenoiseMaxDim) + " and W * H at most " + std::to_string(kDenoiseMaxPixels);
+  if (params) {
+    if (params->max_history < 1 || params->max_history > kTemporalMaxHistory)
+      return "params.max_history " + std::to_string(params->max_history) + " is not in 1.." +
+             std::to_string(kTemporalMaxHistory);
+    if (!(params->normal_min >= -1.0f && params->normal_min <= 1.0f)) return "params.normal_min must be finite and in -1..1";
+    if (!(params->plane_tol >= 0.0f) || !std::isfinite(params->plane_tol)) return "params.plane_tol must be finite and >= 0";
+    if (params->flags & ~WGT_TEMPORAL_MATCH_PRIM) return "params.flags has bits other than WGT_TEMPORAL_MATCH_PRIM";
+  }
+  // what a render of this camera would be refused for, its spp apart (the pass ignores spp and seed)
+  const wgt_camera_param* cams[2] = {cam, first ? nullptr : cam_prev};
+  for (int k = 0; k < 2; ++k) {
+    if (!cams[k]) continue;
+    wgt_camera_param c = *cams[k];
+    c.spp = 1u;
+    // a degenerate camera (origin equal to target, or looking along the up axis: make_frame's terms
+    // are NaN, which a render refuses as out-of-range directions) is no error here: no pixel finds history
+    const bool degenerate = c.aspect == c.aspect && c.fovy == c.fovy && finite_within(c.origin, 3, kCoordLimit) &&
+                            finite_within(c.target, 3, kCoordLimit) && c.origin[0] == c.target[0] &&
+                            c.origin[2] == c.target[2];
+    const std::string bad = degenerate ? "" : check_frame_args(c, W, H, 1u, 1u);
+    if (!bad.empty()) return std::string(k ? "cam_prev: " : "cam: ") + bad;
+  }
+  if (!first) {
+    const size_t n = (size_t)W * H;
+    if (ranges_overlap(out->rgba32f, n * 16, prev->rgba32f, n * 16)) return "overlap: out.rgba32f and prev.rgba32f";
+    if (ranges_overlap(out->len, n * 4, prev->len, n * 4)) return "overlap: out.len and prev.len";
+    if (out->moments && ranges_overlap(out->moments, n * 8, prev->moments, n * 8))
+      return "overlap: out.moments and prev.moments";
+  }
+  return "";
+}
+
+TemporalCam temporal_camera(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
+  const DevFrame fr = make_frame(cam, W, H);
+  const f3 o{fr.ox, fr.oy, fr.oz}, du{fr.dux, fr.duy, fr.duz}, dv{fr.dvx, fr.dvy, fr.dvz};
+  const f3 c = f3{fr.pox, fr.poy, fr.poz} - o;
+  const f3 nrm = cross(du, dv);
+  const f3 iu = du / dot(du, du), iv = dv / dot(dv, dv);
+  TemporalCam t{};
+  t.o[0] = o.x; t.o[1] = o.y; t.o[2] = o.z;
+  t.c[0] = c.x; t.c[1] = c.y; t.c[2] = c.z;
+  t.nrm[0] = nrm.x; t.nrm[1] = nrm.y; t.nrm[2] = nrm.z;
+  t.iu[0] = iu.x; t.iu[1] = iu.y; t.iu[2] = iu.z;
+  t.iv[0] = iv.x; t.iv[1] = iv.y; t.iv[2] = iv.z;
+  t.k = dot(c, nrm);
+  return t;
+}
+
+TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
+                           const wgt_camera_param* cam_prev) {
+  TemporalPlan p{};
+  p.W = W; p.H = H;
+  p.first = cam_prev ? 0u : 1u;
+  p.match_prim = params.flags & WGT_TEMPORAL_MATCH_PRIM;
+  p.max_history = (float)params.max_history;
+  p.normal_min = params.normal_min;
+  p.plane_tol = params.plane_tol;
+  p.cam = temporal_camera(cam, W, H);
+  if (cam_prev) p.cam_prev = temporal_camera(*cam_prev, W, H);
+  return p;
+}
+
 }  // namespace wgt

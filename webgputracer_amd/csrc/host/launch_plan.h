@@ -9,6 +9,7 @@
 
 #include "../wgt_denoise.h"
 #include "../wgt_internal.h"
+#include "../wgt_temporal.h"
 #include "bvh.h"
 
 namespace wgt {
@@ -123,5 +124,24 @@ std::string check_denoise_workspace(const void* ws, size_t ws_bytes, uint32_t W,
 // Of arguments that passed the checks: the workspace layout, each pass's kz in the fp32 operations of
 // the specification, and the largest step that runs LDS-tiled (WGT_DENOISE_TILED_STEP, at most 16).
 DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t H);
+
+// Temporal accumulation (wgt_temporal_accumulate, wgt_temporal_accumulate_async).
+// Its defaults, and the calls' checks after the context, in their order, each returning the
+// refusal's text, empty when fine: null input, camera, guides, out, out->rgba32f, out->len; a null
+// required guide; the first-frame triple (prev, guides_prev, cam_prev all null or all set), then
+// prev's and guides_prev's required fields and moments in prev and out alike; the size (the
+// denoiser's limits); the parameters (null: the defaults); the cameras (check_frame_args with spp 1);
+// an out buffer overlapping the prev buffer of the same name.  No pointer is dereferenced but the
+// structs' own.
+wgt_temporal_params temporal_defaults();
+std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
+                                const wgt_camera_param* cam_prev, const void* in, const wgt_hit_buffers* guides,
+                                const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                const wgt_temporal_state* out);
+// Of arguments that passed the checks (cam_prev null: the first-frame form): each camera's
+// projection constants in the fp32 operations of the specification, from make_frame.
+TemporalCam temporal_camera(const wgt_camera_param& cam, uint32_t W, uint32_t H);
+TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
+                           const wgt_camera_param* cam_prev);
 
 }  // namespace wgt

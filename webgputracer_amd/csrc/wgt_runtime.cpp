@@ -1003,6 +1003,83 @@ int wgt_denoise(wgt_ctx* ctx, const wgt_denoise_params* params, uint32_t W, uint
   return rc != WGT_OK ? rc : rs;
 }
 
+int wgt_temporal_defaults(wgt_temporal_params* out) {
+  if (!out) return fail(nullptr, WGT_E_INVALID, "null params");
+  *out = temporal_defaults();
+  return WGT_OK;
+}
+
+int wgt_temporal_accumulate_async(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                  const wgt_camera_param* cam, const wgt_camera_param* cam_prev,
+                                  const float* d_rgba32f_in, const wgt_hit_buffers* d_guides,
+                                  const wgt_temporal_state* d_prev, const wgt_hit_buffers* d_guides_prev,
+                                  const wgt_temporal_state* d_out, void* d_rgba8_out, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  const std::string bad = check_temporal_args(params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, d_prev, d_guides_prev, d_out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const TemporalPlan plan = plan_temporal(params ? *params : temporal_defaults(), W, H, *cam, cam_prev);
+  // no scene is read: the launch is ordered by the stream alone
+  WGT_HIP(ctx, launch_temporal(plan, (const float4*)d_rgba32f_in, *d_guides, d_prev, d_guides_prev, *d_out,
+                               (uchar4*)d_rgba8_out, stream_or_own(ctx, stream)));
+  return WGT_OK;
+}
+
+int wgt_temporal_accumulate(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                            const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const float* rgba32f_in,
+                            const wgt_hit_buffers* guides, const wgt_temporal_state* prev,
+                            const wgt_hit_buffers* guides_prev, const wgt_temporal_state* out, uint8_t* rgba8_out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  const std::string bad = check_temporal_args(params, W, H, cam, cam_prev, rgba32f_in, guides, prev, guides_prev, out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  // one allocation of the call's own, freed before it returns: the image (accumulated in place), the
+  // guides' planes (prim, pos, norm, flags), the previous state and guides, the new len and moments,
+  // the rgba8 output
+  const size_t n = (size_t)W * H;
+  const bool first = !prev, mom = out->moments != nullptr;
+  enum { kIn, kPrim, kPos, kNorm, kFlags, kPrevRgba, kPrevLen, kPrevMom, kPPrim, kPPos, kPNorm, kPFlags, kLen, kMom, kOut8, kParts };
+  const size_t part[kParts] = {n * 16, n * 4, n * 12, n * 12, n, first ? 0 : n * 16, first ? 0 : n * 4,
+                               first || !mom ? 0 : n * 8, first ? 0 : n * 4, first ? 0 : n * 12, first ? 0 : n * 12,
+                               first ? 0 : n, n * 4, mom ? n * 8 : 0, rgba8_out ? n * 4 : 0};
+  const void* src[kPPrim + 4] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->flags,
+                                 first ? nullptr : prev->rgba32f, first ? nullptr : prev->len,
+                                 first ? nullptr : prev->moments, first ? nullptr : guides_prev->prim,
+                                 first ? nullptr : guides_prev->pos, first ? nullptr : guides_prev->norm,
+                                 first ? nullptr : guides_prev->flags};
+  size_t off[kParts + 1] = {0};
+  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
+  struct Alloc {
+    char* p = nullptr;
+    ~Alloc() {
+      if (p) (void)hipFree(p);
+    }
+  } mem;
+  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
+  }
+  int rc = WGT_OK;
+  for (int k = 0; k <= kPFlags && rc == WGT_OK; ++k)
+    if (part[k] && hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+      rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a temporal accumulation input failed");
+  const auto at = [&](int k) { return part[k] ? mem.p + off[k] : nullptr; };
+  wgt_hit_buffers dg{}, dgp{};
+  dg.prim = (uint32_t*)at(kPrim); dg.pos = (float*)at(kPos); dg.norm = (float*)at(kNorm); dg.flags = (uint8_t*)at(kFlags);
+  dgp.prim = (uint32_t*)at(kPPrim); dgp.pos = (float*)at(kPPos); dgp.norm = (float*)at(kPNorm); dgp.flags = (uint8_t*)at(kPFlags);
+  const wgt_temporal_state dprev{(float*)at(kPrevRgba), (float*)at(kPrevLen), (float*)at(kPrevMom)};
+  const wgt_temporal_state dout{(float*)at(kIn), (float*)at(kLen), (float*)at(kMom)};
+  if (rc == WGT_OK)
+    rc = wgt_temporal_accumulate_async(ctx, params, W, H, cam, cam_prev, (const float*)at(kIn), &dg, first ? nullptr : &dprev,
+                                       first ? nullptr : &dgp, &dout, at(kOut8), ctx->stream);
+  if (rc == WGT_OK) rc = fetch(ctx, out->rgba32f, at(kIn), n * 16);
+  if (rc == WGT_OK) rc = fetch(ctx, out->len, at(kLen), n * 4);
+  if (rc == WGT_OK && mom) rc = fetch(ctx, out->moments, at(kMom), n * 8);
+  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, at(kOut8), n * 4);
+  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
+  return rc != WGT_OK ? rc : rs;
+}
+
 int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8]) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
   if (!counts) return fail(ctx, WGT_E_INVALID, "null counts");

@@ -23,6 +23,10 @@ single-frame render.
 (Context.render_gbuffer with the frame's camera and seed), the guides a denoiser asks for.
 `--denoise` also writes NNN_denoised.png: the frame through wgt_denoise (an edge-avoiding a-trous
 filter guided by that G-buffer), computed on the device on the batch's stream.
+`--accumulate` also writes NNN_accum.png: the frames accumulated over time in frame order
+(wgt_temporal_accumulate: each frame's history reprojected through its G-buffer, capped at
+`--max-history` frames), and with `--denoise` NNN_accum_denoised.png; one process only, because the
+ranks of a distributed run see no consecutive frames.
 
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -88,7 +92,8 @@ class FrameRenderer:
         return {"prim": g["prim"], "depth": g["dist"], "pos": g["pos"], "normal": g["norm"], "albedo": g["col"],
                 "flags": g["flags"]}
 
-    def stream(self, frame_batches, depth: int = 2, denoised=None):
+    def stream(self, frame_batches, depth: int = 2, denoised=None, accumulated=None, max_history=None,
+               accumulated_denoised=None):
         """Yield (batch, {frame: (H, W, 4) uint8}) for each batch of `frame_batches`, in
         order.  Batch k renders on pipeline stream k % depth into buffer set k % depth;
         it is issued before batch k-1 is handed out, so the device always has the next
@@ -100,7 +105,18 @@ class FrameRenderer:
         the frame through wgt_denoise with the default parameters.  The batch's launch then also
         fills a device rgba32f buffer, and each of its frames gets, on the batch's stream, its
         G-buffer (render_gbuffer_async with the frame's one tile) and denoise_async to a device
-        rgba8 buffer; nothing leaves the device but the two rgba8 images."""
+        rgba8 buffer; nothing leaves the device but the two rgba8 images.
+
+        accumulated: a dict that receives {frame: (H, W, 4) uint8}, the frames accumulated over time in
+        the order they are rendered (wgt_temporal_accumulate with `max_history`, the camera being
+        static), each after its G-buffer on its batch's stream.  The history is one sequence: two
+        state sets and two G-buffer sets that alternate frame by frame across batches and pipeline
+        slots, and each slot's rgba8 outputs.  Frame k is accumulated after frame k - 1 also when
+        the two belong to batches on different pipeline streams: a batch's stream waits, after its
+        render launch and before its first G-buffer, for an event recorded behind the previous
+        batch's last accumulation, so the renders still overlap and only the short accumulation
+        passes are serialised.  accumulated_denoised: a dict that also receives the accumulated
+        radiance through denoise_async."""
         import torch
 
         from ._lib import TILE_DTYPE
@@ -113,21 +129,41 @@ class FrameRenderer:
             return
         streams = [torch.cuda.ExternalStream(self.ctx.pipeline_stream(i), device=dev) for i in range(depth)]
         d_out = [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
-        d_dn = None
-        if denoised is not None:
-            n, ws_bytes = W * H, denoise_workspace_bytes(W, H)
+        d_dn = d_acc = d_accdn = None
+        acc = accumulated is not None
+        dn_acc = acc and accumulated_denoised is not None
+        n = W * H
+
+        def u8_set():
+            return [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
+
+        if denoised is not None or acc:
             d_f32 = [torch.empty((nmax, H, W, 4), dtype=torch.float32, device=dev) for _ in range(depth)]
-            d_dn = [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
-            # per set: one frame's guides (reused frame after frame in stream order) and the workspace
-            d_vec = [torch.empty((3, 3, n), dtype=torch.float32, device=dev) for _ in range(depth)]
-            d_prim = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(depth)]
-            d_flags = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(depth)]
+            # per set: one frame's guides (reused frame after frame in stream order).  Accumulating, the
+            # sets are two for the whole sequence instead: a frame's guides are the next frame's history
+            sets = 2 if acc else depth
+            d_vec = [torch.empty((3, 3, n), dtype=torch.float32, device=dev) for _ in range(sets)]
+            d_prim = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(sets)]
+            d_flags = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(sets)]
+        if denoised is not None or dn_acc:
+            ws_bytes = denoise_workspace_bytes(W, H)
             d_ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        if denoised is not None:
+            d_dn = u8_set()
+        if acc:
+            d_acc = u8_set()
+            d_accdn = u8_set() if dn_acc else None
+            d_state = [{"f32": torch.empty((H, W, 4), dtype=torch.float32, device=dev),
+                        "len": torch.empty(n, dtype=torch.float32, device=dev),
+                        "moments": torch.empty((2, n), dtype=torch.float32, device=dev)} for _ in range(2)]
+            history = 0       # frames accumulated so far
+            last_acc = None   # recorded behind the previous batch's last accumulation
+        copies = [(d_dn, denoised), (d_acc, accumulated), (d_accdn, accumulated_denoised)]
         pending = []
         for k, b in enumerate(frame_batches):
             j = k % depth
             if len(pending) == depth:  # the oldest batch in flight holds set j: hand it out first
-                yield self._finish(pending.pop(0), streams, d_out, d_dn, denoised)
+                yield self._finish(pending.pop(0), streams, d_out, copies)
             s = streams[j]
             t = np.zeros(len(b), TILE_DTYPE)  # one full-frame tile per frame (wgt_render_frames' list)
             t["seed"] = np.asarray(b, np.uint32)
@@ -136,31 +172,54 @@ class FrameRenderer:
                 d_tiles = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
                 self.ctx.render_tiles_async(self.cam, W, H, W, H, d_tiles.data_ptr(), len(b),
                                             d_u8=d_out[j].data_ptr(),
-                                            d_f32=d_f32[j].data_ptr() if d_dn else 0, stream=s.cuda_stream)
-                for i in range(len(b) if d_dn else 0):
-                    guides = {"prim": d_prim[j].data_ptr(), "pos": d_vec[j][0].data_ptr(),
-                              "norm": d_vec[j][1].data_ptr(), "col": d_vec[j][2].data_ptr(),
-                              "flags": d_flags[j].data_ptr()}
+                                            d_f32=d_f32[j].data_ptr() if d_dn or acc else 0, stream=s.cuda_stream)
+                if acc and last_acc is not None:
+                    s.wait_event(last_acc)  # frame order across the pipeline streams
+                for i in range(len(b) if d_dn or acc else 0):
+                    q = history % 2 if acc else j
+                    guides = {"prim": d_prim[q].data_ptr(), "pos": d_vec[q][0].data_ptr(),
+                              "norm": d_vec[q][1].data_ptr(), "col": d_vec[q][2].data_ptr(),
+                              "flags": d_flags[q].data_ptr()}
                     self.ctx.render_gbuffer_async(self.cam, W, H, W, H, d_tiles.data_ptr() + i * TILE_DTYPE.itemsize, 1,
                                                   stream=s.cuda_stream, **guides)
-                    self.ctx.denoise_async(W, H, d_f32[j][i].data_ptr(), d_ws[j].data_ptr(), ws_bytes,
-                                           d_u8_out=d_dn[j][i].data_ptr(), stream=s.cuda_stream, **guides)
+                    if d_dn:
+                        self.ctx.denoise_async(W, H, d_f32[j][i].data_ptr(), d_ws[j].data_ptr(), ws_bytes,
+                                               d_u8_out=d_dn[j][i].data_ptr(), stream=s.cuda_stream, **guides)
+                    if acc:
+                        p = 1 - q
+                        before = {"prim": d_prim[p].data_ptr(), "pos": d_vec[p][0].data_ptr(),
+                                  "norm": d_vec[p][1].data_ptr(), "flags": d_flags[p].data_ptr()}
+                        out = {key: t.data_ptr() for key, t in d_state[q].items()}
+                        prev = {key: t.data_ptr() for key, t in d_state[p].items()}
+                        self.ctx.temporal_accumulate_async(
+                            W, H, self.cam, d_f32[j][i].data_ptr(), guides, out, prev if history else None,
+                            before if history else None, self.cam if history else None,
+                            d_u8_out=d_acc[j][i].data_ptr(), max_history=max_history, stream=s.cuda_stream)
+                        if dn_acc:
+                            self.ctx.denoise_async(W, H, out["f32"], d_ws[j].data_ptr(), ws_bytes,
+                                                   d_u8_out=d_accdn[j][i].data_ptr(), stream=s.cuda_stream, **guides)
+                        history += 1
+                if acc:
+                    last_acc = torch.cuda.Event()
+                    last_acc.record(s)
                 d_tiles.record_stream(s)
             pending.append((k, b))
         while pending:
-            yield self._finish(pending.pop(0), streams, d_out, d_dn, denoised)
+            yield self._finish(pending.pop(0), streams, d_out, copies)
 
     @staticmethod
-    def _finish(kb, streams, d_out, d_dn=None, denoised=None):
+    def _finish(kb, streams, d_out, copies=()):
+        """Batch k's images on the host; copies: (per-slot device rgba8 buffers, the dict they go to)."""
         import torch
 
         k, b = kb
         j = k % len(streams)
         with torch.cuda.stream(streams[j]):  # ordered after batch k's launch on its stream
             imgs = d_out[j][:len(b)].cpu().numpy()
-            if d_dn is not None:
-                dn = d_dn[j][:len(b)].cpu().numpy()
-                denoised.update({f: dn[i] for i, f in enumerate(b)})
+            for d_buf, into in copies:
+                if d_buf is not None:
+                    host = d_buf[j][:len(b)].cpu().numpy()
+                    into.update({f: host[i] for i, f in enumerate(b)})
         return b, {f: imgs[i] for i, f in enumerate(b)}
 
 
@@ -184,11 +243,23 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true",
                     help="also write NNN_denoised.png next to each NNN.png: the frame through the edge-avoiding "
                          "a-trous filter (wgt_denoise, default parameters), guided by its G-buffer on the device")
+    ap.add_argument("--accumulate", action="store_true",
+                    help="also write NNN_accum.png: the frames accumulated over time in frame order by reprojecting "
+                         "the history (wgt_temporal_accumulate) on the device; with --denoise also "
+                         "NNN_accum_denoised.png, the accumulated radiance through the filter")
+    ap.add_argument("--max-history", type=int, default=32, help="--accumulate: the history length's cap (1..65536)")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
         ap.error("--gbuffer needs --out")
     if a.denoise and not a.out:
         ap.error("--denoise needs --out")
+    if a.accumulate and not a.out:
+        ap.error("--accumulate needs --out")
+    if a.accumulate and not 1 <= a.max_history <= 65536:
+        ap.error("--max-history must be 1..65536")
+    if a.accumulate and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--accumulate needs consecutive frames: frames are dealt round-robin to the ranks, so run it "
+                 "in one process (WORLD_SIZE = 1)")
     if a.frame[0] < 1 or a.frame[1] < a.frame[0]:
         ap.error("bad frame range")  # the C++ CLI's check (csrc/main.cpp)
     if not 1 <= a.pipeline <= 4:
@@ -222,13 +293,18 @@ def main(argv=None):
     pending = collections.deque()
     t0 = time.perf_counter()
     denoised = {} if a.denoise else None
-    for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised):
+    accumulated = {} if a.accumulate else None
+    accumulated_denoised = {} if a.accumulate and a.denoise else None
+    for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised, accumulated=accumulated,
+                             max_history=a.max_history, accumulated_denoised=accumulated_denoised):
         if a.out:
             for f in b:  # render.cpp:494-497
                 pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
-                if a.denoise:
-                    pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_denoised.png"),
-                                               denoised.pop(f)))
+                for suffix, extra in (("denoised", denoised), ("accum", accumulated),
+                                      ("accum_denoised", accumulated_denoised)):
+                    if extra is not None:
+                        pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_{suffix}.png"),
+                                                   extra.pop(f)))
                 if a.gbuffer:
                     np.savez(os.path.join(a.out, f"{f:03d}_gbuffer.npz"), **fr.gbuffer(f))
             while len(pending) > 4 * workers:

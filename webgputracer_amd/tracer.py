@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
-                   WgtHitBuffers, WgtSceneInfo, WgtStats, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
+                   WgtHitBuffers, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -135,11 +135,13 @@ def bvh_refit(built_from, now):
     return info.as_dict(), nodes, recs, cn, cr, step.value
 
 
-def camera_param(aspect: float, spp: int, seed: int, fovy: float = 40.0):
-    """Camera::Update (camera.cpp:64-70) with an explicit seed instead of RandSeed()."""
+def camera_param(aspect: float, spp: int, seed: int, fovy: float = 40.0, origin=(278.0, 278.0, -800.0),
+                 target=(278.0, 278.0, 0.0)):
+    """Camera::Update (camera.cpp:64-70) with an explicit seed instead of RandSeed(); origin and
+    target default to the reference's constants."""
     cam = np.zeros(1, CAMERA_DTYPE)
-    cam["origin"] = (278.0, 278.0, -800.0)
-    cam["target"] = (278.0, 278.0, 0.0)
+    cam["origin"] = origin
+    cam["target"] = target
     cam["aspect"] = np.float32(aspect)
     cam["fovy"] = np.float32(fovy)
     cam["spp"] = spp
@@ -174,6 +176,13 @@ def denoise_defaults():
 def denoise_workspace_bytes(W: int, H: int) -> int:
     """Bytes of device scratch Context.denoise_async needs for a W x H image (0: a size it refuses)."""
     return int(lib().wgt_denoise_workspace_bytes(W, H))
+
+
+def temporal_defaults():
+    """wgt_temporal_defaults: a WgtTemporalParams of the library's defaults."""
+    p = WgtTemporalParams()
+    check(lib().wgt_temporal_defaults(ctypes.byref(p)))
+    return p
 
 
 def device_count() -> int:
@@ -447,6 +456,112 @@ class Context:
                                               ctypes.byref(bufs), ctypes.c_void_p(d_workspace or None),
                                               workspace_bytes, ctypes.c_void_p(d_f32_out or None),
                                               ctypes.c_void_p(d_u8_out or None), ctypes.c_void_p(stream or None)))
+
+    @staticmethod
+    def _temporal_params(max_history, normal_min, plane_tol, match_prim):
+        """wgt_temporal_params: the library's defaults, with the arguments that are not None over them."""
+        p = temporal_defaults()
+        if max_history is not None:
+            p.max_history = max_history
+        if normal_min is not None:
+            p.normal_min = normal_min
+        if plane_tol is not None:
+            p.plane_tol = plane_tol
+        p.flags = _lib.WGT_TEMPORAL_MATCH_PRIM if match_prim else 0
+        return p
+
+    @staticmethod
+    def _temporal_guides(guides, H, W, what):
+        """The planar host arrays wgt_temporal_accumulate reads of a render_gbuffer dict, and their struct."""
+        missing = [k for k in ("prim", "pos", "norm", "flags") if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"temporal_accumulate: {what} lack {missing}")
+        planar = {k: np.ascontiguousarray(np.moveaxis(np.asarray(guides[k], np.float32).reshape(H, W, 3), -1, 0))
+                  for k in ("pos", "norm")}
+        planar["prim"] = np.ascontiguousarray(guides["prim"], np.uint32).reshape(H, W)
+        planar["flags"] = np.ascontiguousarray(guides["flags"], np.uint8).reshape(H, W)
+        return planar, WgtHitBuffers(**{k: a.ctypes.data for k, a in planar.items()})
+
+    def temporal_accumulate(self, color, guides, cam, prev=None, guides_prev=None, cam_prev=None, max_history=None,
+                            normal_min=None, plane_tol=None, match_prim=False, moments=True, want=("u8",)):
+        """Temporal accumulation by reprojection (wgt_temporal_accumulate) of `color`, the (H, W, 4) float32
+        radiance of render_tile, with `guides`, the dict render_gbuffer returns for the same pixels
+        (prim, pos, norm and flags are read), rendered with `cam`.  prev: the dict the previous frame's
+        call returned, guides_prev and cam_prev that frame's G-buffer and camera; all three None is the
+        first frame.  None for a parameter takes the library's default (max_history 32, normal_min 0.9,
+        plane_tol 1.0).  Returns {"f32": (H, W, 4) float32, "len": (H, W) float32, "moments": (2, H, W)
+        float32 or None (moments=False), "u8": (H, W, 4) uint8 or None ("u8" not in want)}.  Lights,
+        misses and non-finite pixels pass through unchanged with len 0."""
+        color = np.ascontiguousarray(color, np.float32)
+        if color.ndim != 3 or color.shape[2] != 4:
+            raise ValueError(f"temporal_accumulate: color must be (H, W, 4), got {color.shape}")
+        H, W = color.shape[:2]
+        keep, bufs = self._temporal_guides(guides, H, W, "guides")
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        out = {"f32": np.zeros((H, W, 4), np.float32), "len": np.zeros((H, W), np.float32),
+               "moments": np.zeros((2, H, W), np.float32) if moments else None,
+               "u8": np.zeros((H, W, 4), np.uint8) if "u8" in want else None}
+        st_out = WgtTemporalState(out["f32"].ctypes.data, out["len"].ctypes.data,
+                                  out["moments"].ctypes.data if moments else None)
+        p_prev = p_gprev = p_cam_prev = None
+        if prev is not None or guides_prev is not None or cam_prev is not None:
+            # an incomplete triple reaches the library, which refuses it
+            if prev is not None:
+                # moments=False: a previous state's moments are not carried on
+                pa = {k: np.ascontiguousarray(prev[k], np.float32)
+                      if prev.get(k) is not None and (moments or k != "moments") else None
+                      for k in ("f32", "len", "moments")}
+                for k, size in (("f32", 4 * H * W), ("len", H * W), ("moments", 2 * H * W)):
+                    if pa[k] is not None and pa[k].size != size:
+                        raise ValueError(f"temporal_accumulate: prev[{k!r}] has {pa[k].size} elements, not {size}")
+                st_prev = WgtTemporalState(*(pa[k].ctypes.data if pa[k] is not None else None
+                                             for k in ("f32", "len", "moments")))
+                p_prev = ctypes.byref(st_prev)
+            if guides_prev is not None:
+                keep_prev, bufs_prev = self._temporal_guides(guides_prev, H, W, "guides_prev")
+                p_gprev = ctypes.byref(bufs_prev)
+            if cam_prev is not None:
+                cam_prev = np.ascontiguousarray(cam_prev, CAMERA_DTYPE)
+                p_cam_prev = ptr(cam_prev)
+        p = self._temporal_params(max_history, normal_min, plane_tol, match_prim)
+        self._check(self._L.wgt_temporal_accumulate(self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev, ptr(color),
+                                                    ctypes.byref(bufs), p_prev, p_gprev, ctypes.byref(st_out),
+                                                    ptr(out["u8"])))
+        return out
+
+    def temporal_accumulate_async(self, W, H, cam, d_f32_in, guides, out, prev=None, guides_prev=None, cam_prev=None,
+                                  d_u8_out=0, max_history=None, normal_min=None, plane_tol=None, match_prim=False,
+                                  stream=0):
+        """Device-pointer launch (wgt_temporal_accumulate_async; raw device addresses, 0 = NULL): the W x H
+        rgba32f image at d_f32_in; guides and guides_prev: dicts of the G-buffer planes' addresses
+        (prim, pos, norm, flags) of render_gbuffer_async's single full-frame tile; out and prev: dicts
+        {"f32", "len", "moments"} of addresses, the caller's two state sets (moments 0 or absent in
+        both: not kept).  prev, guides_prev and cam_prev all None is the first frame.  out["f32"] may
+        equal d_f32_in.  Ordered on `stream` (0 = the context's)."""
+        def state(d):
+            return WgtTemporalState(*(d.get(k) or None for k in ("f32", "len", "moments")))
+
+        def hits(d):
+            return _device_hit_buffers(d.get("prim"), 0, d.get("pos"), d.get("norm"), 0, d.get("flags"))
+
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        bufs, st_out = hits(guides), state(out)
+        p_prev = p_gprev = p_cam_prev = None
+        if prev is not None:
+            st_prev = state(prev)
+            p_prev = ctypes.byref(st_prev)
+        if guides_prev is not None:
+            bufs_prev = hits(guides_prev)
+            p_gprev = ctypes.byref(bufs_prev)
+        if cam_prev is not None:
+            cam_prev = np.ascontiguousarray(cam_prev, CAMERA_DTYPE)
+            p_cam_prev = ptr(cam_prev)
+        p = self._temporal_params(max_history, normal_min, plane_tol, match_prim)
+        self._check(self._L.wgt_temporal_accumulate_async(self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev,
+                                                          ctypes.c_void_p(d_f32_in or None), ctypes.byref(bufs), p_prev,
+                                                          p_gprev, ctypes.byref(st_out),
+                                                          ctypes.c_void_p(d_u8_out or None),
+                                                          ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
