@@ -483,6 +483,53 @@ int wgt_temporal_accumulate_async(wgt_ctx *ctx, const wgt_temporal_params *param
                                   const wgt_temporal_state *d_prev, const wgt_hit_buffers *d_guides_prev,
                                   const wgt_temporal_state *d_out, void *d_rgba8_out, void *stream);
 
+/* ---- variance-guided denoising (no reference counterpart) ------------------ */
+/* The second half of SVGF-style denoising: wgt_denoise's a-trous filter with a luminance weight
+ * scaled by each pixel's own variance, over the state wgt_temporal_accumulate wrote.  The variance of
+ * a pixel comes from its moments (the per-frame variance m2 - m1^2, not divided by the history
+ * length), or under a history shorter than min_history from a 7 x 7 spatial estimate over the
+ * moments; it is filtered along with the colour, and a 3 x 3 Gaussian of it sets each pass's
+ * luminance tolerance: sigma_lum standard deviations (DESIGN.md §4.9 states the arithmetic operation
+ * by operation; tests/denoise_variance_restatement.py is the same in numpy, and the result equals it
+ * bit for bit).  A pixel is filtered when wgt_denoise would filter it and its len is >= 1 and its
+ * moments are within 2^100; every other pixel passes through bit for bit, is never a tap and has
+ * variance 0.  The moments are of raw luminance: the variance is demodulated by the luminance of the
+ * albedo, which is exact for a grey albedo and an approximation otherwise. */
+typedef struct {
+  uint32_t iterations;   /* 1..8 (default 5): pass i (from 0) taps at a step of 2^i pixels */
+  uint32_t normal_power; /* 0..10 (default 7): the normal weight max0(n.n') is squared this many times */
+  float sigma_pos;       /* finite, > 0 (default 1.0): scene units per pixel of step, along the normal */
+  uint32_t flags;        /* WGT_DENOISE_DEMODULATE (default): filter colour / albedo, multiply back after */
+  float sigma_lum;       /* finite, > 0 (default 4.0): luminance tolerance in standard deviations */
+  uint32_t min_history;  /* 1..64 (default 4): a shorter history takes the spatial variance estimate */
+} wgt_denoise_variance_params; /* 24 bytes */
+int wgt_denoise_variance_defaults(wgt_denoise_variance_params *out);
+/* Bytes of device scratch wgt_denoise_variance_async needs for a W x H image (a multiple of 256: 64
+ * per pixel); 0 for a size it refuses. */
+size_t wgt_denoise_variance_workspace_bytes(uint32_t W, uint32_t H);
+/* state: what wgt_temporal_accumulate wrote for these W x H pixels; rgba32f, len and moments are all
+ * required.  guides: as for wgt_denoise (prim, pos, norm, col and flags are required).  Outputs:
+ * rgba32f_out (alpha is the state's) and rgba8_out as wgt_denoise writes them, one of the two may be
+ * NULL; variance_out (may be NULL): W x H floats, the filtered variance of the demodulated luminance,
+ * 0 for a pixel that passes through.  params NULL = the defaults.  No scene is needed.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context; NULL state
+ * or guides; a NULL state->rgba32f, state->len or state->moments; a NULL required guide; both colour
+ * outputs NULL; W or H 0 or above 32768, or W * H above 2^25; parameters out of range (NaN is
+ * refused); (async) NULL workspace, one not 256-byte aligned, workspace_bytes below
+ * wgt_denoise_variance_workspace_bytes(W, H).
+ * Synchronous, HOST pointers; allocates and frees its own device workspace. */
+int wgt_denoise_variance(wgt_ctx *ctx, const wgt_denoise_variance_params *params, uint32_t W, uint32_t H,
+                         const wgt_temporal_state *state, const wgt_hit_buffers *guides, float *rgba32f_out,
+                         uint8_t *rgba8_out, float *variance_out);
+/* DEVICE pointers inside host structs, ordered on `stream` (NULL = the context's), returns once
+ * queued.  The state and the guides are never written.  d_rgba32f_out may equal d_state->rgba32f:
+ * the state is consumed into the workspace before anything is written.  The workspace is the
+ * caller's and holds nothing between calls: two calls on two streams with two workspaces may overlap. */
+int wgt_denoise_variance_async(wgt_ctx *ctx, const wgt_denoise_variance_params *params, uint32_t W, uint32_t H,
+                               const wgt_temporal_state *d_state, const wgt_hit_buffers *d_guides,
+                               void *d_workspace, size_t workspace_bytes, float *d_rgba32f_out, void *d_rgba8_out,
+                               float *d_variance_out, void *stream);
+
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,
  * sqrt_fast, div_rn) against correctly rounded results (the f64 operation rounded

@@ -47,6 +47,12 @@ class WgtDenoiseParams(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class WgtDenoiseVarianceParams(ctypes.Structure):
+    """wgt_denoise_variance_params (24 bytes); wgt_denoise_variance_defaults fills the defaults."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("normal_power", ctypes.c_uint32), ("sigma_pos", ctypes.c_float),
+                ("flags", ctypes.c_uint32), ("sigma_lum", ctypes.c_float), ("min_history", ctypes.c_uint32)]
+
+
 WGT_TEMPORAL_MATCH_PRIM = 1  # wgt_temporal_params.flags
 
 
@@ -110,6 +116,8 @@ EXPORTS = [
     "wgt_update_triangles_device", "wgt_update_vertices_device",
     "wgt_denoise_defaults", "wgt_denoise_workspace_bytes", "wgt_denoise", "wgt_denoise_async",
     "wgt_temporal_defaults", "wgt_temporal_accumulate", "wgt_temporal_accumulate_async",
+    "wgt_denoise_variance_defaults", "wgt_denoise_variance_workspace_bytes", "wgt_denoise_variance",
+    "wgt_denoise_variance_async",
 ]
 
 _lib = None
@@ -190,6 +198,13 @@ def lib():
         "wgt_temporal_accumulate_async": (I, [P, ctypes.POINTER(WgtTemporalParams), U32, U32, P, P, P,
                                               ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState),
                                               ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtTemporalState), P, P]),
+        "wgt_denoise_variance_defaults": (I, [ctypes.POINTER(WgtDenoiseVarianceParams)]),
+        "wgt_denoise_variance_workspace_bytes": (ctypes.c_size_t, [U32, U32]),
+        "wgt_denoise_variance": (I, [P, ctypes.POINTER(WgtDenoiseVarianceParams), U32, U32,
+                                     ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers), P, P, P]),
+        "wgt_denoise_variance_async": (I, [P, ctypes.POINTER(WgtDenoiseVarianceParams), U32, U32,
+                                           ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers), P,
+                                           ctypes.c_size_t, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

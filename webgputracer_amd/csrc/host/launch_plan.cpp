@@ -408,6 +408,72 @@ DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t 
   return p;
 }
 
+wgt_denoise_variance_params denoise_variance_defaults() {
+  return wgt_denoise_variance_params{5u, 7u, 1.0f, WGT_DENOISE_DEMODULATE, 4.0f, 4u};
+}
+
+size_t denoise_variance_workspace_bytes(uint32_t W, uint32_t H) { return denoise_workspace_bytes(W, H); }
+
+std::string check_denoise_variance_args(const wgt_denoise_variance_params* params, uint32_t W, uint32_t H,
+                                        const wgt_temporal_state* state, const wgt_hit_buffers* guides,
+                                        const void* out32, const void* out8) {
+  if (!state) return "null state";
+  if (!guides) return "null guides";
+  if (!state->rgba32f) return "null state.rgba32f";
+  if (!state->len) return "null state.len";
+  if (!state->moments) return "null state.moments";
+  if (!guides->prim) return "null guides.prim";
+  if (!guides->pos) return "null guides.pos";
+  if (!guides->norm) return "null guides.norm";
+  if (!guides->col) return "null guides.col";
+  if (!guides->flags) return "null guides.flags";
+  if (!out32 && !out8) return "null outputs: rgba32f_out and rgba8_out are both null";
+  if (!denoise_size_ok(W, H))
+    return "image size " + std::to_string(W) + " x " + std::to_string(H) + ": W and H must be 1.." +
+           std::to_string(kDenoiseMaxDim) + " and W * H at most " + std::to_string(kDenoiseMaxPixels);
+  if (params) {
+    if (params->iterations < 1 || params->iterations > kDenoiseMaxIterations)
+      return "params.iterations " + std::to_string(params->iterations) + " is not in 1.." +
+             std::to_string(kDenoiseMaxIterations);
+    if (params->normal_power > kDenoiseMaxNormalPower)
+      return "params.normal_power " + std::to_string(params->normal_power) + " is not in 0.." +
+             std::to_string(kDenoiseMaxNormalPower);
+    if (!(params->sigma_pos > 0.0f) || !std::isfinite(params->sigma_pos)) return "params.sigma_pos must be finite and > 0";
+    if (params->flags & ~WGT_DENOISE_DEMODULATE) return "params.flags has bits other than WGT_DENOISE_DEMODULATE";
+    if (!(params->sigma_lum > 0.0f) || !std::isfinite(params->sigma_lum)) return "params.sigma_lum must be finite and > 0";
+    if (params->min_history < 1 || params->min_history > kDenoiseVarianceMaxMinHistory)
+      return "params.min_history " + std::to_string(params->min_history) + " is not in 1.." +
+             std::to_string(kDenoiseVarianceMaxMinHistory);
+  }
+  return "";
+}
+
+std::string check_denoise_variance_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H) {
+  if (!ws) return "null workspace";
+  if (!aligned_to(ws, kDenoiseAlign)) return "misaligned workspace: it must be 256-byte aligned";
+  const size_t need = denoise_variance_workspace_bytes(W, H);
+  if (ws_bytes < need)
+    return "workspace_bytes " + std::to_string(ws_bytes) + " is below the " + std::to_string(need) +
+           " that wgt_denoise_variance_workspace_bytes asks for";
+  return "";
+}
+
+DenoiseVariancePlan plan_denoise_variance(const wgt_denoise_variance_params& params, uint32_t W, uint32_t H) {
+  // the layout, the kz and the switch are the plain filter's
+  const DenoisePlan d = plan_denoise(wgt_denoise_params{params.iterations, params.normal_power, params.sigma_pos, params.flags}, W, H);
+  DenoiseVariancePlan p{};
+  p.W = W; p.H = H;
+  p.iterations = d.iterations;
+  p.normal_power = d.normal_power;
+  p.demodulate = d.demodulate;
+  for (uint32_t i = 0; i < kDenoiseMaxIterations; ++i) p.kz[i] = d.kz[i];
+  p.sigma_lum = params.sigma_lum;
+  p.min_history = (float)params.min_history;
+  p.tiled_max_step = d.tiled_max_step;
+  p.off_rec = d.off_rec; p.off_it0 = d.off_it0; p.off_it1 = d.off_it1; p.bytes = d.bytes;
+  return p;
+}
+
 wgt_temporal_params temporal_defaults() { return wgt_temporal_params{32u, 0.9f, 1.0f, 0u}; }
 
 // [a, a + na) and [b, b + nb) share a byte (no pointer arithmetic: the addresses as integers)

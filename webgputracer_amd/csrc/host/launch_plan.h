@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../wgt_denoise.h"
+#include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
 #include "../wgt_temporal.h"
 #include "bvh.h"
@@ -124,6 +125,23 @@ std::string check_denoise_workspace(const void* ws, size_t ws_bytes, uint32_t W,
 // Of arguments that passed the checks: the workspace layout, each pass's kz in the fp32 operations of
 // the specification, and the largest step that runs LDS-tiled (WGT_DENOISE_TILED_STEP, at most 16).
 DenoisePlan plan_denoise(const wgt_denoise_params& params, uint32_t W, uint32_t H);
+
+// The variance-guided denoiser (wgt_denoise_variance, wgt_denoise_variance_async).  Its
+// defaults; its workspace (wgt_denoise's size and limits); and the calls' checks after the context, in
+// their order, each returning the refusal's text, empty when fine: null state or guides; a null
+// state->rgba32f, state->len or state->moments; a null required guide; both colour outputs null; the
+// size; the parameters (null: the defaults; NaN is refused); then of the async form the workspace:
+// null, alignment, size.  No pointer is dereferenced but the structs' own.
+wgt_denoise_variance_params denoise_variance_defaults();
+size_t denoise_variance_workspace_bytes(uint32_t W, uint32_t H);
+std::string check_denoise_variance_args(const wgt_denoise_variance_params* params, uint32_t W, uint32_t H,
+                                        const wgt_temporal_state* state, const wgt_hit_buffers* guides,
+                                        const void* out32, const void* out8);
+std::string check_denoise_variance_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H);
+// Of arguments that passed the checks: the workspace layout, each pass's kz (kz[0] = 1 / sigma_pos^2)
+// in the fp32 operations of the specification, min_history as a float, and the largest step that runs
+// LDS-tiled (WGT_DENOISE_TILED_STEP, at most 16).
+DenoiseVariancePlan plan_denoise_variance(const wgt_denoise_variance_params& params, uint32_t W, uint32_t H);
 
 // Temporal accumulation (wgt_temporal_accumulate, wgt_temporal_accumulate_async).
 // Its defaults, and the calls' checks after the context, in their order, each returning the

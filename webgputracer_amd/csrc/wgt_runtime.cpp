@@ -1080,6 +1080,76 @@ int wgt_temporal_accumulate(wgt_ctx* ctx, const wgt_temporal_params* params, uin
   return rc != WGT_OK ? rc : rs;
 }
 
+int wgt_denoise_variance_defaults(wgt_denoise_variance_params* out) {
+  if (!out) return fail(nullptr, WGT_E_INVALID, "null params");
+  *out = denoise_variance_defaults();
+  return WGT_OK;
+}
+
+size_t wgt_denoise_variance_workspace_bytes(uint32_t W, uint32_t H) { return denoise_variance_workspace_bytes(W, H); }
+
+int wgt_denoise_variance_async(wgt_ctx* ctx, const wgt_denoise_variance_params* params, uint32_t W, uint32_t H,
+                               const wgt_temporal_state* d_state, const wgt_hit_buffers* d_guides, void* d_workspace,
+                               size_t workspace_bytes, float* d_rgba32f_out, void* d_rgba8_out, float* d_variance_out,
+                               void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  std::string bad = check_denoise_variance_args(params, W, H, d_state, d_guides, d_rgba32f_out, d_rgba8_out);
+  if (bad.empty()) bad = check_denoise_variance_workspace(d_workspace, workspace_bytes, W, H);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const DenoiseVariancePlan plan = plan_denoise_variance(params ? *params : denoise_variance_defaults(), W, H);
+  // no scene is read: the launches are ordered by the stream alone
+  WGT_HIP(ctx, launch_denoise_variance(plan, *d_state, *d_guides, d_workspace, (float4*)d_rgba32f_out,
+                                       (uchar4*)d_rgba8_out, d_variance_out, stream_or_own(ctx, stream)));
+  return WGT_OK;
+}
+
+int wgt_denoise_variance(wgt_ctx* ctx, const wgt_denoise_variance_params* params, uint32_t W, uint32_t H,
+                         const wgt_temporal_state* state, const wgt_hit_buffers* guides, float* rgba32f_out,
+                         uint8_t* rgba8_out, float* variance_out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  const std::string bad = check_denoise_variance_args(params, W, H, state, guides, rgba32f_out, rgba8_out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  // one allocation of the call's own, freed before it returns: the state (its image filtered in
+  // place), the guides' planes, the rgba8 and variance outputs, the workspace
+  const size_t n = (size_t)W * H, ws_bytes = denoise_variance_workspace_bytes(W, H);
+  enum { kIn, kLen, kMom, kPrim, kPos, kNorm, kCol, kFlags, kOut8, kVar, kWs, kParts };
+  const size_t part[kParts] = {n * 16, n * 4, n * 8, n * 4, n * 12, n * 12, n * 12, n, rgba8_out ? n * 4 : 0,
+                               variance_out ? n * 4 : 0, ws_bytes};
+  const void* src[kFlags + 1] = {state->rgba32f, state->len, state->moments, guides->prim,
+                                 guides->pos,    guides->norm, guides->col,  guides->flags};
+  size_t off[kParts + 1] = {0};
+  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
+  struct Alloc {
+    char* p = nullptr;
+    ~Alloc() {
+      if (p) (void)hipFree(p);
+    }
+  } mem;
+  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
+  }
+  int rc = WGT_OK;
+  for (int k = 0; k <= kFlags && rc == WGT_OK; ++k)
+    if (hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+      rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a denoiser input failed");
+  const auto at = [&](int k) { return part[k] ? mem.p + off[k] : nullptr; };
+  wgt_hit_buffers dg{};
+  dg.prim = (uint32_t*)at(kPrim); dg.pos = (float*)at(kPos); dg.norm = (float*)at(kNorm); dg.col = (float*)at(kCol);
+  dg.flags = (uint8_t*)at(kFlags);
+  const wgt_temporal_state dst{(float*)at(kIn), (float*)at(kLen), (float*)at(kMom)};
+  if (rc == WGT_OK)
+    rc = wgt_denoise_variance_async(ctx, params, W, H, &dst, &dg, at(kWs), ws_bytes, rgba32f_out ? dst.rgba32f : nullptr,
+                                    at(kOut8), (float*)at(kVar), ctx->stream);
+  if (rc == WGT_OK && rgba32f_out) rc = fetch(ctx, rgba32f_out, at(kIn), n * 16);
+  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, at(kOut8), n * 4);
+  if (rc == WGT_OK && variance_out) rc = fetch(ctx, variance_out, at(kVar), n * 4);
+  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
+  return rc != WGT_OK ? rc : rs;
+}
+
 int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8]) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
   if (!counts) return fail(ctx, WGT_E_INVALID, "null counts");

@@ -27,6 +27,8 @@ filter guided by that G-buffer), computed on the device on the batch's stream.
 (wgt_temporal_accumulate: each frame's history reprojected through its G-buffer, capped at
 `--max-history` frames), and with `--denoise` NNN_accum_denoised.png; one process only, because the
 ranks of a distributed run see no consecutive frames.
+`--denoise-variance` (with `--accumulate`) also writes NNN_accum_vdenoised.png: the accumulated state
+through wgt_denoise_variance, the filter whose luminance weight follows each pixel's variance.
 
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -93,7 +95,7 @@ class FrameRenderer:
                 "flags": g["flags"]}
 
     def stream(self, frame_batches, depth: int = 2, denoised=None, accumulated=None, max_history=None,
-               accumulated_denoised=None):
+               accumulated_denoised=None, accumulated_vdenoised=None):
         """Yield (batch, {frame: (H, W, 4) uint8}) for each batch of `frame_batches`, in
         order.  Batch k renders on pipeline stream k % depth into buffer set k % depth;
         it is issued before batch k-1 is handed out, so the device always has the next
@@ -116,11 +118,13 @@ class FrameRenderer:
         render launch and before its first G-buffer, for an event recorded behind the previous
         batch's last accumulation, so the renders still overlap and only the short accumulation
         passes are serialised.  accumulated_denoised: a dict that also receives the accumulated
-        radiance through denoise_async."""
+        radiance through denoise_async.  accumulated_vdenoised: a dict that also receives the
+        accumulated state through denoise_variance_async (default parameters), on the same stream
+        right behind the accumulation."""
         import torch
 
         from ._lib import TILE_DTYPE
-        from .tracer import denoise_workspace_bytes
+        from .tracer import denoise_variance_workspace_bytes, denoise_workspace_bytes
 
         dev = torch.device("cuda", self.ctx.device)
         W, H = self.W, self.H
@@ -129,9 +133,10 @@ class FrameRenderer:
             return
         streams = [torch.cuda.ExternalStream(self.ctx.pipeline_stream(i), device=dev) for i in range(depth)]
         d_out = [torch.empty((nmax, H, W, 4), dtype=torch.uint8, device=dev) for _ in range(depth)]
-        d_dn = d_acc = d_accdn = None
+        d_dn = d_acc = d_accdn = d_accvdn = None
         acc = accumulated is not None
         dn_acc = acc and accumulated_denoised is not None
+        vdn_acc = acc and accumulated_vdenoised is not None
         n = W * H
 
         def u8_set():
@@ -145,20 +150,22 @@ class FrameRenderer:
             d_vec = [torch.empty((3, 3, n), dtype=torch.float32, device=dev) for _ in range(sets)]
             d_prim = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(sets)]
             d_flags = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(sets)]
-        if denoised is not None or dn_acc:
-            ws_bytes = denoise_workspace_bytes(W, H)
+        if denoised is not None or dn_acc or vdn_acc:
+            ws_bytes = max(denoise_workspace_bytes(W, H), denoise_variance_workspace_bytes(W, H))  # one serves both
             d_ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(depth)]
         if denoised is not None:
             d_dn = u8_set()
         if acc:
             d_acc = u8_set()
             d_accdn = u8_set() if dn_acc else None
+            d_accvdn = u8_set() if vdn_acc else None
             d_state = [{"f32": torch.empty((H, W, 4), dtype=torch.float32, device=dev),
                         "len": torch.empty(n, dtype=torch.float32, device=dev),
                         "moments": torch.empty((2, n), dtype=torch.float32, device=dev)} for _ in range(2)]
             history = 0       # frames accumulated so far
             last_acc = None   # recorded behind the previous batch's last accumulation
-        copies = [(d_dn, denoised), (d_acc, accumulated), (d_accdn, accumulated_denoised)]
+        copies = [(d_dn, denoised), (d_acc, accumulated), (d_accdn, accumulated_denoised),
+                  (d_accvdn, accumulated_vdenoised)]
         pending = []
         for k, b in enumerate(frame_batches):
             j = k % depth
@@ -198,6 +205,11 @@ class FrameRenderer:
                         if dn_acc:
                             self.ctx.denoise_async(W, H, out["f32"], d_ws[j].data_ptr(), ws_bytes,
                                                    d_u8_out=d_accdn[j][i].data_ptr(), stream=s.cuda_stream, **guides)
+                        if vdn_acc:
+                            # the same workspace right behind the plain filter: one stream orders them
+                            self.ctx.denoise_variance_async(W, H, out, d_ws[j].data_ptr(), ws_bytes,
+                                                            d_u8_out=d_accvdn[j][i].data_ptr(), stream=s.cuda_stream,
+                                                            **guides)
                         history += 1
                 if acc:
                     last_acc = torch.cuda.Event()
@@ -247,6 +259,9 @@ def main(argv=None):
                     help="also write NNN_accum.png: the frames accumulated over time in frame order by reprojecting "
                          "the history (wgt_temporal_accumulate) on the device; with --denoise also "
                          "NNN_accum_denoised.png, the accumulated radiance through the filter")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="with --accumulate, also write NNN_accum_vdenoised.png: the accumulated state through the "
+                         "variance-guided filter (wgt_denoise_variance, default parameters) on the device")
     ap.add_argument("--max-history", type=int, default=32, help="--accumulate: the history length's cap (1..65536)")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
@@ -255,6 +270,8 @@ def main(argv=None):
         ap.error("--denoise needs --out")
     if a.accumulate and not a.out:
         ap.error("--accumulate needs --out")
+    if a.denoise_variance and not (a.accumulate and a.out):
+        ap.error("--denoise-variance needs --accumulate and --out: it filters the accumulated state")
     if a.accumulate and not 1 <= a.max_history <= 65536:
         ap.error("--max-history must be 1..65536")
     if a.accumulate and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -295,13 +312,16 @@ def main(argv=None):
     denoised = {} if a.denoise else None
     accumulated = {} if a.accumulate else None
     accumulated_denoised = {} if a.accumulate and a.denoise else None
+    accumulated_vdenoised = {} if a.accumulate and a.denoise_variance else None
     for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised, accumulated=accumulated,
-                             max_history=a.max_history, accumulated_denoised=accumulated_denoised):
+                             max_history=a.max_history, accumulated_denoised=accumulated_denoised,
+                             accumulated_vdenoised=accumulated_vdenoised):
         if a.out:
             for f in b:  # render.cpp:494-497
                 pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
                 for suffix, extra in (("denoised", denoised), ("accum", accumulated),
-                                      ("accum_denoised", accumulated_denoised)):
+                                      ("accum_denoised", accumulated_denoised),
+                                      ("accum_vdenoised", accumulated_vdenoised)):
                     if extra is not None:
                         pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_{suffix}.png"),
                                                    extra.pop(f)))

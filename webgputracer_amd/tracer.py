@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+                   WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
@@ -176,6 +177,18 @@ def denoise_defaults():
 def denoise_workspace_bytes(W: int, H: int) -> int:
     """Bytes of device scratch Context.denoise_async needs for a W x H image (0: a size it refuses)."""
     return int(lib().wgt_denoise_workspace_bytes(W, H))
+
+
+def denoise_variance_defaults():
+    """wgt_denoise_variance_defaults: a WgtDenoiseVarianceParams of the library's defaults."""
+    p = WgtDenoiseVarianceParams()
+    check(lib().wgt_denoise_variance_defaults(ctypes.byref(p)))
+    return p
+
+
+def denoise_variance_workspace_bytes(W: int, H: int) -> int:
+    """Bytes of device scratch Context.denoise_variance_async needs for a W x H image (0: a size it refuses)."""
+    return int(lib().wgt_denoise_variance_workspace_bytes(W, H))
 
 
 def temporal_defaults():
@@ -562,6 +575,73 @@ class Context:
                                                           p_gprev, ctypes.byref(st_out),
                                                           ctypes.c_void_p(d_u8_out or None),
                                                           ctypes.c_void_p(stream or None)))
+
+    @staticmethod
+    def _denoise_variance_params(iterations, normal_power, sigma_pos, sigma_lum, min_history, demodulate):
+        """wgt_denoise_variance_params: the library's defaults, with the arguments that are not None over them."""
+        p = denoise_variance_defaults()
+        for name, value in (("iterations", iterations), ("normal_power", normal_power), ("sigma_pos", sigma_pos),
+                            ("sigma_lum", sigma_lum), ("min_history", min_history)):
+            if value is not None:
+                setattr(p, name, value)
+        p.flags = _lib.WGT_DENOISE_DEMODULATE if demodulate else 0
+        return p
+
+    def denoise_variance(self, state, guides, iterations=None, normal_power=None, sigma_pos=None, sigma_lum=None,
+                         min_history=None, demodulate=True, want=("f32", "u8")):
+        """Variance-guided a-trous filter (wgt_denoise_variance) of `state`, the dict temporal_accumulate
+        returns (its "f32", "len" and "moments" are read), guided by `guides`, the dict render_gbuffer
+        returns for the same pixels (prim, pos, norm, col and flags are read).  None for a parameter
+        takes the library's default (5 iterations, normal_power 7, sigma_pos 1.0, sigma_lum 4.0,
+        min_history 4).  Returns {"f32": (H, W, 4) float32, "u8": (H, W, 4) uint8, "var": (H, W) float32,
+        the filtered variance of the demodulated luminance}, None for an output not in `want`.  Lights,
+        misses, non-finite pixels and pixels without history pass through unchanged, with variance 0."""
+        missing = [k for k in ("f32", "len", "moments") if state.get(k) is None]
+        if missing:
+            raise ValueError(f"denoise_variance: state lacks {missing}")
+        color = np.ascontiguousarray(state["f32"], np.float32)
+        if color.ndim != 3 or color.shape[2] != 4:
+            raise ValueError(f"denoise_variance: state['f32'] must be (H, W, 4), got {color.shape}")
+        H, W = color.shape[:2]
+        length = np.ascontiguousarray(state["len"], np.float32)
+        moments = np.ascontiguousarray(state["moments"], np.float32)
+        for k, a, size in (("len", length, H * W), ("moments", moments, 2 * H * W)):
+            if a.size != size:
+                raise ValueError(f"denoise_variance: state[{k!r}] has {a.size} elements, not {size}")
+        missing = [k for k in ("prim", "pos", "norm", "col", "flags") if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"denoise_variance: guides lack {missing}")
+        planar = {k: np.ascontiguousarray(np.moveaxis(np.asarray(guides[k], np.float32).reshape(H, W, 3), -1, 0))
+                  for k in ("pos", "norm", "col")}
+        planar["prim"] = np.ascontiguousarray(guides["prim"], np.uint32).reshape(H, W)
+        planar["flags"] = np.ascontiguousarray(guides["flags"], np.uint8).reshape(H, W)
+        bufs = WgtHitBuffers(**{k: a.ctypes.data for k, a in planar.items()})
+        st = WgtTemporalState(color.ctypes.data, length.ctypes.data, moments.ctypes.data)
+        f32 = np.zeros((H, W, 4), np.float32) if "f32" in want else None
+        u8 = np.zeros((H, W, 4), np.uint8) if "u8" in want else None
+        var = np.zeros((H, W), np.float32) if "var" in want else None
+        p = self._denoise_variance_params(iterations, normal_power, sigma_pos, sigma_lum, min_history, demodulate)
+        self._check(self._L.wgt_denoise_variance(self.h, ctypes.byref(p), W, H, ctypes.byref(st), ctypes.byref(bufs),
+                                                 ptr(f32), ptr(u8), ptr(var)))
+        return {"f32": f32, "u8": u8, "var": var}
+
+    def denoise_variance_async(self, W, H, state, d_workspace, workspace_bytes, prim=0, pos=0, norm=0, col=0, flags=0,
+                               d_f32_out=0, d_u8_out=0, d_var_out=0, iterations=None, normal_power=None,
+                               sigma_pos=None, sigma_lum=None, min_history=None, demodulate=True, stream=0):
+        """Device-pointer launch (wgt_denoise_variance_async; raw device addresses, 0 = NULL): `state`, a
+        dict {"f32", "len", "moments"} of addresses as temporal_accumulate_async's `out`, the G-buffer
+        planes of render_gbuffer_async's single full-frame tile, a workspace of
+        denoise_variance_workspace_bytes(W, H) bytes that is the caller's, and the outputs, of which
+        d_f32_out may equal state["f32"].  Ordered on `stream` (0 = the context's)."""
+        st = WgtTemporalState(*(state.get(k) or None for k in ("f32", "len", "moments")))
+        bufs = _device_hit_buffers(prim, 0, pos, norm, col, flags)
+        p = self._denoise_variance_params(iterations, normal_power, sigma_pos, sigma_lum, min_history, demodulate)
+        self._check(self._L.wgt_denoise_variance_async(self.h, ctypes.byref(p), W, H, ctypes.byref(st),
+                                                       ctypes.byref(bufs), ctypes.c_void_p(d_workspace or None),
+                                                       workspace_bytes, ctypes.c_void_p(d_f32_out or None),
+                                                       ctypes.c_void_p(d_u8_out or None),
+                                                       ctypes.c_void_p(d_var_out or None),
+                                                       ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
