@@ -22,6 +22,8 @@
  *   HitInfo after sample_hit path_tracer.wgsl:27-36   wgt_trace_hits (the whole hit record)
  *   (none: HitInfo of a pixel's first camera ray)     wgt_render_gbuffer (first-hit G-buffer)
  *   (none: history reprojected frame to frame)        wgt_temporal_accumulate (temporal accumulation)
+ *   (none: history that follows a moved mesh)         wgt_motion_snapshot, wgt_motion_reproject,
+ *                                                     wgt_temporal_accumulate_motion
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -432,9 +434,10 @@ int wgt_denoise_async(wgt_ctx *ctx, const wgt_denoise_params *params, uint32_t W
  * caller owns the history and alternates two wgt_temporal_state sets and two G-buffers.  A pixel
  * accumulates when it hit a primitive that is not emissive and its guides and colour are finite and
  * within 2^100; every other pixel (lights, misses, NaN) passes through bit for bit with len = 0 and
- * moments = 0, and is never a tap.  Known limit: there are no per-primitive motion vectors, so a
+ * moments = 0, and is never a tap.  Known limit of this form: it knows no per-primitive motion, so a
  * moved triangle fails the plane test and restarts its history, while a triangle sliding in its own
- * plane keeps a history that is not its own. */
+ * plane keeps a history that is not its own; wgt_temporal_accumulate_motion (below) follows the
+ * triangles that wgt_update_triangles and its device forms move. */
 #define WGT_TEMPORAL_MATCH_PRIM 1u
 typedef struct {
   uint32_t max_history; /* 1..65536 (default 32): the history length is capped here; 1 = no accumulation */
@@ -482,6 +485,70 @@ int wgt_temporal_accumulate_async(wgt_ctx *ctx, const wgt_temporal_params *param
                                   const float *d_rgba32f_in, const wgt_hit_buffers *d_guides,
                                   const wgt_temporal_state *d_prev, const wgt_hit_buffers *d_guides_prev,
                                   const wgt_temporal_state *d_out, void *d_rgba8_out, void *stream);
+
+/* ---- temporal history that follows moved triangles (no reference counterpart) -- */
+/* A refit never changes topology and primitive ids are stable, so a pixel that hit triangle t can ask
+ * where its hit point lay on t before the update.  Per frame: wgt_motion_snapshot, then the update,
+ * then the render and its G-buffer, then wgt_motion_reproject, then wgt_temporal_accumulate_motion
+ * (DESIGN.md §4.10 states the arithmetic operation by operation; tests/motion_restatement.py is the
+ * same in numpy, and the results equal it bit for bit).
+ *
+ * wgt_motion_snapshot copies the resident triangles, as they are at that point of the stream's order
+ * (NULL = the context's stream), into device memory the context owns: per original triangle index 48
+ * bytes (v0, e1, e2 of its leaf-ordered record and its face normal) and the leaf slot of its record,
+ * 52 bytes per triangle, allocated by the first snapshot after an upload and not counted in
+ * wgt_scene_info's device_bytes.  It returns once queued, ordered against every query, every
+ * reproject and every update of the context.  A later snapshot replaces it; an update never touches
+ * it; wgt_upload_scene and wgt_destroy drop it.  WGT_E_NOSCENE before an upload, WGT_E_INVALID for a
+ * scene without triangles. */
+int wgt_motion_snapshot(wgt_ctx *ctx, void *stream);
+/* Diagnostic (synchronous): the snapshot as n_tris x 12 floats (v0, e1, e2, face normal) in original
+ * triangle order.  WGT_E_INVALID without a snapshot or with cap_tris below the scene's n_tris. */
+int wgt_motion_snapshot_read(wgt_ctx *ctx, float *out, uint32_t cap_tris);
+
+typedef struct {
+  float *pos_prev;   /* 3 planes of n floats: where the hit point lay before the update */
+  float *norm_prev;  /* 3 planes of n floats: the normal it had there (turned as the record's) */
+} wgt_motion_buffers; /* 16 bytes */
+
+/* guides: n planar records as wgt_render_gbuffer or wgt_trace_hits writes them, of which prim, pos,
+ * norm and flags are required (dist and col are ignored).  A record that hit a triangle which differs
+ * from the snapshot (any of the nine floats of v0, e1, e2) gets its hit point's barycentric
+ * coordinates on the resident triangle carried to the snapshot's triangle, and the snapshot's face
+ * normal turned by WGT_HIT_FRONT_FACE; every other record (an unmoved triangle, a quad, light, sphere,
+ * miss or any other id) gets pos and norm back bit for bit, and nothing is indexed by its id.  A
+ * zero-area triangle on either side gives NaN or inf, which wgt_temporal_accumulate_motion reads as
+ * "no history".  n is 1..2^25.  Order of checks, each WGT_E_INVALID naming the argument, nothing
+ * launched: NULL context; WGT_E_NOSCENE; no snapshot since the last upload; NULL guides or a NULL
+ * required guide; NULL out or a NULL plane; n out of range.  Pointers are not validated.
+ * The synchronous form takes host pointers and stages through the context's scratch; the async form
+ * takes host structs of device pointers, is ordered on `stream` (NULL = the context's) against the
+ * snapshots and updates of the context, and returns once queued. */
+int wgt_motion_reproject(wgt_ctx *ctx, uint32_t n, const wgt_hit_buffers *guides, const wgt_motion_buffers *out);
+int wgt_motion_reproject_async(wgt_ctx *ctx, uint32_t n, const wgt_hit_buffers *d_guides,
+                               const wgt_motion_buffers *d_out, void *stream);
+
+/* wgt_temporal_accumulate with the history looked up where the pixel's surface point lay before the
+ * update: motion holds pos_prev and norm_prev of the W x H pixels (wgt_motion_reproject of `guides`).
+ * The previous camera projects pos_prev instead of pos, a pixel whose pos_prev or norm_prev is not
+ * finite and within 2^100 finds no history (it starts at len = 1), and a tap is tested against
+ * norm_prev and the plane through pos_prev; everything else is wgt_temporal_accumulate's, and with
+ * pos_prev == pos and norm_prev == norm bitwise so is the result, bit for bit.  motion and its two
+ * planes are required when prev is set (checked right after the first-frame triple) and ignored on
+ * the first frame, where motion may be NULL.  Every other argument, check and rule is
+ * wgt_temporal_accumulate's, the synchronous and the async form alike. */
+int wgt_temporal_accumulate_motion(wgt_ctx *ctx, const wgt_temporal_params *params, uint32_t W, uint32_t H,
+                                   const wgt_camera_param *cam, const wgt_camera_param *cam_prev,
+                                   const float *rgba32f_in, const wgt_hit_buffers *guides,
+                                   const wgt_motion_buffers *motion, const wgt_temporal_state *prev,
+                                   const wgt_hit_buffers *guides_prev, const wgt_temporal_state *out,
+                                   uint8_t *rgba8_out);
+int wgt_temporal_accumulate_motion_async(wgt_ctx *ctx, const wgt_temporal_params *params, uint32_t W, uint32_t H,
+                                         const wgt_camera_param *cam, const wgt_camera_param *cam_prev,
+                                         const float *d_rgba32f_in, const wgt_hit_buffers *d_guides,
+                                         const wgt_motion_buffers *d_motion, const wgt_temporal_state *d_prev,
+                                         const wgt_hit_buffers *d_guides_prev, const wgt_temporal_state *d_out,
+                                         void *d_rgba8_out, void *stream);
 
 /* ---- variance-guided denoising (no reference counterpart) ------------------ */
 /* The second half of SVGF-style denoising: wgt_denoise's a-trous filter with a luminance weight

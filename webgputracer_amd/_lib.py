@@ -67,6 +67,11 @@ class WgtTemporalState(ctypes.Structure):
     _fields_ = [("rgba32f", ctypes.c_void_p), ("len", ctypes.c_void_p), ("moments", ctypes.c_void_p)]
 
 
+class WgtMotionBuffers(ctypes.Structure):
+    """wgt_motion_buffers (16 bytes): where each hit lay before the update, 3 planes of n floats each."""
+    _fields_ = [("pos_prev", ctypes.c_void_p), ("norm_prev", ctypes.c_void_p)]
+
+
 class WgtStats(ctypes.Structure):
     _fields_ = [("queries", ctypes.c_uint64), ("traced_rays", ctypes.c_uint64), ("samples", ctypes.c_uint64),
                 ("nan_rays", ctypes.c_uint64), ("node_visits", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64),
@@ -118,6 +123,8 @@ EXPORTS = [
     "wgt_temporal_defaults", "wgt_temporal_accumulate", "wgt_temporal_accumulate_async",
     "wgt_denoise_variance_defaults", "wgt_denoise_variance_workspace_bytes", "wgt_denoise_variance",
     "wgt_denoise_variance_async",
+    "wgt_motion_snapshot", "wgt_motion_snapshot_read", "wgt_motion_reproject", "wgt_motion_reproject_async",
+    "wgt_temporal_accumulate_motion", "wgt_temporal_accumulate_motion_async",
 ]
 
 _lib = None
@@ -205,6 +212,18 @@ def lib():
         "wgt_denoise_variance_async": (I, [P, ctypes.POINTER(WgtDenoiseVarianceParams), U32, U32,
                                            ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers), P,
                                            ctypes.c_size_t, P, P, P, P]),
+        "wgt_motion_snapshot": (I, [P, P]),
+        "wgt_motion_snapshot_read": (I, [P, P, U32]),
+        "wgt_motion_reproject": (I, [P, U32, ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtMotionBuffers)]),
+        "wgt_motion_reproject_async": (I, [P, U32, ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtMotionBuffers), P]),
+        "wgt_temporal_accumulate_motion": (I, [P, ctypes.POINTER(WgtTemporalParams), U32, U32, P, P, P,
+                                               ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtMotionBuffers),
+                                               ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers),
+                                               ctypes.POINTER(WgtTemporalState), P]),
+        "wgt_temporal_accumulate_motion_async": (I, [P, ctypes.POINTER(WgtTemporalParams), U32, U32, P, P, P,
+                                                     ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtMotionBuffers),
+                                                     ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers),
+                                                     ctypes.POINTER(WgtTemporalState), P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -490,10 +490,12 @@ static const char* null_temporal_guide(const wgt_hit_buffers& g, bool prev) {
   return nullptr;
 }
 
-std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
-                                const wgt_camera_param* cam_prev, const void* in, const wgt_hit_buffers* guides,
-                                const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
-                                const wgt_temporal_state* out) {
+// Both forms' checks: motion_form adds the motion buffers' right after the first-frame triple.
+static std::string check_temporal_form(const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                       const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const void* in,
+                                       const wgt_hit_buffers* guides, bool motion_form, const wgt_motion_buffers* motion,
+                                       const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                       const wgt_temporal_state* out) {
   if (!in) return "null input image";
   if (!cam) return "null camera";
   if (!guides) return "null guides";
@@ -505,6 +507,11 @@ std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, u
   if (!first) {
     if (!prev || !guides_prev || !cam_prev)
       return "first-frame arguments: prev, guides_prev and cam_prev must be all null (the first frame) or all set";
+    if (motion_form) {
+      if (!motion) return "null motion";
+      if (!motion->pos_prev) return "null motion.pos_prev";
+      if (!motion->norm_prev) return "null motion.norm_prev";
+    }
     if (!prev->rgba32f) return "null prev.rgba32f";
     if (!prev->len) return "null prev.len";
     if (const char* bad = null_temporal_guide(*guides_prev, true)) return bad;
@@ -542,6 +549,34 @@ std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, u
     if (out->moments && ranges_overlap(out->moments, n * 8, prev->moments, n * 8))
       return "overlap: out.moments and prev.moments";
   }
+  return "";
+}
+
+std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
+                                const wgt_camera_param* cam_prev, const void* in, const wgt_hit_buffers* guides,
+                                const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                const wgt_temporal_state* out) {
+  return check_temporal_form(params, W, H, cam, cam_prev, in, guides, false, nullptr, prev, guides_prev, out);
+}
+
+std::string check_temporal_motion_args(const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                       const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const void* in,
+                                       const wgt_hit_buffers* guides, const wgt_motion_buffers* motion,
+                                       const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                       const wgt_temporal_state* out) {
+  return check_temporal_form(params, W, H, cam, cam_prev, in, guides, true, motion, prev, guides_prev, out);
+}
+
+std::string check_motion_reproject_args(bool has_snapshot, uint32_t n, const wgt_hit_buffers* guides,
+                                        const wgt_motion_buffers* out) {
+  if (!has_snapshot) return "no motion snapshot since the last upload (wgt_motion_snapshot)";
+  if (!guides) return "null guides";
+  if (const char* bad = null_temporal_guide(*guides, false)) return bad;
+  if (!out) return "null out";
+  if (!out->pos_prev) return "null out.pos_prev";
+  if (!out->norm_prev) return "null out.norm_prev";
+  if (n < 1 || n > kMotionMaxRecords)
+    return "n " + std::to_string(n) + " is not in 1.." + std::to_string(kMotionMaxRecords);
   return "";
 }
 

@@ -10,6 +10,7 @@
 #include "../wgt_denoise.h"
 #include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
+#include "../wgt_motion.h"
 #include "../wgt_temporal.h"
 #include "bvh.h"
 
@@ -156,6 +157,19 @@ std::string check_temporal_args(const wgt_temporal_params* params, uint32_t W, u
                                 const wgt_camera_param* cam_prev, const void* in, const wgt_hit_buffers* guides,
                                 const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
                                 const wgt_temporal_state* out);
+// wgt_temporal_accumulate_motion's: the same checks in the same order, with the
+// motion buffers' right after the first-frame triple: when there is a previous frame, a null motion,
+// motion->pos_prev or motion->norm_prev; on the first frame motion is not looked at.
+std::string check_temporal_motion_args(const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                       const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const void* in,
+                                       const wgt_hit_buffers* guides, const wgt_motion_buffers* motion,
+                                       const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                                       const wgt_temporal_state* out);
+// wgt_motion_reproject's checks after the context and the scene, in their order: no snapshot since
+// the last upload; null guides or a null required guide (prim, pos, norm, flags); null out or a null
+// plane; n outside 1..kMotionMaxRecords.
+std::string check_motion_reproject_args(bool has_snapshot, uint32_t n, const wgt_hit_buffers* guides,
+                                        const wgt_motion_buffers* out);
 // Of arguments that passed the checks (cam_prev null: the first-frame form): each camera's
 // projection constants in the fp32 operations of the specification, from make_frame.
 TemporalCam temporal_camera(const wgt_camera_param& cam, uint32_t W, uint32_t H);

@@ -51,12 +51,16 @@ struct wgt_ctx {
   std::vector<uint32_t> level_begin;
   DevBuf level_order;
   float refit_host_ms = 0.0f, refit_device_ms = 0.0f;  // of the last update (wgt_update_timing)
+  // wgt_motion_snapshot: n_tris x 48 B (v0, e1, e2, face normal by original index), then n_tris leaf
+  // slots; allocated by the first snapshot after an upload, dropped by the next upload
+  DevBuf motion;
+  bool has_snapshot = false;
   // scratch for the synchronous entry points: the renders' tile list, outputs and counters; the
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
   // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
-  // a refit's moved triangles; the device check's result (RefitCheck)
+  // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kMoved, kCheck, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -407,6 +411,7 @@ void wgt_destroy(wgt_ctx* ctx) {
   if (ctx->scene_mem) (void)hipFree(ctx->scene_mem);
   for (DevBuf& b : ctx->buf) free_buf(b);
   free_buf(ctx->level_order);
+  free_buf(ctx->motion);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -517,6 +522,8 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
   ctx->fixed_extent = fixed_ext;
   ctx->level_begin.clear();  // the next refit prepares the new tree's level lists
   free_buf(ctx->level_order);
+  free_buf(ctx->motion);  // the old scene's snapshot: no launch reads it any more
+  ctx->has_snapshot = false;
   WGT_HIP(ctx, hipMalloc(&ctx->scene_mem, plan.host.size()));
   WGT_HIP(ctx, hipMemcpy(ctx->scene_mem, plan.host.data(), plan.host.size(), hipMemcpyHostToDevice));
   DevScene& sc = ctx->sc;
@@ -1009,44 +1016,58 @@ int wgt_temporal_defaults(wgt_temporal_params* out) {
   return WGT_OK;
 }
 
-int wgt_temporal_accumulate_async(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
-                                  const wgt_camera_param* cam, const wgt_camera_param* cam_prev,
-                                  const float* d_rgba32f_in, const wgt_hit_buffers* d_guides,
-                                  const wgt_temporal_state* d_prev, const wgt_hit_buffers* d_guides_prev,
-                                  const wgt_temporal_state* d_out, void* d_rgba8_out, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The two forms of the accumulation share everything but one check and the motion buffers:
+// motion_form = wgt_temporal_accumulate_motion (motion is then looked at when there is a previous frame).
+int temporal_async(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
+                   const wgt_camera_param* cam_prev, const float* d_rgba32f_in, const wgt_hit_buffers* d_guides,
+                   bool motion_form, const wgt_motion_buffers* d_motion, const wgt_temporal_state* d_prev,
+                   const wgt_hit_buffers* d_guides_prev, const wgt_temporal_state* d_out, void* d_rgba8_out,
+                   void* stream) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
-  const std::string bad = check_temporal_args(params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, d_prev, d_guides_prev, d_out);
+  const std::string bad =
+      motion_form ? check_temporal_motion_args(params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, d_motion, d_prev,
+                                               d_guides_prev, d_out)
+                  : check_temporal_args(params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, d_prev, d_guides_prev, d_out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   const TemporalPlan plan = plan_temporal(params ? *params : temporal_defaults(), W, H, *cam, cam_prev);
   // no scene is read: the launch is ordered by the stream alone
-  WGT_HIP(ctx, launch_temporal(plan, (const float4*)d_rgba32f_in, *d_guides, d_prev, d_guides_prev, *d_out,
-                               (uchar4*)d_rgba8_out, stream_or_own(ctx, stream)));
+  WGT_HIP(ctx, launch_temporal(plan, (const float4*)d_rgba32f_in, *d_guides, motion_form && !plan.first ? d_motion : nullptr,
+                               d_prev, d_guides_prev, *d_out, (uchar4*)d_rgba8_out, stream_or_own(ctx, stream)));
   return WGT_OK;
 }
 
-int wgt_temporal_accumulate(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
-                            const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const float* rgba32f_in,
-                            const wgt_hit_buffers* guides, const wgt_temporal_state* prev,
-                            const wgt_hit_buffers* guides_prev, const wgt_temporal_state* out, uint8_t* rgba8_out) {
+int temporal_sync(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H, const wgt_camera_param* cam,
+                  const wgt_camera_param* cam_prev, const float* rgba32f_in, const wgt_hit_buffers* guides,
+                  bool motion_form, const wgt_motion_buffers* motion, const wgt_temporal_state* prev,
+                  const wgt_hit_buffers* guides_prev, const wgt_temporal_state* out, uint8_t* rgba8_out) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
-  const std::string bad = check_temporal_args(params, W, H, cam, cam_prev, rgba32f_in, guides, prev, guides_prev, out);
+  const std::string bad =
+      motion_form ? check_temporal_motion_args(params, W, H, cam, cam_prev, rgba32f_in, guides, motion, prev, guides_prev, out)
+                  : check_temporal_args(params, W, H, cam, cam_prev, rgba32f_in, guides, prev, guides_prev, out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   // one allocation of the call's own, freed before it returns: the image (accumulated in place), the
-  // guides' planes (prim, pos, norm, flags), the previous state and guides, the new len and moments,
-  // the rgba8 output
+  // guides' planes (prim, pos, norm, flags), the previous state and guides, the motion form's pos_prev
+  // and norm_prev, the new len and moments, the rgba8 output
   const size_t n = (size_t)W * H;
-  const bool first = !prev, mom = out->moments != nullptr;
-  enum { kIn, kPrim, kPos, kNorm, kFlags, kPrevRgba, kPrevLen, kPrevMom, kPPrim, kPPos, kPNorm, kPFlags, kLen, kMom, kOut8, kParts };
+  const bool first = !prev, mom = out->moments != nullptr, mot = motion_form && !first;
+  enum { kIn, kPrim, kPos, kNorm, kFlags, kPrevRgba, kPrevLen, kPrevMom, kPPrim, kPPos, kPNorm, kPFlags, kMPos, kMNorm,
+         kLen, kMom, kOut8, kParts };
   const size_t part[kParts] = {n * 16, n * 4, n * 12, n * 12, n, first ? 0 : n * 16, first ? 0 : n * 4,
                                first || !mom ? 0 : n * 8, first ? 0 : n * 4, first ? 0 : n * 12, first ? 0 : n * 12,
-                               first ? 0 : n, n * 4, mom ? n * 8 : 0, rgba8_out ? n * 4 : 0};
-  const void* src[kPPrim + 4] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->flags,
+                               first ? 0 : n, mot ? n * 12 : 0, mot ? n * 12 : 0, n * 4, mom ? n * 8 : 0,
+                               rgba8_out ? n * 4 : 0};
+  const void* src[kMNorm + 1] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->flags,
                                  first ? nullptr : prev->rgba32f, first ? nullptr : prev->len,
                                  first ? nullptr : prev->moments, first ? nullptr : guides_prev->prim,
                                  first ? nullptr : guides_prev->pos, first ? nullptr : guides_prev->norm,
-                                 first ? nullptr : guides_prev->flags};
+                                 first ? nullptr : guides_prev->flags, mot ? motion->pos_prev : nullptr,
+                                 mot ? motion->norm_prev : nullptr};
   size_t off[kParts + 1] = {0};
   for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
   struct Alloc {
@@ -1060,24 +1081,148 @@ int wgt_temporal_accumulate(wgt_ctx* ctx, const wgt_temporal_params* params, uin
     return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
   }
   int rc = WGT_OK;
-  for (int k = 0; k <= kPFlags && rc == WGT_OK; ++k)
+  for (int k = 0; k <= kMNorm && rc == WGT_OK; ++k)
     if (part[k] && hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
       rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a temporal accumulation input failed");
   const auto at = [&](int k) { return part[k] ? mem.p + off[k] : nullptr; };
   wgt_hit_buffers dg{}, dgp{};
   dg.prim = (uint32_t*)at(kPrim); dg.pos = (float*)at(kPos); dg.norm = (float*)at(kNorm); dg.flags = (uint8_t*)at(kFlags);
   dgp.prim = (uint32_t*)at(kPPrim); dgp.pos = (float*)at(kPPos); dgp.norm = (float*)at(kPNorm); dgp.flags = (uint8_t*)at(kPFlags);
+  const wgt_motion_buffers dmot{(float*)at(kMPos), (float*)at(kMNorm)};
   const wgt_temporal_state dprev{(float*)at(kPrevRgba), (float*)at(kPrevLen), (float*)at(kPrevMom)};
   const wgt_temporal_state dout{(float*)at(kIn), (float*)at(kLen), (float*)at(kMom)};
   if (rc == WGT_OK)
-    rc = wgt_temporal_accumulate_async(ctx, params, W, H, cam, cam_prev, (const float*)at(kIn), &dg, first ? nullptr : &dprev,
-                                       first ? nullptr : &dgp, &dout, at(kOut8), ctx->stream);
+    rc = temporal_async(ctx, params, W, H, cam, cam_prev, (const float*)at(kIn), &dg, motion_form, mot ? &dmot : nullptr,
+                        first ? nullptr : &dprev, first ? nullptr : &dgp, &dout, at(kOut8), ctx->stream);
   if (rc == WGT_OK) rc = fetch(ctx, out->rgba32f, at(kIn), n * 16);
   if (rc == WGT_OK) rc = fetch(ctx, out->len, at(kLen), n * 4);
   if (rc == WGT_OK && mom) rc = fetch(ctx, out->moments, at(kMom), n * 8);
   if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, at(kOut8), n * 4);
   const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
   return rc != WGT_OK ? rc : rs;
+}
+
+// The reproject's launch on stream s (behind the calls' checks): a reader of the scene and of the snapshot.
+int reproject_launch(wgt_ctx* ctx, uint32_t n, const wgt_hit_buffers& dev, const wgt_motion_buffers& out, hipStream_t s) {
+  const float4* snap = (const float4*)ctx->motion.p;
+  const uint32_t* slot_of = (const uint32_t*)(snap + (size_t)ctx->sc.n_tris * kMotionSnapFloat4s);
+  return launch_on(ctx, s, "launch_motion_reproject",
+                   [&] { return launch_motion_reproject(ctx->sc, snap, slot_of, n, dev, out, s); });
+}
+// wgt_motion_reproject's preamble, in the calls' order of checks.
+int reproject_begin(wgt_ctx* ctx, uint32_t n, const wgt_hit_buffers* guides, const wgt_motion_buffers* out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  const std::string bad = check_motion_reproject_args(ctx->has_snapshot, n, guides, out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  return WGT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wgt_temporal_accumulate_async(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                  const wgt_camera_param* cam, const wgt_camera_param* cam_prev,
+                                  const float* d_rgba32f_in, const wgt_hit_buffers* d_guides,
+                                  const wgt_temporal_state* d_prev, const wgt_hit_buffers* d_guides_prev,
+                                  const wgt_temporal_state* d_out, void* d_rgba8_out, void* stream) {
+  return temporal_async(ctx, params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, false, nullptr, d_prev, d_guides_prev,
+                        d_out, d_rgba8_out, stream);
+}
+
+int wgt_temporal_accumulate(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                            const wgt_camera_param* cam, const wgt_camera_param* cam_prev, const float* rgba32f_in,
+                            const wgt_hit_buffers* guides, const wgt_temporal_state* prev,
+                            const wgt_hit_buffers* guides_prev, const wgt_temporal_state* out, uint8_t* rgba8_out) {
+  return temporal_sync(ctx, params, W, H, cam, cam_prev, rgba32f_in, guides, false, nullptr, prev, guides_prev, out,
+                       rgba8_out);
+}
+
+int wgt_temporal_accumulate_motion_async(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                         const wgt_camera_param* cam, const wgt_camera_param* cam_prev,
+                                         const float* d_rgba32f_in, const wgt_hit_buffers* d_guides,
+                                         const wgt_motion_buffers* d_motion, const wgt_temporal_state* d_prev,
+                                         const wgt_hit_buffers* d_guides_prev, const wgt_temporal_state* d_out,
+                                         void* d_rgba8_out, void* stream) {
+  return temporal_async(ctx, params, W, H, cam, cam_prev, d_rgba32f_in, d_guides, true, d_motion, d_prev, d_guides_prev,
+                        d_out, d_rgba8_out, stream);
+}
+
+int wgt_temporal_accumulate_motion(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, uint32_t H,
+                                   const wgt_camera_param* cam, const wgt_camera_param* cam_prev,
+                                   const float* rgba32f_in, const wgt_hit_buffers* guides,
+                                   const wgt_motion_buffers* motion, const wgt_temporal_state* prev,
+                                   const wgt_hit_buffers* guides_prev, const wgt_temporal_state* out,
+                                   uint8_t* rgba8_out) {
+  return temporal_sync(ctx, params, W, H, cam, cam_prev, rgba32f_in, guides, true, motion, prev, guides_prev, out,
+                       rgba8_out);
+}
+
+int wgt_motion_snapshot(wgt_ctx* ctx, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  const DevScene& sc = ctx->sc;
+  if (sc.n_tris == 0) return fail(ctx, WGT_E_INVALID, "the scene has no triangles, so nothing to snapshot");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->motion.p) {  // the first snapshot of this scene; slot_of starts as "no slot" in every word
+    if (int rc = ensure(ctx, ctx->motion, (size_t)sc.n_tris * kMotionSnapBytes)) return rc;
+    WGT_HIP(ctx, hipMemsetAsync(ctx->motion.p, 0xff, ctx->motion.bytes, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+  }
+  float4* snap = (float4*)ctx->motion.p;
+  uint32_t* slot_of = (uint32_t*)(snap + (size_t)sc.n_tris * kMotionSnapFloat4s);
+  hipStream_t s = stream_or_own(ctx, stream);
+  if (int rc = launch_on(ctx, s, "launch_motion_snapshot", [&] { return launch_motion_snapshot(sc, snap, slot_of, s); }))
+    return rc;
+  ctx->has_snapshot = true;
+  return WGT_OK;
+}
+
+int wgt_motion_snapshot_read(wgt_ctx* ctx, float* out, uint32_t cap_tris) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  if (!ctx->has_snapshot) return fail(ctx, WGT_E_INVALID, "no motion snapshot since the last upload (wgt_motion_snapshot)");
+  if (!out) return fail(ctx, WGT_E_INVALID, "null out");
+  if (cap_tris < ctx->sc.n_tris) return fail(ctx, WGT_E_INVALID, "triangle capacity too small");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = use_drain(ctx)) return rc;
+  WGT_HIP(ctx, hipMemcpy(out, ctx->motion.p, (size_t)ctx->sc.n_tris * kMotionSnapFloat4s * 16, hipMemcpyDeviceToHost));
+  return WGT_OK;
+}
+
+int wgt_motion_reproject_async(wgt_ctx* ctx, uint32_t n, const wgt_hit_buffers* d_guides, const wgt_motion_buffers* d_out,
+                               void* stream) {
+  if (int rc = reproject_begin(ctx, n, d_guides, d_out)) return rc;
+  return reproject_launch(ctx, n, *d_guides, *d_out, stream_or_own(ctx, stream));
+}
+
+int wgt_motion_reproject(wgt_ctx* ctx, uint32_t n, const wgt_hit_buffers* guides, const wgt_motion_buffers* out) {
+  int rc;
+  if ((rc = reproject_begin(ctx, n, guides, out))) return rc;
+  // staged through the context's scratch, as wgt_trace_hits' records: prim, pos | norm, flags in;
+  // pos_prev | norm_prev out
+  const size_t N = n;
+  wgt_hit_buffers dev{};
+  const uint32_t* d_prim;
+  const uint8_t* d_flags;
+  float *d_vec, *d_out;
+  if ((rc = stage(ctx, wgt_ctx::kPrim, guides->prim, N * 4, d_prim))) return rc;
+  if ((rc = stage(ctx, wgt_ctx::kHitFlags, guides->flags, N, d_flags))) return rc;
+  if ((rc = scratch(ctx, wgt_ctx::kHitVec, N * 24, d_vec))) return rc;
+  if ((rc = scratch(ctx, wgt_ctx::kMotionOut, N * 24, d_out))) return rc;
+  WGT_HIP(ctx, hipMemcpyAsync(d_vec, guides->pos, N * 12, hipMemcpyHostToDevice, ctx->stream));
+  WGT_HIP(ctx, hipMemcpyAsync(d_vec + 3 * N, guides->norm, N * 12, hipMemcpyHostToDevice, ctx->stream));
+  dev.prim = const_cast<uint32_t*>(d_prim);
+  dev.flags = const_cast<uint8_t*>(d_flags);
+  dev.pos = d_vec;
+  dev.norm = d_vec + 3 * N;
+  const wgt_motion_buffers dout{d_out, d_out + 3 * N};
+  if ((rc = reproject_launch(ctx, n, dev, dout, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, out->pos_prev, dout.pos_prev, N * 12))) return rc;
+  if ((rc = fetch(ctx, out->norm_prev, dout.norm_prev, N * 12))) return rc;
+  return sync_stream(ctx);
 }
 
 int wgt_denoise_variance_defaults(wgt_denoise_variance_params* out) {

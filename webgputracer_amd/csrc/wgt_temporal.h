@@ -39,9 +39,12 @@ struct TemporalPlan {
 // Launcher implemented in wgt_temporal.hip: one pass on `stream`.  Device pointers; prev and
 // guides_prev are null in the first-frame form (plan.first); out.moments and out8 may be null.
 // out.rgba32f may equal `in` (each pixel reads only its own current colour); no out buffer may
-// overlap the prev buffer of the same name (the callers' checks hold this).
+// overlap the prev buffer of the same name (the callers' checks hold this).  motion (null: the plain
+// form): the pixels' pos_prev and norm_prev of wgt_temporal_accumulate_motion, unused in the
+// first-frame form.
 hipError_t launch_temporal(const TemporalPlan& plan, const float4* in, const wgt_hit_buffers& guides,
-                           const wgt_temporal_state* prev, const wgt_hit_buffers* guides_prev,
+                           const wgt_motion_buffers* motion, const wgt_temporal_state* prev,
+                           const wgt_hit_buffers* guides_prev,
                            const wgt_temporal_state& out, uchar4* out8, hipStream_t stream);
 
 }  // namespace wgt

@@ -13,6 +13,8 @@
 //                first (weight, bounds, length, primitive and flags, normal, position, colour) and
 //                the loads of a tap that fails are skipped, which the running sums cannot tell from
 //                adding +0.  No atomics, no scratch, no LDS; every index is checked against W x H.
+//   k_temporal_motion : the same pixel code for wgt_temporal_accumulate_motion: the
+//                history is looked up through the pixel's pos_prev and norm_prev, 24 B more per pixel.
 #include "wgt_temporal.h"
 
 #include "wgt_pixel.h"
@@ -59,8 +61,13 @@ struct TaArgs {
   uchar4* out8;
 };
 
-template <bool MOMENTS>
-__global__ void __launch_bounds__(kTaX * kTaY) k_temporal(TaArgs a) {
+// One pixel.  MOTION (wgt_temporal_accumulate_motion): the previous camera projects the pixel's
+// pos_prev, and a tap is tested against norm_prev and the plane through pos_prev (pos_prev and
+// norm_prev: planar over W x H, read only where there is a previous frame); else both are the
+// pixel's own position and normal, and the two pointers are unused.
+template <bool MOMENTS, bool MOTION>
+__device__ __forceinline__ void temporal_pixel(const TaArgs a, const float* __restrict__ pos_prev,
+                                               const float* __restrict__ norm_prev) {
   const uint32_t W = a.p.W, H = a.p.H;
   const uint32_t X = blockIdx.x * kTaX + threadIdx.x, Y = blockIdx.y * kTaY + threadIdx.y;
   if (X >= W || Y >= H) return;
@@ -83,8 +90,9 @@ __global__ void __launch_bounds__(kTaX * kTaY) k_temporal(TaArgs a) {
   f3 csum{0.0f, 0.0f, 0.0f};
   if (!a.p.first) {
     float xc, yc, xp, yp;
+    const f3 pp = MOTION ? load_planar(pos_prev, n, i) : pos, np = MOTION ? load_planar(norm_prev, n, i) : norm;
     const bool fc = project(a.p.cam, pos, xc, yc);
-    const bool fp = project(a.p.cam_prev, pos, xp, yp);
+    const bool fp = project(a.p.cam_prev, pp, xp, yp) && (!MOTION || (ok3(pp) && ok3(np)));
     const float hx = (float)X + (xp - xc), hy = (float)Y + (yp - yc);
     if (fc && fp && hx > -1.0f && hx < (float)W && hy > -1.0f && hy < (float)H) {
       const float x0f = __builtin_floorf(hx), y0f = __builtin_floorf(hy);
@@ -103,9 +111,9 @@ __global__ void __launch_bounds__(kTaX * kTaY) k_temporal(TaArgs a) {
           const uint32_t pq = a.gp.prim[q];
           if (pq == kNoHit || (a.gp.flags[q] & WGT_HIT_EMISSIVE) || (a.p.match_prim && pq != prim)) continue;
           const f3 nt = load_planar(a.gp.norm, n, q);
-          if (!ok3(nt) || !(dot(norm, nt) >= a.p.normal_min)) continue;
+          if (!ok3(nt) || !(dot(np, nt) >= a.p.normal_min)) continue;
           const f3 pt = load_planar(a.gp.pos, n, q);
-          if (!ok3(pt) || !(__builtin_fabsf(dot(norm, pt - pos)) <= a.p.plane_tol)) continue;
+          if (!ok3(pt) || !(__builtin_fabsf(dot(np, pt - pp)) <= a.p.plane_tol)) continue;
           const float4 ct = a.prev_rgba[q];
           if (!ok3(f3{ct.x, ct.y, ct.z})) continue;
           wsum = wsum + b;
@@ -145,17 +153,29 @@ __global__ void __launch_bounds__(kTaX * kTaY) k_temporal(TaArgs a) {
   if (a.out8) a.out8[i] = make_uchar4(unorm8(o.x), unorm8(o.y), unorm8(o.z), 255);  // write_pixel's store
 }
 
+template <bool MOMENTS>
+__global__ void __launch_bounds__(kTaX * kTaY) k_temporal(TaArgs a) {
+  temporal_pixel<MOMENTS, false>(a, nullptr, nullptr);
+}
+// ... with the motion buffers beside the same arguments: k_temporal's own are laid out as before
+template <bool MOMENTS>
+__global__ void __launch_bounds__(kTaX * kTaY)
+k_temporal_motion(TaArgs a, const float* __restrict__ pos_prev, const float* __restrict__ norm_prev) {
+  temporal_pixel<MOMENTS, true>(a, pos_prev, norm_prev);
+}
+
 }  // namespace
 
 hipError_t launch_temporal(const TemporalPlan& p, const float4* in, const wgt_hit_buffers& g,
-                           const wgt_temporal_state* prev, const wgt_hit_buffers* gprev, const wgt_temporal_state& out,
-                           uchar4* out8, hipStream_t stream) {
+                           const wgt_motion_buffers* motion, const wgt_temporal_state* prev, const wgt_hit_buffers* gprev,
+                           const wgt_temporal_state& out, uchar4* out8, hipStream_t stream) {
   // the callers' checks hold these: the kernel indexes in 32 bits and dereferences what it is given
   if (p.W == 0 || p.H == 0 || p.W > 32768u || p.H > 32768u || (uint64_t)p.W * p.H > (1u << 25)) return hipErrorInvalidValue;
   if (!in || !g.prim || !g.pos || !g.norm || !g.flags || !out.rgba32f || !out.len) return hipErrorInvalidValue;
   if (!p.first && (!prev || !gprev || !prev->rgba32f || !prev->len || !gprev->prim || !gprev->pos || !gprev->norm ||
                    !gprev->flags || (out.moments && !prev->moments)))
     return hipErrorInvalidValue;
+  if (!p.first && motion && (!motion->pos_prev || !motion->norm_prev)) return hipErrorInvalidValue;
   TaArgs a{};
   a.p = p;
   a.in = in;
@@ -171,7 +191,10 @@ hipError_t launch_temporal(const TemporalPlan& p, const float4* in, const wgt_hi
   a.out_mom = out.moments;
   a.out8 = out8;
   const dim3 block(kTaX, kTaY), grid((p.W + kTaX - 1) / kTaX, (p.H + kTaY - 1) / kTaY);
-  if (out.moments) k_temporal<true><<<grid, block, 0, stream>>>(a);
+  if (motion && !p.first) {  // the first-frame form reads no previous frame: the plain kernel
+    if (out.moments) k_temporal_motion<true><<<grid, block, 0, stream>>>(a, motion->pos_prev, motion->norm_prev);
+    else k_temporal_motion<false><<<grid, block, 0, stream>>>(a, motion->pos_prev, motion->norm_prev);
+  } else if (out.moments) k_temporal<true><<<grid, block, 0, stream>>>(a);
   else k_temporal<false><<<grid, block, 0, stream>>>(a);
   return hipGetLastError();
 }

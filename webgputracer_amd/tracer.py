@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
-                   WgtHitBuffers, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
+                   WgtHitBuffers, WgtMotionBuffers, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -505,6 +505,12 @@ class Context:
         plane_tol 1.0).  Returns {"f32": (H, W, 4) float32, "len": (H, W) float32, "moments": (2, H, W)
         float32 or None (moments=False), "u8": (H, W, 4) uint8 or None ("u8" not in want)}.  Lights,
         misses and non-finite pixels pass through unchanged with len 0."""
+        return self._temporal_accumulate(False, None, color, guides, cam, prev, guides_prev, cam_prev, max_history,
+                                         normal_min, plane_tol, match_prim, moments, want)
+
+    def _temporal_accumulate(self, motion_form, motion, color, guides, cam, prev, guides_prev, cam_prev, max_history,
+                             normal_min, plane_tol, match_prim, moments, want):
+        """temporal_accumulate and temporal_accumulate_motion (motion_form: `motion` is passed on)."""
         color = np.ascontiguousarray(color, np.float32)
         if color.ndim != 3 or color.shape[2] != 4:
             raise ValueError(f"temporal_accumulate: color must be (H, W, 4), got {color.shape}")
@@ -537,14 +543,89 @@ class Context:
                 cam_prev = np.ascontiguousarray(cam_prev, CAMERA_DTYPE)
                 p_cam_prev = ptr(cam_prev)
         p = self._temporal_params(max_history, normal_min, plane_tol, match_prim)
+        if motion_form:
+            p_motion = None
+            if motion is not None:
+                missing = [k for k in ("pos_prev", "norm_prev") if motion.get(k) is None]
+                if missing:
+                    raise ValueError(f"temporal_accumulate_motion: motion lacks {missing}")
+                mp = {k: np.ascontiguousarray(np.moveaxis(np.asarray(motion[k], np.float32).reshape(H, W, 3), -1, 0))
+                      for k in ("pos_prev", "norm_prev")}
+                mb = WgtMotionBuffers(mp["pos_prev"].ctypes.data, mp["norm_prev"].ctypes.data)
+                p_motion = ctypes.byref(mb)
+            self._check(self._L.wgt_temporal_accumulate_motion(self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev,
+                                                               ptr(color), ctypes.byref(bufs), p_motion, p_prev, p_gprev,
+                                                               ctypes.byref(st_out), ptr(out["u8"])))
+            return out
         self._check(self._L.wgt_temporal_accumulate(self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev, ptr(color),
                                                     ctypes.byref(bufs), p_prev, p_gprev, ctypes.byref(st_out),
                                                     ptr(out["u8"])))
         return out
 
+    def temporal_accumulate_motion(self, color, guides, cam, motion=None, prev=None, guides_prev=None, cam_prev=None,
+                                   max_history=None, normal_min=None, plane_tol=None, match_prim=False, moments=True,
+                                   want=("u8",)):
+        """temporal_accumulate with a history that follows moved triangles (wgt_temporal_accumulate_motion):
+        `motion` is the dict motion_reproject returned for `guides` ({"pos_prev", "norm_prev"}, (H, W, 3)
+        each), required when prev is set and ignored on the first frame.  Everything else, the returned
+        state included, is temporal_accumulate's."""
+        return self._temporal_accumulate(True, motion, color, guides, cam, prev, guides_prev, cam_prev, max_history,
+                                         normal_min, plane_tol, match_prim, moments, want)
+
+    def motion_snapshot(self, stream=0):
+        """Keep a copy of the resident triangles as they are now (wgt_motion_snapshot), to be taken before
+        an update: motion_reproject then tells where each hit lay before it.  Returns once queued on
+        `stream` (0 = the context's)."""
+        self._check(self._L.wgt_motion_snapshot(self.h, ctypes.c_void_p(stream or None)))
+
+    def motion_snapshot_read(self):
+        """Diagnostic (wgt_motion_snapshot_read): the snapshot as (n_tris, 12) float32, v0, e1, e2 and the
+        face normal of each triangle in original order."""
+        n = self.scene_info()["n_tris"]
+        out = np.zeros((n, 12), np.float32)
+        self._check(self._L.wgt_motion_snapshot_read(self.h, ptr(out), n))
+        return out
+
+    def motion_reproject(self, guides):
+        """Where each hit lay before the update since the last snapshot (wgt_motion_reproject).  guides: a
+        dict as render_gbuffer or trace_hits returns it (prim, pos, norm and flags are read), of any
+        leading shape.  Returns {"pos_prev", "norm_prev"} shaped as guides["pos"]."""
+        missing = [k for k in ("prim", "pos", "norm", "flags") if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"motion_reproject: guides lack {missing}")
+        shape = np.asarray(guides["pos"]).shape
+        prim = np.ascontiguousarray(guides["prim"], np.uint32).reshape(-1)
+        n = prim.size
+        flags = np.ascontiguousarray(guides["flags"], np.uint8).reshape(-1)
+        planar = {k: np.ascontiguousarray(np.asarray(guides[k], np.float32).reshape(n, 3).T) for k in ("pos", "norm")}
+        bufs = WgtHitBuffers(prim=prim.ctypes.data, pos=planar["pos"].ctypes.data, norm=planar["norm"].ctypes.data,
+                             flags=flags.ctypes.data)
+        out = {k: np.zeros((3, n), np.float32) for k in ("pos_prev", "norm_prev")}
+        mb = WgtMotionBuffers(out["pos_prev"].ctypes.data, out["norm_prev"].ctypes.data)
+        self._check(self._L.wgt_motion_reproject(self.h, n, ctypes.byref(bufs), ctypes.byref(mb)))
+        return {k: np.ascontiguousarray(a.T).reshape(shape) for k, a in out.items()}
+
+    def motion_reproject_async(self, n, guides, pos_prev, norm_prev, stream=0):
+        """Device-pointer launch (wgt_motion_reproject_async; raw device addresses): guides, a dict of the
+        planes' addresses (prim, pos, norm, flags) of n records; pos_prev and norm_prev receive 3 planes
+        of n floats each.  Ordered on `stream` (0 = the context's)."""
+        bufs = _device_hit_buffers(guides.get("prim"), 0, guides.get("pos"), guides.get("norm"), 0, guides.get("flags"))
+        mb = WgtMotionBuffers(pos_prev or None, norm_prev or None)
+        self._check(self._L.wgt_motion_reproject_async(self.h, n, ctypes.byref(bufs), ctypes.byref(mb),
+                                                       ctypes.c_void_p(stream or None)))
+
+    def temporal_accumulate_motion_async(self, W, H, cam, d_f32_in, guides, out, motion=None, prev=None,
+                                         guides_prev=None, cam_prev=None, d_u8_out=0, max_history=None,
+                                         normal_min=None, plane_tol=None, match_prim=False, stream=0):
+        """temporal_accumulate_async with a history that follows moved triangles
+        (wgt_temporal_accumulate_motion_async): motion, a dict {"pos_prev", "norm_prev"} of the addresses
+        motion_reproject_async wrote for `guides`, required when prev is set."""
+        self.temporal_accumulate_async(W, H, cam, d_f32_in, guides, out, prev, guides_prev, cam_prev, d_u8_out,
+                                       max_history, normal_min, plane_tol, match_prim, stream, _motion=(motion,))
+
     def temporal_accumulate_async(self, W, H, cam, d_f32_in, guides, out, prev=None, guides_prev=None, cam_prev=None,
                                   d_u8_out=0, max_history=None, normal_min=None, plane_tol=None, match_prim=False,
-                                  stream=0):
+                                  stream=0, _motion=None):
         """Device-pointer launch (wgt_temporal_accumulate_async; raw device addresses, 0 = NULL): the W x H
         rgba32f image at d_f32_in; guides and guides_prev: dicts of the G-buffer planes' addresses
         (prim, pos, norm, flags) of render_gbuffer_async's single full-frame tile; out and prev: dicts
@@ -570,6 +651,16 @@ class Context:
             cam_prev = np.ascontiguousarray(cam_prev, CAMERA_DTYPE)
             p_cam_prev = ptr(cam_prev)
         p = self._temporal_params(max_history, normal_min, plane_tol, match_prim)
+        if _motion is not None:  # the motion form: (motion,)
+            p_motion = None
+            if _motion[0] is not None:
+                mb = WgtMotionBuffers(_motion[0].get("pos_prev") or None, _motion[0].get("norm_prev") or None)
+                p_motion = ctypes.byref(mb)
+            self._check(self._L.wgt_temporal_accumulate_motion_async(
+                self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev, ctypes.c_void_p(d_f32_in or None), ctypes.byref(bufs),
+                p_motion, p_prev, p_gprev, ctypes.byref(st_out), ctypes.c_void_p(d_u8_out or None),
+                ctypes.c_void_p(stream or None)))
+            return
         self._check(self._L.wgt_temporal_accumulate_async(self.h, ctypes.byref(p), W, H, ptr(cam), p_cam_prev,
                                                           ctypes.c_void_p(d_f32_in or None), ctypes.byref(bufs), p_prev,
                                                           p_gprev, ctypes.byref(st_out),
