@@ -24,6 +24,9 @@
  *   (none: history reprojected frame to frame)        wgt_temporal_accumulate (temporal accumulation)
  *   (none: history that follows a moved mesh)         wgt_motion_snapshot, wgt_motion_reproject,
  *                                                     wgt_temporal_accumulate_motion
+ *   camera.spp, one per frame path_tracer.wgsl:23     wgt_render_tile_sampled, ..._tiles_sampled_async,
+ *                                                     wgt_render_gbuffer_sampled (a side per pixel)
+ *   (none: the sides planned from the variance)       wgt_sample_plan
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -311,6 +314,29 @@ int wgt_render_tiles_stats(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W
                            uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
                            wgt_stats *stats);
 
+/* ---- rendering with a per-pixel sample count ------------------------------- */
+/* A sample map is one uint8_t per pixel of the full W x H frame, row-major, indexed by global pixel
+ * coordinates (so any tiling reproduces the frame).  Value k is the side of the pixel's sample grid:
+ * pixel (x, y) is computed exactly as invocation (x, y) of compute_sample with camera.spp = k * k, and
+ * a uniform map of k equals wgt_render_tile at spp = k * k bit for bit.  k = 0 gives a black pixel with
+ * hit id 0xffffffff, the plain calls' spp = 0.  cam->spp is ignored (the camera is checked with spp 1);
+ * cam->seed, or the per-tile seeds, act as in the plain calls.  stats->samples is the sum of k * k over
+ * the rendered pixels.  Limits: sides above 255 and spp values that are not squares are not expressible;
+ * the map is per frame, not per tile.  DESIGN.md §4.11.
+ * Order of checks: everything the plain call checks, in its order, with spp taken as 1; then a NULL
+ * map (WGT_E_INVALID "null sample map", nothing launched).  A map value cannot be out of range.
+ * wgt_render_tile_sampled: wgt_render_tile with a HOST map (W x H bytes, borrowed for the call). */
+int wgt_render_tile_sampled(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                            uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, const uint8_t *sample_map,
+                            uint8_t *rgba8_out, float *rgba32f_out, uint32_t *hit_id_out, wgt_stats *stats);
+/* wgt_render_tiles_async with a DEVICE map, read by the launch in stream order: the rules for
+ * ordering and workspace slots are wgt_render_tiles_async's.  With LPT ordering on (the default) the
+ * cost pre-pass always runs, each pixel at min(k, WGT_PQ_LPT) per side; no result bit depends on it. */
+int wgt_render_tiles_sampled_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                                   uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
+                                   const uint8_t *d_sample_map, void *d_rgba8, float *d_rgba32f,
+                                   uint32_t *d_hit_id, void *stream);
+
 /* ---- closest-hit queries (sample_hit, path_tracer.wgsl:290-310) ---------- */
 /* Rays as SoA host arrays ox,oy,oz,dx,dy,dz (each n floats, packed in that order
  * in `rays`, i.e. rays[k*n + i]).  Writes prim id (lights, quads, triangles,
@@ -381,6 +407,20 @@ int wgt_render_gbuffer(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, ui
 int wgt_render_gbuffer_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
                              uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
                              const wgt_hit_buffers *d_out, float *d_rays, void *stream);
+
+/* The G-buffer of a sampled frame: sample 0's jitter is -0.5 + rand / k, so it depends on the pixel's
+ * side, and the record needs the frame's sample map to keep prim equal to the sampled render's
+ * hit_id_out bit for bit.  A pixel with k = 0 gets the miss record and a zero ray.  Otherwise as
+ * wgt_render_gbuffer and wgt_render_gbuffer_async; the map and the order of checks as
+ * wgt_render_tile_sampled (HOST map) and wgt_render_tiles_sampled_async (DEVICE map): the NULL map
+ * is checked last. */
+int wgt_render_gbuffer_sampled(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                               uint32_t x0, uint32_t y0, uint32_t tw, uint32_t th, const uint8_t *sample_map,
+                               const wgt_hit_buffers *out, float *rays_out);
+int wgt_render_gbuffer_sampled_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
+                                     uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
+                                     const uint8_t *d_sample_map, const wgt_hit_buffers *d_out, float *d_rays,
+                                     void *stream);
 
 /* ---- denoising (no reference counterpart) --------------------------------- */
 /* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered W x H image, guided
@@ -596,6 +636,50 @@ int wgt_denoise_variance_async(wgt_ctx *ctx, const wgt_denoise_variance_params *
                                const wgt_temporal_state *d_state, const wgt_hit_buffers *d_guides,
                                void *d_workspace, size_t workspace_bytes, float *d_rgba32f_out, void *d_rgba8_out,
                                float *d_variance_out, void *stream);
+
+/* ---- planning a sample map from the accumulated state (no reference counterpart) ---- */
+/* The next frame's sample map from what wgt_temporal_accumulate knows about this one: a pixel whose
+ * history is at least min_history long wants ceil(gain * sqrt(max0(m2 - m1^2)) / (|m1| + lum_floor))
+ * sides, clamped to [side_min, side_max]; a pixel the accumulation passes through (len = 0: lights,
+ * misses, NaN) wants side_min; every other pixel (a short history, moments beyond 2^100) wants
+ * side_max.  The wanted sides are dilated (the maximum within `dilate` pixels in x and y, in-image
+ * pixels only), and a budget caps them: with B = floor(budget_spp * W * H), the map is min(dilated, c)
+ * for the largest c in [side_min, side_max] whose sum of squares is at most B (c = side_min when not
+ * even that fits, so the budget can then be exceeded).  DESIGN.md §4.11 states the arithmetic
+ * operation by operation; tests/sample_plan_restatement.py is the same in numpy, and the map and its
+ * total equal it bit for bit.  Nothing is summed in floating point across pixels: the cap comes from
+ * a 256-bin integer histogram, so the result does not depend on the order of waves. */
+typedef struct {
+  uint32_t side_min;    /* 0..255 (default 1): every pixel gets at least this */
+  uint32_t side_max;    /* side_min..255 (default 8): ... and at most this */
+  float gain;           /* finite, > 0 (default 12.0): sides per unit of relative standard deviation */
+  float lum_floor;      /* finite, > 0 (default 1.0): added to |m1| before dividing */
+  uint32_t min_history; /* 1..64 (default 4): a shorter history is unknown and wants side_max */
+  uint32_t dilate;      /* 0..3 (default 2): radius of the max filter over the wanted sides */
+  float budget_spp;     /* finite, >= 0 (default 0 = none): the map's mean of k * k may not exceed this */
+} wgt_sample_plan_params; /* 28 bytes */
+int wgt_sample_plan_defaults(wgt_sample_plan_params *out);
+/* Bytes of device scratch wgt_sample_plan_async needs for a W x H image (a multiple of 256: one per
+ * pixel and the histogram); 0 for a size it refuses. */
+size_t wgt_sample_plan_workspace_bytes(uint32_t W, uint32_t H);
+/* state: what wgt_temporal_accumulate wrote for these W x H pixels; len and moments are required,
+ * rgba32f is not read.  map_out: W x H bytes.  total_out (may be NULL): the map's sum of k * k, the
+ * paths a sampled frame with it traces.  params NULL = the defaults.  No scene is needed; the library
+ * keeps no state.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context; NULL state;
+ * a NULL state->len or state->moments; a NULL map_out; W or H 0 or above 32768, or W * H above 2^25;
+ * parameters out of range, in the struct's order (NaN is refused); (async) NULL workspace, one not
+ * 256-byte aligned, workspace_bytes below wgt_sample_plan_workspace_bytes(W, H).
+ * Synchronous, HOST pointers; allocates and frees its own device workspace. */
+int wgt_sample_plan(wgt_ctx *ctx, const wgt_sample_plan_params *params, uint32_t W, uint32_t H,
+                    const wgt_temporal_state *state, uint8_t *map_out, uint64_t *total_out);
+/* DEVICE pointers (the state a host struct of device pointers), ordered on `stream` (NULL = the
+ * context's), returns once queued: the cap is chosen on the device and applied in a second pass, so a
+ * sampled render queued behind it on the same stream reads the finished map.  The state is never
+ * written.  The workspace is the caller's and holds nothing between calls.  d_total_out is 8-byte aligned. */
+int wgt_sample_plan_async(wgt_ctx *ctx, const wgt_sample_plan_params *params, uint32_t W, uint32_t H,
+                          const wgt_temporal_state *d_state, void *d_workspace, size_t workspace_bytes,
+                          uint8_t *d_map_out, uint64_t *d_total_out, void *stream);
 
 int wgt_sync(wgt_ctx *ctx);
 /* Diagnostics: the kernels' short sqrt / division forms (wgt_math.h sqrt_rn,

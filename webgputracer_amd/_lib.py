@@ -72,6 +72,13 @@ class WgtMotionBuffers(ctypes.Structure):
     _fields_ = [("pos_prev", ctypes.c_void_p), ("norm_prev", ctypes.c_void_p)]
 
 
+class WgtSamplePlanParams(ctypes.Structure):
+    """wgt_sample_plan_params (28 bytes); wgt_sample_plan_defaults fills the defaults."""
+    _fields_ = [("side_min", ctypes.c_uint32), ("side_max", ctypes.c_uint32), ("gain", ctypes.c_float),
+                ("lum_floor", ctypes.c_float), ("min_history", ctypes.c_uint32), ("dilate", ctypes.c_uint32),
+                ("budget_spp", ctypes.c_float)]
+
+
 class WgtStats(ctypes.Structure):
     _fields_ = [("queries", ctypes.c_uint64), ("traced_rays", ctypes.c_uint64), ("samples", ctypes.c_uint64),
                 ("nan_rays", ctypes.c_uint64), ("node_visits", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64),
@@ -125,6 +132,9 @@ EXPORTS = [
     "wgt_denoise_variance_async",
     "wgt_motion_snapshot", "wgt_motion_snapshot_read", "wgt_motion_reproject", "wgt_motion_reproject_async",
     "wgt_temporal_accumulate_motion", "wgt_temporal_accumulate_motion_async",
+    "wgt_render_tile_sampled", "wgt_render_tiles_sampled_async", "wgt_render_gbuffer_sampled",
+    "wgt_render_gbuffer_sampled_async",
+    "wgt_sample_plan_defaults", "wgt_sample_plan_workspace_bytes", "wgt_sample_plan", "wgt_sample_plan_async",
 ]
 
 _lib = None
@@ -224,6 +234,17 @@ def lib():
                                                      ctypes.POINTER(WgtHitBuffers), ctypes.POINTER(WgtMotionBuffers),
                                                      ctypes.POINTER(WgtTemporalState), ctypes.POINTER(WgtHitBuffers),
                                                      ctypes.POINTER(WgtTemporalState), P, P]),
+        "wgt_render_tile_sampled": (I, [P, P, U32, U32, U32, U32, U32, U32, P, P, P, P, P]),
+        "wgt_render_tiles_sampled_async": (I, [P, P, U32, U32, U32, U32, P, U32, P, P, P, P, P]),
+        "wgt_render_gbuffer_sampled": (I, [P, P, U32, U32, U32, U32, U32, U32, P, ctypes.POINTER(WgtHitBuffers), P]),
+        "wgt_render_gbuffer_sampled_async": (I, [P, P, U32, U32, U32, U32, P, U32, P, ctypes.POINTER(WgtHitBuffers), P,
+                                                 P]),
+        "wgt_sample_plan_defaults": (I, [ctypes.POINTER(WgtSamplePlanParams)]),
+        "wgt_sample_plan_workspace_bytes": (ctypes.c_size_t, [U32, U32]),
+        "wgt_sample_plan": (I, [P, ctypes.POINTER(WgtSamplePlanParams), U32, U32, ctypes.POINTER(WgtTemporalState), P,
+                                ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_sample_plan_async": (I, [P, ctypes.POINTER(WgtSamplePlanParams), U32, U32,
+                                      ctypes.POINTER(WgtTemporalState), P, ctypes.c_size_t, P, P, P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -139,6 +139,8 @@ DevFrame make_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H) {
   // the full 50-bounce tail set the pre-pass's own drain): sponza +0.4%, bunny +0.7%, the frame
   // alone -0.6% against full paths, 3 rounds on one box (profiles/sweeps/r04_pq_depth.log)
   fr.pq_depth = std::min<uint32_t>(std::max<uint32_t>(env_u32("WGT_PQ_DEPTH", 6), 1u), (uint32_t)kRayDepth);
+  // sampled frames: the pre-pass's cost of a pixel of side k > pq_lpt scaled to its k^2 samples
+  fr.pq_lpt_weight = env_u32("WGT_PQ_LPT_WEIGHT", 1);
   fr.pq_lpt_all = env_u32("WGT_PQ_LPT_ALL", 1);  // sweep: all pixels -3% (sponza), -4% (bunny) at 256 spp
   return fr;
 }
@@ -578,6 +580,92 @@ std::string check_motion_reproject_args(bool has_snapshot, uint32_t n, const wgt
   if (n < 1 || n > kMotionMaxRecords)
     return "n " + std::to_string(n) + " is not in 1.." + std::to_string(kMotionMaxRecords);
   return "";
+}
+
+wgt_camera_param sampled_camera(const wgt_camera_param& cam) {
+  wgt_camera_param c = cam;
+  c.spp = 1u;
+  return c;
+}
+
+const char* check_sample_map(const void* map) { return map ? nullptr : "null sample map"; }
+
+void sample_constants(float (*out)[4]) {
+  for (uint32_t k = 0; k < kSampleBins; ++k) {
+    const uint32_t spp = k * k;  // make_frame's expressions for camera.spp = k * k
+    out[k][0] = 1.0f / __builtin_sqrtf((float)spp);
+    out[k][1] = (float)spp;
+    out[k][2] = pow2_recip(spp);
+    out[k][3] = 0.0f;
+  }
+}
+
+wgt_sample_plan_params sample_plan_defaults() { return wgt_sample_plan_params{1u, 8u, 12.0f, 1.0f, 4u, 2u, 0.0f}; }
+
+size_t sample_plan_workspace_bytes(uint32_t W, uint32_t H) {
+  if (!denoise_size_ok(W, H)) return 0;
+  return align_up((size_t)W * H, kDenoiseAlign) + align_up((kSampleBins + 1) * sizeof(uint32_t), kDenoiseAlign);
+}
+
+std::string check_sample_plan_args(const wgt_sample_plan_params* params, uint32_t W, uint32_t H,
+                                   const wgt_temporal_state* state, const void* map_out) {
+  if (!state) return "null state";
+  if (!state->len) return "null state.len";
+  if (!state->moments) return "null state.moments";
+  if (!map_out) return "null map_out";
+  if (!denoise_size_ok(W, H))
+    return "image size " + std::to_string(W) + " x " + std::to_string(H) + ": W and H must be 1.." +
+           std::to_string(kDenoiseMaxDim) + " and W * H at most " + std::to_string(kDenoiseMaxPixels);
+  if (params) {
+    if (params->side_min > kSampleSideMax)
+      return "params.side_min " + std::to_string(params->side_min) + " is not in 0.." + std::to_string(kSampleSideMax);
+    if (params->side_max < params->side_min || params->side_max > kSampleSideMax)
+      return "params.side_max " + std::to_string(params->side_max) + " is not in side_min.." + std::to_string(kSampleSideMax);
+    if (!(params->gain > 0.0f) || !std::isfinite(params->gain)) return "params.gain must be finite and > 0";
+    if (!(params->lum_floor > 0.0f) || !std::isfinite(params->lum_floor)) return "params.lum_floor must be finite and > 0";
+    if (params->min_history < 1 || params->min_history > kSamplePlanMaxHistory)
+      return "params.min_history " + std::to_string(params->min_history) + " is not in 1.." +
+             std::to_string(kSamplePlanMaxHistory);
+    if (params->dilate > kSamplePlanMaxDilate)
+      return "params.dilate " + std::to_string(params->dilate) + " is not in 0.." + std::to_string(kSamplePlanMaxDilate);
+    if (!(params->budget_spp >= 0.0f) || !std::isfinite(params->budget_spp)) return "params.budget_spp must be finite and >= 0";
+  }
+  return "";
+}
+
+std::string check_sample_plan_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H) {
+  if (!ws) return "null workspace";
+  if (!aligned_to(ws, kDenoiseAlign)) return "misaligned workspace: it must be 256-byte aligned";
+  const size_t need = sample_plan_workspace_bytes(W, H);
+  if (ws_bytes < need)
+    return "workspace_bytes " + std::to_string(ws_bytes) + " is below the " + std::to_string(need) +
+           " that wgt_sample_plan_workspace_bytes asks for";
+  return "";
+}
+
+SamplePlan plan_sample_plan(const wgt_sample_plan_params& params, uint32_t W, uint32_t H) {
+  SamplePlan p{};
+  p.W = W; p.H = H;
+  p.side_min = params.side_min; p.side_max = params.side_max; p.dilate = params.dilate;
+  p.side_min_f = (float)params.side_min; p.side_max_f = (float)params.side_max;
+  p.gain = params.gain; p.lum_floor = params.lum_floor;
+  p.min_history = (float)params.min_history;
+  p.budgeted = params.budget_spp > 0.0f ? 1u : 0u;
+  // a float times W * H <= 2^25 is exact in double up to its own rounding; beyond 2^64 every map fits
+  const double b = std::floor((double)params.budget_spp * (double)W * (double)H);
+  p.budget = b >= 18446744073709551616.0 ? ~(uint64_t)0 : (uint64_t)b;
+  p.off_want = 0;
+  p.off_bins = align_up((size_t)W * H, kDenoiseAlign);
+  p.bytes = p.off_bins + align_up((kSampleBins + 1) * sizeof(uint32_t), kDenoiseAlign);
+  return p;
+}
+
+uint32_t sample_plan_cap(const SamplePlan& p, const uint32_t* bins, uint64_t& total) {
+  uint32_t c = p.side_max;
+  if (p.budgeted)
+    while (c > p.side_min && sample_plan_total(bins, c) > p.budget) --c;  // side_min when not even it meets the budget
+  total = sample_plan_total(bins, c);
+  return c;
 }
 
 TemporalCam temporal_camera(const wgt_camera_param& cam, uint32_t W, uint32_t H) {

@@ -11,6 +11,7 @@
 #include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
 #include "../wgt_motion.h"
+#include "../wgt_sample_plan.h"
 #include "../wgt_temporal.h"
 #include "bvh.h"
 
@@ -173,6 +174,35 @@ std::string check_motion_reproject_args(bool has_snapshot, uint32_t n, const wgt
 // Of arguments that passed the checks (cam_prev null: the first-frame form): each camera's
 // projection constants in the fp32 operations of the specification, from make_frame.
 TemporalCam temporal_camera(const wgt_camera_param& cam, uint32_t W, uint32_t H);
+// The sampled renders and G-buffers (wgt_render_tile_sampled and the like).  Their
+// checks are the plain calls' in the plain calls' order with the camera's spp taken as 1
+// (sampled_camera: cam->spp is ignored), then this one: a null sample map.  A map value cannot be
+// out of range: a side is one uint8_t.
+wgt_camera_param sampled_camera(const wgt_camera_param& cam);
+const char* check_sample_map(const void* map);
+// The table of each side's constants that the sampled kernels read (SampleArgs::tab), kSampleBins
+// rows of (recip_sqrt_spp, fspp, inv_fspp, 0): make_frame's own expressions for spp = k * k, so the
+// bits are the host's for that spp.
+void sample_constants(float (*out)[4]);
+
+// The sample-map planner (wgt_sample_plan, wgt_sample_plan_async).  Its defaults; its
+// workspace in bytes, 0 for a size the calls refuse; and the calls' checks after the context, in their
+// order, each returning the refusal's text, empty when fine: null state; a null state->len or
+// state->moments; a null map; the size (the denoisers' limits); the parameters (null: the defaults;
+// NaN is refused) in the struct's order; then of the async form the workspace: null, alignment, size.
+// No pointer is dereferenced but the structs' own.
+wgt_sample_plan_params sample_plan_defaults();
+size_t sample_plan_workspace_bytes(uint32_t W, uint32_t H);
+std::string check_sample_plan_args(const wgt_sample_plan_params* params, uint32_t W, uint32_t H,
+                                   const wgt_temporal_state* state, const void* map_out);
+std::string check_sample_plan_workspace(const void* ws, size_t ws_bytes, uint32_t W, uint32_t H);
+// Of arguments that passed the checks: the parameters as the kernels compare them, the budget
+// B = floor(budget_spp * W * H) in double (saturated at 2^64 - 1), and the workspace layout.
+SamplePlan plan_sample_plan(const wgt_sample_plan_params& params, uint32_t W, uint32_t H);
+// The budget rule on a histogram of the dilated sides (what k_sp_cap computes on the device): the
+// largest cap c in [side_min, side_max] whose total (sample_plan_total) is at most the budget,
+// side_min when none is; side_max without a budget.  total: the map's sum of k^2 under that cap.
+uint32_t sample_plan_cap(const SamplePlan& plan, const uint32_t* bins, uint64_t& total);
 TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
                            const wgt_camera_param* cam_prev);
 

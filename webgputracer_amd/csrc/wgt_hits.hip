@@ -55,21 +55,24 @@ k_trace_hits(DevScene sc, const float* __restrict__ rays, uint32_t n, wgt_hit_bu
 // A pixel without samples (sqrt_spp = 0) gets hit_init's record (write_pixel's kNoHit) and
 // a zero ray; a pixel of a tile outside the frame is not written, as the render leaves it.
 // n = n_tiles * tw * th records, pixel offset po (slot_setup).
-template <bool TRIS>
+// SM: the G-buffer of a sampled frame (SampleArgs, the last kernel argument): sample 0's jitter depends on the pixel's
+// side, which slot_setup takes from the map as the sampled render does; a pixel of side 0 is a
+// pixel without samples.
+template <bool TRIS, bool SM = false>
 __global__ void __launch_bounds__(kBlock)
 k_gbuffer(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, wgt_hit_buffers out,
-          float* __restrict__ rays) {
+          float* __restrict__ rays, SampleArgs sm) {
   extern __shared__ int s_stack[];  // sc.stack entries per lane (stack_lds_bytes)
   uint32_t po;
   Pixel px;
-  if (!slot_setup(fr, tiles, blockIdx.x, threadIdx.x, po, px)) return;  // one pixel per lane
+  if (!slot_setup<SM>(fr, tiles, blockIdx.x, threadIdx.x, po, px, sm)) return;  // one pixel per lane
   const size_t n = (size_t)fr.n_tiles * fr.tw * fr.th;
   f3 ro{0.0f, 0.0f, 0.0f}, rd{0.0f, 0.0f, 0.0f};
   Hit h;
-  if (px_done(fr, px)) {
+  if (px_done<SM>(fr, px)) {
     hit_init(h);
   } else {
-    camera_ray(fr, px, ro, rd);
+    camera_ray<SM>(fr, px, ro, rd, sm);
     closest_hit<TRIS, true>(sc, ro, rd, s_stack + threadIdx.x, h);
   }
   store_hit(out, n, po, h);
@@ -93,15 +96,16 @@ hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n
   return hipGetLastError();
 }
 
-hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
+hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                           const wgt_hit_buffers& out, float* d_rays, hipStream_t stream) {
   uint32_t blocks;
   DevFrame fm;  // + slot_setup's division multipliers
   const hipError_t eg = tile_grid(fr, blocks, fm);
   if (eg != hipSuccess || blocks == 0) return eg;
   const dim3 grid(blocks), block(kBlock);
-  (sc.n_tris > 0 ? k_gbuffer<true> : k_gbuffer<false>)
-      <<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, fm, d_tiles, out, d_rays);
+  (sm.map ? (sc.n_tris > 0 ? k_gbuffer<true, true> : k_gbuffer<false, true>)
+           : (sc.n_tris > 0 ? k_gbuffer<true> : k_gbuffer<false>))
+      <<<grid, block, stack_lds_bytes(sc.stack), stream>>>(sc, fm, d_tiles, out, d_rays, sm);
   return hipGetLastError();
 }
 

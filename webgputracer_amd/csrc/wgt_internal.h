@@ -158,6 +158,9 @@ struct DevFrame {
   uint32_t pq_lpt_all;  // the pre-pass renders all 64 pixels of each block (else the 16 at even x, y)
   uint32_t pq_svc_cost;  // pre-pass work units per ray started (a service iteration ~ 7 traversal steps)
   uint32_t pq_depth;     // the pre-pass's paths end at this depth (kRayDepth: the full path)
+  // sampled launches: the pre-pass, which renders min(k, pq_lpt)^2 samples of a pixel of side k,
+  // scales the pixel's work by k^2 / min(k, pq_lpt)^2 (1, the default) or leaves it (0)
+  uint32_t pq_lpt_weight;
   const uint32_t* perm;
   uint32_t* cost;
   // parked k_render_ps (DevScene::ps_park): the global part of the lanes' stacks, entry e
@@ -167,6 +170,20 @@ struct DevFrame {
   // (2^32 - 1) / d for the 8x8 blocks per tile row (bx) and per tile (bx * by) of the launch
   // (launch_render, launch_gbuffer): slot_setup's divisions by them (wgt_pixel.h tile_grid, udiv_by)
   uint32_t div_bx, div_bpt;
+};
+// DevFrame keeps its size: the instrumented parked 5-wave kernel allocated one more VGPR when the
+// kernel arguments behind the frame moved by 16 bytes, so what the sampled
+// kernels need comes as a last kernel argument of its own
+static_assert(sizeof(DevFrame) == 176, "the kernel arguments after the frame keep their offsets");
+
+// The sampled launches' own kernel argument, the last one (the SM instantiations; no other kernel
+// reads it): the frame's sample map, one side k per pixel of the W x H frame, row-major, and the
+// context's table of each side's constants, tab[k] = (recip_sqrt_spp, fspp, inv_fspp, 0) of
+// spp = k^2 (host/launch_plan.h sample_constants).  map != null selects the sampled kernels
+// (launch_render, launch_gbuffer); DevFrame::sqrt_spp and its three uniform constants are then not read.
+struct SampleArgs {
+  const uint8_t* map;
+  const float4* tab;
 };
 
 enum {
@@ -214,7 +231,8 @@ enum {
 size_t render_ws_bytes(const DevScene& sc, const DevFrame& fr, uint32_t resident);
 // ws_clean_nb: in, the block count whose queues and costs the workspace's previous LPT launch left
 // zero (0: unknown, a memset clears them); out, the same for this launch
-hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
+// sm: the sampled frame's map and table (sm.map null: the plain kernels, at fr's uniform spp)
+hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                          uchar4* out8, float4* out32, uint32_t* outhit,
                          unsigned long long* counters, uint32_t resident, void* ws, size_t ws_cap,
                          hipStream_t stream, uint32_t& ws_clean_nb);
@@ -240,7 +258,8 @@ hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n
                              hipStream_t stream);
 // The record of sample 0's camera ray of every pixel of the tile list (k_gbuffer; fr as
 // launch_render's), at the render's pixel offsets; d_rays (may be null) receives those rays.
-hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
+// sm as launch_render's: the G-buffer of a sampled frame needs its map (sample 0's jitter depends on the side).
+hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                           const wgt_hit_buffers& out, float* d_rays, hipStream_t stream);
 
 // The scene limits of coordinates and of triangle edge components (host/launch_plan.h states why),

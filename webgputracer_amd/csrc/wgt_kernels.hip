@@ -43,15 +43,18 @@
 
 namespace wgt {
 
-template <bool TRIS, bool STATS>
+// SM (both kernels): the sampled form.  A pixel takes its side from the frame's sample map (the
+// last kernel argument, SampleArgs) where it is set up and keeps it per lane (wgt_pixel.h Pixel):
+// pixel (x, y) of side k is invocation (x, y) of compute_sample with camera.spp = k^2.
+template <bool TRIS, bool STATS, bool SM = false>
 __global__ void __launch_bounds__(kBlock)
 k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* __restrict__ out8,
          float4* __restrict__ out32, uint32_t* __restrict__ outhit,
-         unsigned long long* __restrict__ counters) {
+         unsigned long long* __restrict__ counters, SampleArgs sm) {
   extern __shared__ int s_stack[];  // sc.stack entries per lane (stack_lds_bytes)
   uint32_t po;
   Pixel px;
-  if (!slot_setup(fr, tiles, blockIdx.x, threadIdx.x, po, px)) return;  // one pixel per lane
+  if (!slot_setup<SM>(fr, tiles, blockIdx.x, threadIdx.x, po, px, sm)) return;  // one pixel per lane
   int* lds = s_stack + threadIdx.x;
   const Light L{xyz(sc.quads[0]), xyz(sc.quads[1]), xyz(sc.quads[2])};
   const uint32_t nsamp = fr.sqrt_spp * fr.sqrt_spp;
@@ -59,17 +62,18 @@ k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* _
   int depth = 0;
   TravStats st{};
   Counters c{0u, 0u, 0u, 0u, 0u, 0u, 1u};  // one pixel per lane
+  const unsigned long long smp = SM ? px_side<SM>(fr, px) * px_side<SM>(fr, px) : 0u;  // this pixel's samples
 
-  while (!px_done(fr, px)) {
+  while (!px_done<SM>(fr, px)) {
     if (STATS) simt_count(c.lw, c.ll);
     if (depth == 0) {
-      camera_ray(fr, px, ro, rd);
+      camera_ray<SM>(fr, px, ro, rd, sm);
       pc = f3{1.0f, 1.0f, 1.0f};
     }
     const bool nanray = has_nan(ro) || has_nan(rd);
     if (nanray && !sc.last_sphere_emissive) {
-      first_hit(px, depth, last_prim(sc), po, outhit);
-      skip_nan_path<STATS>(sc, fr, px, depth, c);
+      first_hit<SM>(px, depth, last_prim(sc), po, outhit);
+      skip_nan_path<STATS, SM>(sc, fr, px, depth, c);
       depth = 0;
       continue;
     }
@@ -79,16 +83,16 @@ k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* _
       ++c.q;
       if (nanray) ++c.nan; else ++c.tr;
     }
-    first_hit(px, depth, h.prim, po, outhit);
+    first_hit<SM>(px, depth, h.prim, po, outhit);
     const bool end = shade(sc, L, h, depth, px.seed, ro, rd, pc);
     ++depth;
     if (end || depth == kRayDepth) {
-      end_sample(fr, px, pc);
+      end_sample<SM>(fr, px, pc, sm);
       depth = 0;
     }
   }
-  write_pixel(fr, po, px, out8, out32, outhit);
-  if (STATS) flush_counters(counters, c, st, nsamp);
+  write_pixel<SM>(fr, po, px, out8, out32, outhit);
+  if (STATS) flush_counters<SM>(counters, c, st, nsamp, smp);
 }
 
 // Phase-split kernel for scenes with triangles (see the file comment), persistent:
@@ -117,12 +121,20 @@ k_render(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* _
 // LDS words (Park) while the wave runs a service pass, and the LDS holds sc.ps_cap stack
 // entries per lane with the rest on a per-lane global stack (park_fix): the service code
 // then holds no traversal registers, which it used to spill to scratch.
-template <bool STATS, bool COST, int CN, int W, bool TRIS = true, bool PK = false>
+// FORM: the node form (0 = 128-B nodes, 1 = 80-B compact records), + kPsSampled for the sampled form
+// (SM).  The switch rides on this argument instead of being one more, so that the plain kernels keep
+// their names: profiles and the benchmark's counter passes find k_render_ps<..., 1, 6, true, false> by
+// its name, and a body shared by two entry points compiled five of the existing instantiations to
+// other register counts.
+constexpr int kPsSampled = 2;
+template <bool STATS, bool COST, int FORM, int W, bool TRIS = true, bool PK = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W)))
 k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4* __restrict__ out8,
             float4* __restrict__ out32, uint32_t* __restrict__ outhit,
             unsigned long long* __restrict__ counters, uint32_t* __restrict__ queue,
-            int* __restrict__ spill) {
+            int* __restrict__ spill, SampleArgs sm) {
+  constexpr int CN = FORM & 1;
+  constexpr bool SM = (FORM & kPsSampled) != 0;
   // spill: the global stacks (PK, DevFrame::ps_spill), a kernel argument of its own: a
   // noalias pointer, so its stores do not clobber the scene for the compiler, whose
   // wave-uniform loads (quads, spheres, the root node) stay scalar loads
@@ -160,6 +172,7 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
   uint32_t dq = 0;
   TravStats st{};
   Counters c{0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  unsigned long long smp = 0;  // SM, STATS: the samples of the pixels this lane finished
   // invariant: trav == !trav_done(t) (a lane leaves the traversal exactly when
   // trav_done turns true), so a lane with a node to visit or a pending leaf is
   // traversing; a lane starts done.  PK: t lives in registers only in the traversal
@@ -194,12 +207,20 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
       const uint64_t tr0 = STATS ? __builtin_amdgcn_s_memtime() : 0;
       if (fin) {  // a finished pixel: write it (here, outside the sample loop)
         if (COST) {
+          if (SM && fr.pq_lpt_weight) {
+            // the pixel was rendered at min(k, pq_lpt): its frame cost is k^2 / min(k, pq_lpt)^2 times
+            // that (an estimate; at most 2^25 per pixel, so that a block's 64 stay within 32 bits)
+            const float k = (float)(px.sij >> 24), r = (float)px_side<SM>(fr, px);
+            const float w = r > 0.0f ? (float)work * ((k * k) / (r * r)) : 0.0f;
+            work = (uint32_t)(w < 0x1p25f ? w : 0x1p25f);
+          }
           atomicAdd(fr.cost + pblock, work);
           work = 0;
         } else {
-          write_pixel(fr, po, px, out8, out32, outhit);
+          write_pixel<SM>(fr, po, px, out8, out32, outhit);
         }
         if (STATS) ++c.px;
+        if (SM && STATS) smp += px_side<SM>(fr, px) * px_side<SM>(fr, px);
         fin = false;
       }
       // refill: lanes without a pixel take consecutive slots, one atomic per wave
@@ -222,7 +243,7 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
               const uint32_t sb = quarter ? (slot >> 4) : (slot >> 6);
               const uint32_t sl = quarter ? (((slot & 3u) << 1) | (((slot >> 2) & 3u) << 4)) : (slot & 63u);
               const uint32_t b = fr.perm ? fr.perm[sb] : sb;
-              if (slot_setup(fr, tiles, b, sl, po, px)) {
+              if (slot_setup<SM>(fr, tiles, b, sl, po, px, sm, COST ? fr.pq_lpt : 255u)) {
                 have = true;
                 dq = 0u;
                 pblock = b;
@@ -272,13 +293,13 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
                        quad_rebuild(sc, ro, rd, (dq >> 6) - 1u, q_t, h); finish_hit(sc, ro, rd, bt, bi, h, TRIS ? pre : nullptr));
             if (STATS) { ++c.q; ++c.tr; }
           }
-          first_hit(px, (int)(dq & 63u), h.prim, po, outhit);
+          first_hit<SM>(px, (int)(dq & 63u), h.prim, po, outhit);
           const uint64_t ts0 = STATS ? __builtin_amdgcn_s_memtime() : 0;
           const bool end = shade(sc, L, h, (int)(dq & 63u), px.seed, ro, rd, pc);
           dq = (dq & 63u) + 1u;  // the quad is used: q_prim + 1 = 0
           // COST: the pre-pass's paths may end early (DevFrame::pq_depth): a cost estimate
           if (end || dq == (COST ? fr.pq_depth : (uint32_t)kRayDepth)) {
-            end_sample(fr, px, pc);
+            end_sample<SM>(fr, px, pc, sm);
             dq = 0u;
           }
           if (STATS) cr_shade += __builtin_amdgcn_s_memtime() - ts0;
@@ -286,19 +307,19 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
         }
         // start the next ray of this pixel
         if (!resume) for (;;) {
-          if (px_done(fr, px)) {
+          if (px_done<SM>(fr, px)) {
             have = false;
             fin = true;
             break;
           }
           if ((dq & 63u) == 0u) {
-            WGT_REGION(cr_cam, camera_ray(fr, px, ro, rd));
+            WGT_REGION(cr_cam, camera_ray<SM>(fr, px, ro, rd, sm));
             pc = f3{1.0f, 1.0f, 1.0f};
           }
           if (has_nan(ro) || has_nan(rd)) {
             if (!sc.last_sphere_emissive) {
-              first_hit(px, (int)(dq & 63u), last_prim(sc), po, outhit);
-              skip_nan_path<STATS>(sc, fr, px, (int)(dq & 63u), c);
+              first_hit<SM>(px, (int)(dq & 63u), last_prim(sc), po, outhit);
+              skip_nan_path<STATS, SM>(sc, fr, px, (int)(dq & 63u), c);
               dq = 0u;
               continue;
             }
@@ -412,7 +433,7 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
     if (STATS) cyc_trav += __builtin_amdgcn_s_memtime() - t_phase;
   }
   if (STATS) {
-    flush_counters(counters, c, st, nsamp);
+    flush_counters<SM>(counters, c, st, nsamp, smp);
     if (lane == 0) {
       atomicAdd(&counters[CNT_CYC_SERVICE], (unsigned long long)cyc_svc);
       atomicAdd(&counters[CNT_CYC_TRAV], (unsigned long long)cyc_trav);
@@ -468,18 +489,24 @@ k_lpt_order(uint32_t* __restrict__ cost, uint32_t blocks, uint32_t* __restrict__
 
 // The k_render_ps instantiation of a pass (STATS: counting, COST: the pre-pass) for the scene's
 // form and the frame's node form (node_form: 0 = 128-B nodes, 1 = 80-B compact records): the one
-// place that names them.  Scenes without triangles run the traversal-free instantiation.
+// place that names them.  Scenes without triangles run the traversal-free instantiation.  SM: the
+// sampled form of each (a frame with a sample map, SampleArgs).
 using PsKernel = void (*)(DevScene, DevFrame, const wgt_tile*, uchar4*, float4*, uint32_t*, unsigned long long*,
-                          uint32_t*, int*);
-template <bool STATS, bool COST>
+                          uint32_t*, int*, SampleArgs);
+template <bool STATS, bool COST, bool SM = false>
 PsKernel ps_kernel(const PsForm& f, int cn) {
-  if (!f.tris) return k_render_ps<STATS, COST, 0, kPsWavesNoTris, false>;
+#define WGT_PS(CN, W, TRIS, PK) k_render_ps<STATS, COST, (CN) | (SM ? kPsSampled : 0), W, TRIS, PK>
+  if (!f.tris) return WGT_PS(0, kPsWavesNoTris, false, false);
   static constexpr PsKernel k[2][2][2] = {  // [6 waves][parked][compact]
-      {{k_render_ps<STATS, COST, 0, 5, true, false>, k_render_ps<STATS, COST, 1, 5, true, false>},
-       {k_render_ps<STATS, COST, 0, 5, true, true>, k_render_ps<STATS, COST, 1, 5, true, true>}},
-      {{k_render_ps<STATS, COST, 0, 6, true, false>, k_render_ps<STATS, COST, 1, 6, true, false>},
-       {k_render_ps<STATS, COST, 0, 6, true, true>, k_render_ps<STATS, COST, 1, 6, true, true>}}};
+      {{WGT_PS(0, 5, true, false), WGT_PS(1, 5, true, false)}, {WGT_PS(0, 5, true, true), WGT_PS(1, 5, true, true)}},
+      {{WGT_PS(0, 6, true, false), WGT_PS(1, 6, true, false)}, {WGT_PS(0, 6, true, true), WGT_PS(1, 6, true, true)}}};
+#undef WGT_PS
   return k[f.waves == 6][f.park][cn != 0];
+}
+// ... by the frame: the sampled forms when it has a sample map
+template <bool STATS, bool COST>
+PsKernel ps_kernel(const PsForm& f, int cn, const SampleArgs& sm) {
+  return sm.map ? ps_kernel<STATS, COST, true>(f, cn) : ps_kernel<STATS, COST, false>(f, cn);
 }
 
 // The compact codes are exact for ray origins within their bound (the margin, wgt_geom.h):
@@ -507,7 +534,7 @@ size_t render_ws_bytes(const DevScene& sc, const DevFrame& fr, uint32_t resident
   return ((256 + 8 * bx * by * fr.n_tiles + 255) & ~(uint64_t)255) + ps_spill_bytes(sc, resident);
 }
 
-hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile* d_tiles,
+hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                          uchar4* out8, float4* out32, uint32_t* outhit,
                          unsigned long long* counters, uint32_t resident, void* ws, size_t ws_cap,
                          hipStream_t stream, uint32_t& ws_clean_nb) {
@@ -526,7 +553,9 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
     const dim3 grid(nb < resident ? nb : resident);
     // workspace (the context's, used in stream order): [0] pre-pass queue,
     // [1] queue | cost[nb] | perm[nb]
-    const bool lpt = fr.pq_lpt && fr.sqrt_spp > fr.pq_lpt;
+    // a sampled frame's sides are on the device: its pre-pass runs whenever LPT is on, each pixel
+    // at min(k, pq_lpt) (slot_setup's side_cap), so it never costs more than the frame
+    const bool lpt = fr.pq_lpt && (sm.map || fr.sqrt_spp > fr.pq_lpt);
     const int cn = node_form(sc, fr);
     uint32_t* q = (uint32_t*)ws;
     DevFrame f = fm;
@@ -552,14 +581,14 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
       fc.inv_fspp = pow2_recip(fc.sqrt_spp * fc.sqrt_spp);
       fc.cost = (uint32_t*)((char*)ws + 256);
       fc.n_slots = nb * (fr.pq_lpt_all ? 64u : 16u);  // by default a quarter of each block's pixels estimate its cost
-      ps_kernel<false, true>(form, cn)<<<grid, block, plds, stream>>>(sc, fc, d_tiles, nullptr, nullptr, nullptr, nullptr, q, fc.ps_spill);
+      ps_kernel<false, true>(form, cn, sm)<<<grid, block, plds, stream>>>(sc, fc, d_tiles, nullptr, nullptr, nullptr, nullptr, q, fc.ps_spill, sm);
       k_lpt_order<<<1, kLptThreads, 0, stream>>>(fc.cost, nb, fc.cost + nb, q);
       f.perm = fc.cost + nb;
       e = hipGetLastError();
     }
     if (e == hipSuccess) {
-      const PsKernel k = counters ? ps_kernel<true, false>(form, cn) : ps_kernel<false, false>(form, cn);
-      k<<<grid, block, plds, stream>>>(sc, f, d_tiles, out8, out32, outhit, counters, q + 1, f.ps_spill);
+      const PsKernel k = counters ? ps_kernel<true, false>(form, cn, sm) : ps_kernel<false, false>(form, cn, sm);
+      k<<<grid, block, plds, stream>>>(sc, f, d_tiles, out8, out32, outhit, counters, q + 1, f.ps_spill, sm);
       e = hipGetLastError();
     }
     // after an LPT launch k_lpt_order has left the queues and nb costs zero for the next one
@@ -567,10 +596,11 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const wgt_tile*
     return e;
   }
   const dim3 grid(blocks);
-  using Kernel = void (*)(DevScene, DevFrame, const wgt_tile*, uchar4*, float4*, uint32_t*, unsigned long long*);
-  static constexpr Kernel k[2][2] = {{k_render<false, false>, k_render<false, true>},  // [triangles][counting]
-                                     {k_render<true, false>, k_render<true, true>}};
-  k[sc.n_tris > 0][counters != nullptr]<<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, counters);
+  using Kernel = void (*)(DevScene, DevFrame, const wgt_tile*, uchar4*, float4*, uint32_t*, unsigned long long*, SampleArgs);
+  static constexpr Kernel k[2][2][2] = {  // [sampled][triangles][counting]
+      {{k_render<false, false>, k_render<false, true>}, {k_render<true, false>, k_render<true, true>}},
+      {{k_render<false, false, true>, k_render<false, true, true>}, {k_render<true, false, true>, k_render<true, true, true>}}};
+  k[sm.map != nullptr][sc.n_tris > 0][counters != nullptr]<<<grid, block, lds, stream>>>(sc, fm, d_tiles, out8, out32, outhit, counters, sm);
   return hipGetLastError();
 }
 

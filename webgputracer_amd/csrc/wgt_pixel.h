@@ -83,16 +83,30 @@ struct Pixel {
   uint32_t sij;  // the sample's s_i | s_j << 16 (sqrt_spp < 2^16); index = s_i + s_j * sqrt_spp
   f3 col;
 };
+// SM (the sampled kernels, SampleArgs): the pixel's side k (its sqrt_spp, <= 255) comes from
+// the sample map and lives in the same register: sij = s_i | s_j << 8 | k << 16 (s_i < k, s_j <= k
+// fit 8 bits each); the cost pre-pass renders min(k, pq_lpt) there and keeps the map's k in bits 24-31.
 // all sqrt_spp^2 samples done (sj reaches sqrt_spp; at once when spp = 0)
-__device__ __forceinline__ uint32_t px_si(const Pixel& px) { return px.sij & 0xffffu; }
-__device__ __forceinline__ uint32_t px_sj(const Pixel& px) { return px.sij >> 16; }
-__device__ __forceinline__ bool px_done(const DevFrame& fr, const Pixel& px) { return px_sj(px) >= fr.sqrt_spp; }
+template <bool SM = false>
+__device__ __forceinline__ uint32_t px_si(const Pixel& px) { return SM ? px.sij & 0xffu : px.sij & 0xffffu; }
+template <bool SM = false>
+__device__ __forceinline__ uint32_t px_sj(const Pixel& px) { return SM ? (px.sij >> 8) & 0xffu : px.sij >> 16; }
+// the pixel's sample-grid side
+template <bool SM = false>
+__device__ __forceinline__ uint32_t px_side(const DevFrame& fr, const Pixel& px) {
+  return SM ? (px.sij >> 16) & 0xffu : fr.sqrt_spp;
+}
+template <bool SM = false>
+__device__ __forceinline__ bool px_done(const DevFrame& fr, const Pixel& px) { return px_sj<SM>(px) >= px_side<SM>(fr, px); }
 // next (s_i, s_j) in the reference's loop order (path_tracer.wgsl:381-382)
+template <bool SM = false>
 __device__ __forceinline__ void px_next(const DevFrame& fr, Pixel& px) {
-  px.sij = px_si(px) + 1u == fr.sqrt_spp ? (px.sij & 0xffff0000u) + 0x10000u : px.sij + 1u;
+  if (SM) px.sij = px_si<SM>(px) + 1u == px_side<SM>(fr, px) ? (px.sij & 0xffffff00u) + 0x100u : px.sij + 1u;
+  else px.sij = px_si(px) + 1u == fr.sqrt_spp ? (px.sij & 0xffff0000u) + 0x10000u : px.sij + 1u;
 }
 // sample 0 (the one whose first hit is the pixel's hit ID)
-__device__ __forceinline__ bool px_first(const Pixel& px) { return px.sij == 0u; }
+template <bool SM = false>
+__device__ __forceinline__ bool px_first(const Pixel& px) { return SM ? (px.sij & 0xffffu) == 0u : px.sij == 0u; }
 
 struct Counters {
   uint32_t q, tr, nan, lw, ll;
@@ -130,8 +144,12 @@ inline hipError_t tile_grid(const DevFrame& fr, uint32_t& blocks, DevFrame& fm) 
 // 8x8 sub-block of tile b / (sub-blocks per tile).  false if the slot is outside
 // its tile or the frame.  po = the pixel's offset in the tile-major output
 // ((tile * th + ly) * tw + lx; the host keeps tiles * tw * th < 2^31).
+// SM: the pixel's side from the sample map (global pixel coordinates, row-major); side_cap: the
+// side the launch renders at most (255; the cost pre-pass: pq_lpt).
+template <bool SM = false>
 __device__ __forceinline__ bool slot_setup(const DevFrame& fr, const wgt_tile* __restrict__ tiles,
-                                           uint32_t block, uint32_t lane, uint32_t& po, Pixel& px) {
+                                           uint32_t block, uint32_t lane, uint32_t& po, Pixel& px,
+                                           const SampleArgs& sm = SampleArgs{}, uint32_t side_cap = 255u) {
   const uint32_t bx = (fr.tw + 7u) >> 3, by = (fr.th + 7u) >> 3;
   const uint32_t bpt = bx * by;
   // divisions by the host's multipliers (DevFrame::div_bx, div_bpt): no per-lane reciprocal kept
@@ -147,42 +165,58 @@ __device__ __forceinline__ bool slot_setup(const DevFrame& fr, const wgt_tile* _
   if (x >= fr.W || y >= fr.H) return false;  // path_tracer.wgsl:377
   px.xy = x | y << 16;
   px.seed = x + y * fr.W + td.seed * fr.W * fr.H;  // path_tracer.wgsl:378
-  px.sij = 0u;
+  if (SM) {
+    const uint32_t k = sm.map[(size_t)y * fr.W + x];
+    px.sij = (k < side_cap ? k : side_cap) << 16 | k << 24;
+  } else {
+    px.sij = 0u;
+  }
   px.col = f3{0.0f, 0.0f, 0.0f};
   po = (tile * fr.th + ly) * fr.tw + lx;
   return true;
 }
 
 // setup_camera_ray + pixel_sample_square (path_tracer.wgsl:232-262) for the sample (s_i, s_j) of px.sij
-__device__ __forceinline__ void camera_ray(const DevFrame& fr, Pixel& px, f3& ro, f3& rd) {
+template <bool SM = false>
+__device__ __forceinline__ void camera_ray(const DevFrame& fr, Pixel& px, f3& ro, f3& rd,
+                                           const SampleArgs& sm = SampleArgs{}) {
   const f3 origin = f3{fr.ox, fr.oy, fr.oz};
   const f3 du = f3{fr.dux, fr.duy, fr.duz};
   const f3 dv = f3{fr.dvx, fr.dvy, fr.dvz};
   const f3 pixel_center = (f3{fr.pox, fr.poy, fr.poz} + (float)(px.xy & 0xffffu) * du) + (float)(px.xy >> 16) * dv;
-  const float sx = -0.5f + fr.recip_sqrt_spp * ((float)px_si(px) + rand_next(px.seed));
-  const float sy = -0.5f + fr.recip_sqrt_spp * ((float)px_sj(px) + rand_next(px.seed));
+  // SM: the side's constants from the host's table (SampleArgs::tab), read per sample
+  const float rss = SM ? sm.tab[px_side<SM>(fr, px)].x : fr.recip_sqrt_spp;
+  const float sx = -0.5f + rss * ((float)px_si<SM>(px) + rand_next(px.seed));
+  const float sy = -0.5f + rss * ((float)px_sj<SM>(px) + rand_next(px.seed));
   const f3 pixel_sample = pixel_center + (sx * du + sy * dv);
   ro = origin;
   rd = pixel_sample - origin;
 }
 
 // col += max(path.col, 0) / f32(spp) (path_tracer.wgsl:393) and advance to the next sample
-__device__ __forceinline__ void end_sample(const DevFrame& fr, Pixel& px, f3 pc) {
+template <bool SM = false>
+__device__ __forceinline__ void end_sample(const DevFrame& fr, Pixel& px, f3 pc, const SampleArgs& sm = SampleArgs{}) {
   // x / 2^k == x * 2^-k exactly (one rounding of the same real value), so a
   // power-of-two spp multiplies
   const f3 m{max0(pc.x), max0(pc.y), max0(pc.z)};
-  px.col = px.col + (fr.inv_fspp != 0.0f ? fr.inv_fspp * m : m / fr.fspp);
-  px_next(fr, px);
+  if (SM) {
+    const float4 k = sm.tab[px_side<SM>(fr, px)];  // (recip_sqrt_spp, fspp, inv_fspp, 0) of this pixel's side
+    px.col = px.col + (k.z != 0.0f ? k.z * m : m / k.y);
+  } else {
+    px.col = px.col + (fr.inv_fspp != 0.0f ? fr.inv_fspp * m : m / fr.fspp);
+  }
+  px_next<SM>(fr, px);
 }
 
 // The pixel's hit ID (path_tracer.wgsl:384-386): the primitive of sample 0's camera ray.
+template <bool SM = false>
 __device__ __forceinline__ void first_hit(const Pixel& px, int depth, uint32_t prim, uint32_t po,
                                           uint32_t* __restrict__ outhit) {
-  if (outhit && depth == 0 && px_first(px)) outhit[po] = prim;
+  if (outhit && depth == 0 && px_first<SM>(px)) outhit[po] = prim;
 }
 
 // NaN-absorbed for the rest of the path: 3 rand() per remaining bounce, colour NaN.
-template <bool STATS>
+template <bool STATS, bool SM = false>
 __device__ __forceinline__ void skip_nan_path(const DevScene& sc, const DevFrame& fr, Pixel& px,
                                               int depth, Counters& c) {
   px.seed = lcg_jump(px.seed, 3u * (uint32_t)(kRayDepth - depth));
@@ -191,25 +225,27 @@ __device__ __forceinline__ void skip_nan_path(const DevScene& sc, const DevFrame
     c.nan += (uint32_t)(kRayDepth - depth);
   }
   // col += max(NaN, 0) / spp == col + 0
-  px_next(fr, px);
+  px_next<SM>(fr, px);
 }
 
+template <bool SM = false>
 __device__ __forceinline__ void write_pixel(const DevFrame& fr, uint32_t po, const Pixel& px, uchar4* out8,
                                             float4* out32, uint32_t* outhit) {
   if (out32) out32[po] = make_float4(px.col.x, px.col.y, px.col.z, 1.0f);
   if (out8) out8[po] = make_uchar4(unorm8(px.col.x), unorm8(px.col.y), unorm8(px.col.z), 255);
   // the hit ID is written when sample 0's first hit is known (first_hit); a
   // pixel without samples has none
-  if (outhit && fr.sqrt_spp == 0u) outhit[po] = kNoHit;
+  if (outhit && px_side<SM>(fr, px) == 0u) outhit[po] = kNoHit;
 }
 
+template <bool SM = false>
 __device__ __forceinline__ void flush_counters(unsigned long long* __restrict__ counters,
                                                const Counters& c, const TravStats& st,
-                                               uint32_t nsamp) {
-  // c.px pixels, nsamp samples each
+                                               uint32_t nsamp, unsigned long long smp = 0) {
+  // c.px pixels, nsamp samples each (SM: smp samples, the sum of the finished pixels' k^2)
   atomicAdd(&counters[CNT_QUERIES], (unsigned long long)c.q);
   atomicAdd(&counters[CNT_TRACED], (unsigned long long)c.tr);
-  atomicAdd(&counters[CNT_SAMPLES], (unsigned long long)nsamp * c.px);
+  atomicAdd(&counters[CNT_SAMPLES], SM ? smp : (unsigned long long)nsamp * c.px);
   atomicAdd(&counters[CNT_NAN], (unsigned long long)c.nan);
   atomicAdd(&counters[CNT_NODES], (unsigned long long)st.nodes);
   atomicAdd(&counters[CNT_TRIS], (unsigned long long)st.tris);

@@ -55,12 +55,15 @@ struct wgt_ctx {
   // slots; allocated by the first snapshot after an upload, dropped by the next upload
   DevBuf motion;
   bool has_snapshot = false;
+  // the sampled kernels' table of each side's constants (sample_constants), uploaded with the context
+  DevBuf sample_tab;
   // scratch for the synchronous entry points: the renders' tile list, outputs and counters; the
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
   // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
-  // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev
+  // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev;
+  // a sampled call's sample map
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -254,7 +257,8 @@ hipEvent_t pool_event(wgt_ctx* ctx, size_t i) {
 
 // Render the tile list: one launch of the persistent kernel (or, WGT_KERNEL=1, of the
 // simple one), asynchronous on stream s unless timed (ms: the launch's time, waited for).
-int render_frame(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, uchar4* out8, float4* out32,
+// sm: a sampled frame's map and table (sample_args), SampleArgs{} for a plain one.
+int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, uchar4* out8, float4* out32,
                  uint32_t* outhit, unsigned long long* counters, hipStream_t s, float* ms) {
   const uint64_t n64 = (uint64_t)fr.tw * fr.th * fr.n_tiles;
   if (n64 == 0) return WGT_OK;
@@ -283,7 +287,7 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, ucha
   if (!sl.ev) WGT_HIP(ctx, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
   else WGT_HIP(ctx, hipStreamWaitEvent(s, sl.ev, 0));
   {
-    const hipError_t e = launch_render(ctx->sc, fr, d_tiles, out8, out32, outhit, counters, ctx->ps_resident,
+    const hipError_t e = launch_render(ctx->sc, fr, sm, d_tiles, out8, out32, outhit, counters, ctx->ps_resident,
                                        sl.ws.p, sl.ws.bytes, s, sl.clean_nb);
     if (e != hipSuccess) {
       sl.clean_nb = 0;
@@ -299,6 +303,18 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, ucha
   return WGT_OK;
 }
 
+// The counting pass of a launch (the instrumented kernels) over the tile list d_tiles, read back.
+int count_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, wgt_stats* stats) {
+  int rc;
+  unsigned long long c[CNT_N], *d_c;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = render_frame(ctx, fr, sm, d_tiles, nullptr, nullptr, nullptr, d_c, ctx->stream, nullptr))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  fill_stats(c, stats);
+  return WGT_OK;
+}
+
 // The queries' launches on stream s; the asynchronous entry points are these behind their checks,
 // the synchronous ones stage their inputs, call the same, fetch and synchronise.
 int occluded_launch(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n, uint8_t* d_out,
@@ -309,12 +325,12 @@ int hits_launch(wgt_ctx* ctx, const float* d_rays, uint32_t n, const wgt_hit_buf
   return launch_on(ctx, s, "launch_trace_hits", [&] { return launch_trace_hits(ctx->sc, d_rays, n, dev, s); });
 }
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
-int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const wgt_tile* d_tiles, const wgt_hit_buffers& dev,
-                   float* d_rays, hipStream_t s) {
+int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
+                   const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
   // 32-bit pixel offsets in the kernels (slot_setup), as render_frame
   if ((uint64_t)fr.tw * fr.th * fr.n_tiles > 0x7fffffffull)
     return fail(ctx, WGT_E_INVALID, "too many pixels in one launch");
-  return launch_on(ctx, s, "launch_gbuffer", [&] { return launch_gbuffer(ctx->sc, fr, d_tiles, dev, d_rays, s); });
+  return launch_on(ctx, s, "launch_gbuffer", [&] { return launch_gbuffer(ctx->sc, fr, sm, d_tiles, dev, d_rays, s); });
 }
 
 // Device staging of n hit records for the fields `out` asks for (the synchronous forms).
@@ -393,6 +409,13 @@ int wgt_create(int hip_device, wgt_ctx** out) {
   if ((e = hipSetDevice(hip_device)) != hipSuccess) return cleanup("hipSetDevice", e);
   if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
     return cleanup("hipStreamCreate", e);
+  // the sampled kernels' constants, here so that no sampled call, asynchronous ones included, ever copies
+  float tab[kSampleBins][4];
+  sample_constants(tab);
+  if ((e = hipMalloc(&ctx->sample_tab.p, sizeof tab)) != hipSuccess) return cleanup("hipMalloc", e);
+  ctx->sample_tab.bytes = sizeof tab;
+  if ((e = hipMemcpy(ctx->sample_tab.p, tab, sizeof tab, hipMemcpyHostToDevice)) != hipSuccess)
+    return cleanup("hipMemcpy", e);
   *out = ctx;
   return WGT_OK;
 }
@@ -412,6 +435,7 @@ void wgt_destroy(wgt_ctx* ctx) {
   for (DevBuf& b : ctx->buf) free_buf(b);
   free_buf(ctx->level_order);
   free_buf(ctx->motion);
+  free_buf(ctx->sample_tab);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -762,7 +786,7 @@ int wgt_render_tiles_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W
                            void* d_rgba8, float* d_rgba32f, uint32_t* d_hit_id, void* stream) {
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, nullptr));
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
-  return render_frame(ctx, fr, d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
+  return render_frame(ctx, fr, SampleArgs{}, d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
                       stream_or_own(ctx, stream), nullptr);
 }
 
@@ -770,15 +794,7 @@ int wgt_render_tiles_stats(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W
                            uint32_t tw, uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles,
                            wgt_stats* stats) {
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, true, stats, nullptr));
-  int rc;
-  unsigned long long c[CNT_N], *d_c;
-  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
-  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
-  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
-  if ((rc = render_frame(ctx, fr, d_tiles, nullptr, nullptr, nullptr, d_c, ctx->stream, nullptr))) return rc;
-  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
-  fill_stats(c, stats);
-  return WGT_OK;
+  return count_frame(ctx, tile_frame(*cam, W, H, tw, th, n_tiles), SampleArgs{}, d_tiles, stats);
 }
 
 int wgt_render_tiles_profile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H,
@@ -788,7 +804,7 @@ int wgt_render_tiles_profile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t
   int rc;
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, d_tiles, nullptr, nullptr, nullptr, nullptr, ctx->stream, &ms))) return rc;
+  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, nullptr, nullptr, nullptr, nullptr, ctx->stream, &ms))) return rc;
   if ((rc = sync_stream(ctx))) return rc;
   fill_timing(ms, stats);
   return WGT_OK;
@@ -812,18 +828,37 @@ int wgt_render_frames(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uin
   if ((rc = stage(ctx, wgt_ctx::kTiles, tl.data(), n_frames * sizeof(wgt_tile), d_tiles))) return rc;
   const DevFrame fr = tile_frame(*cam, W, H, W, H, n_frames);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, d_tiles, d_out8, nullptr, nullptr, nullptr, ctx->stream, stats ? &ms : nullptr)))
+  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, d_out8, nullptr, nullptr, nullptr, ctx->stream, stats ? &ms : nullptr)))
     return rc;
   if ((rc = fetch(ctx, rgba8_out, d_out8, npx * n_frames * 4)) || (rc = sync_stream(ctx))) return rc;
   return stats ? stats_of_render(ctx, cam, W, H, W, H, n_frames, ms, stats) : WGT_OK;
 }
 
-int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0,
-                    uint32_t y0, uint32_t tw, uint32_t th, uint8_t* rgba8_out, float* rgba32f_out,
-                    uint32_t* hit_id_out, wgt_stats* stats) {
+}  // extern "C"
+
+namespace {
+
+// The sampled calls' map and the context's table for the kernels.
+SampleArgs sample_args(const wgt_ctx* ctx, const uint8_t* d_map) {
+  return SampleArgs{d_map, (const float4*)ctx->sample_tab.p};
+}
+
+// wgt_render_tile, and with a host sample map (sampled) wgt_render_tile_sampled: the map is checked
+// last and staged on the context's stream; the camera's spp is then taken as 1.
+int render_tile(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0,
+                uint32_t tw, uint32_t th, bool sampled, const uint8_t* sample_map, uint8_t* rgba8_out,
+                float* rgba32f_out, uint32_t* hit_id_out, wgt_stats* stats) {
+  wgt_camera_param c1;
+  const wgt_camera_param* cam = cam_in;
+  if (sampled && ctx && cam_in) {
+    c1 = sampled_camera(*cam_in);
+    cam = &c1;
+  }
   int rc = check_render_args(ctx, cam, W, H, tw, th);
   if (rc) return rc;
   if (x0 >= W || y0 >= H) return fail(ctx, WGT_E_INVALID, "tile origin outside the frame");
+  if (sampled)
+    if (const char* bad = check_sample_map(sample_map)) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t npx = (size_t)tw * th;
   const wgt_tile tile{x0, y0, cam->seed, 0u};
@@ -831,6 +866,12 @@ int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint3
   float4* d_out32 = nullptr;
   uint32_t* d_hit = nullptr;
   const wgt_tile* d_tile;
+  SampleArgs sm{};
+  if (sampled) {
+    const uint8_t* d_map;
+    if ((rc = stage(ctx, wgt_ctx::kSampleMap, sample_map, (size_t)W * H, d_map))) return rc;
+    sm = sample_args(ctx, d_map);
+  }
   if (rgba8_out && (rc = scratch(ctx, wgt_ctx::kOut8, npx * 4, d_out8))) return rc;
   if (rgba32f_out && (rc = scratch(ctx, wgt_ctx::kOut32, npx * 16, d_out32))) return rc;
   if (hit_id_out && (rc = scratch(ctx, wgt_ctx::kHit, npx * 4, d_hit))) return rc;
@@ -844,13 +885,48 @@ int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint3
   }
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, 1);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, d_tile, d_out8, d_out32, d_hit, nullptr, ctx->stream, stats ? &ms : nullptr)))
+  if ((rc = render_frame(ctx, fr, sm, d_tile, d_out8, d_out32, d_hit, nullptr, ctx->stream, stats ? &ms : nullptr)))
     return rc;
   if (d_out8 && (rc = fetch(ctx, rgba8_out, d_out8, npx * 4))) return rc;
   if (d_out32 && (rc = fetch(ctx, rgba32f_out, d_out32, npx * 16))) return rc;
   if (d_hit && (rc = fetch(ctx, hit_id_out, d_hit, npx * 4))) return rc;
   if ((rc = sync_stream(ctx))) return rc;
-  return stats ? stats_of_render(ctx, cam, W, H, tw, th, 1, ms, stats) : WGT_OK;
+  if (!stats) return WGT_OK;
+  if (!sampled) return stats_of_render(ctx, cam, W, H, tw, th, 1, ms, stats);
+  std::memset(stats, 0, sizeof *stats);
+  if ((rc = count_frame(ctx, fr, sm, d_tile, stats))) return rc;
+  fill_timing(ms, stats);
+  return WGT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wgt_render_tile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0,
+                    uint32_t y0, uint32_t tw, uint32_t th, uint8_t* rgba8_out, float* rgba32f_out,
+                    uint32_t* hit_id_out, wgt_stats* stats) {
+  return render_tile(ctx, cam, W, H, x0, y0, tw, th, false, nullptr, rgba8_out, rgba32f_out, hit_id_out, stats);
+}
+
+int wgt_render_tile_sampled(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0,
+                            uint32_t y0, uint32_t tw, uint32_t th, const uint8_t* sample_map, uint8_t* rgba8_out,
+                            float* rgba32f_out, uint32_t* hit_id_out, wgt_stats* stats) {
+  return render_tile(ctx, cam, W, H, x0, y0, tw, th, true, sample_map, rgba8_out, rgba32f_out, hit_id_out, stats);
+}
+
+int wgt_render_tiles_sampled_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw,
+                                   uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles, const uint8_t* d_sample_map,
+                                   void* d_rgba8, float* d_rgba32f, uint32_t* d_hit_id, void* stream) {
+  wgt_camera_param c1;
+  if (cam) {
+    c1 = sampled_camera(*cam);
+    cam = &c1;
+  }
+  WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, check_sample_map(d_sample_map)));
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
+  return render_frame(ctx, fr, sample_args(ctx, d_sample_map), d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
+                      stream_or_own(ctx, stream), nullptr);
 }
 
 int wgt_trace_rays_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t* d_prim_id,
@@ -916,21 +992,56 @@ int wgt_render_gbuffer_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t
                              float* d_rays, void* stream) {
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, bad_hits(d_out)));
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
-  return gbuffer_launch(ctx, fr, d_tiles, *d_out, d_rays, stream_or_own(ctx, stream));
+  return gbuffer_launch(ctx, fr, SampleArgs{}, d_tiles, *d_out, d_rays, stream_or_own(ctx, stream));
 }
 
-int wgt_render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0,
-                       uint32_t tw, uint32_t th, const wgt_hit_buffers* out, float* rays_out) {
+int wgt_render_gbuffer_sampled_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw,
+                                     uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles, const uint8_t* d_sample_map,
+                                     const wgt_hit_buffers* d_out, float* d_rays, void* stream) {
+  wgt_camera_param c1;
+  if (cam) {
+    c1 = sampled_camera(*cam);
+    cam = &c1;
+  }
+  const char* bad = bad_hits(d_out);
+  if (!bad) bad = check_sample_map(d_sample_map);
+  WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, bad));
+  const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
+  return gbuffer_launch(ctx, fr, sample_args(ctx, d_sample_map), d_tiles, *d_out, d_rays, stream_or_own(ctx, stream));
+}
+
+}  // extern "C"
+
+namespace {
+
+// wgt_render_gbuffer, and with a host sample map (sampled) wgt_render_gbuffer_sampled, as render_tile.
+int render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0,
+                   uint32_t tw, uint32_t th, bool sampled, const uint8_t* sample_map, const wgt_hit_buffers* out,
+                   float* rays_out) {
+  wgt_camera_param c1;
+  const wgt_camera_param* cam = cam_in;
+  if (sampled && ctx && cam_in) {
+    c1 = sampled_camera(*cam_in);
+    cam = &c1;
+  }
   int rc = check_render_args(ctx, cam, W, H, tw, th);
   if (rc) return rc;
   if (const char* bad = bad_hits(out)) return fail(ctx, WGT_E_INVALID, bad);
   if (x0 >= W || y0 >= H) return fail(ctx, WGT_E_INVALID, "tile origin outside the frame");
+  if (sampled)
+    if (const char* bad = check_sample_map(sample_map)) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t npx = (size_t)tw * th;
   const wgt_tile tile{x0, y0, cam->seed, 0u};
   wgt_hit_buffers dev;
   const wgt_tile* d_tile;
   float* d_rays = nullptr;
+  SampleArgs sm{};
+  if (sampled) {
+    const uint8_t* d_map;
+    if ((rc = stage(ctx, wgt_ctx::kSampleMap, sample_map, (size_t)W * H, d_map))) return rc;
+    sm = sample_args(ctx, d_map);
+  }
   if ((rc = stage_hits(ctx, *out, npx, dev))) return rc;
   if (rays_out && (rc = scratch(ctx, wgt_ctx::kGbRays, npx * 24, d_rays))) return rc;
   if ((rc = stage(ctx, wgt_ctx::kTiles, &tile, sizeof tile, d_tile))) return rc;
@@ -940,10 +1051,84 @@ int wgt_render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, ui
     if (d_rays) WGT_HIP(ctx, hipMemsetAsync(d_rays, 0, npx * 24, ctx->stream));
   }
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, 1);
-  if ((rc = gbuffer_launch(ctx, fr, d_tile, dev, d_rays, ctx->stream))) return rc;
+  if ((rc = gbuffer_launch(ctx, fr, sm, d_tile, dev, d_rays, ctx->stream))) return rc;
   if ((rc = fetch_hits(ctx, *out, dev, npx))) return rc;
   if (d_rays && (rc = fetch(ctx, rays_out, d_rays, npx * 24))) return rc;
   return sync_stream(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wgt_render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0,
+                       uint32_t tw, uint32_t th, const wgt_hit_buffers* out, float* rays_out) {
+  return render_gbuffer(ctx, cam, W, H, x0, y0, tw, th, false, nullptr, out, rays_out);
+}
+
+int wgt_render_gbuffer_sampled(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t x0,
+                               uint32_t y0, uint32_t tw, uint32_t th, const uint8_t* sample_map,
+                               const wgt_hit_buffers* out, float* rays_out) {
+  return render_gbuffer(ctx, cam, W, H, x0, y0, tw, th, true, sample_map, out, rays_out);
+}
+
+int wgt_sample_plan_defaults(wgt_sample_plan_params* out) {
+  if (!out) return fail(nullptr, WGT_E_INVALID, "null params");
+  *out = sample_plan_defaults();
+  return WGT_OK;
+}
+
+size_t wgt_sample_plan_workspace_bytes(uint32_t W, uint32_t H) { return sample_plan_workspace_bytes(W, H); }
+
+int wgt_sample_plan_async(wgt_ctx* ctx, const wgt_sample_plan_params* params, uint32_t W, uint32_t H,
+                          const wgt_temporal_state* d_state, void* d_workspace, size_t workspace_bytes,
+                          uint8_t* d_map_out, uint64_t* d_total_out, void* stream) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  std::string bad = check_sample_plan_args(params, W, H, d_state, d_map_out);
+  if (bad.empty()) bad = check_sample_plan_workspace(d_workspace, workspace_bytes, W, H);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const SamplePlan plan = plan_sample_plan(params ? *params : sample_plan_defaults(), W, H);
+  // no scene is read: the launches are ordered by the stream alone
+  WGT_HIP(ctx, launch_sample_plan(plan, d_state->len, d_state->moments, d_workspace, d_map_out,
+                                  (unsigned long long*)d_total_out, stream_or_own(ctx, stream)));
+  return WGT_OK;
+}
+
+int wgt_sample_plan(wgt_ctx* ctx, const wgt_sample_plan_params* params, uint32_t W, uint32_t H,
+                    const wgt_temporal_state* state, uint8_t* map_out, uint64_t* total_out) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  const std::string bad = check_sample_plan_args(params, W, H, state, map_out);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  // one allocation of the call's own, freed before it returns: len, the moments, the map, its total, the workspace
+  const size_t n = (size_t)W * H, ws_bytes = sample_plan_workspace_bytes(W, H);
+  enum { kLen, kMom, kMap, kTotal, kWs, kParts };
+  const size_t part[kParts] = {n * 4, n * 8, n, 8, ws_bytes};
+  size_t off[kParts + 1] = {0};
+  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
+  struct Alloc {
+    char* p = nullptr;
+    ~Alloc() {
+      if (p) (void)hipFree(p);
+    }
+  } mem;
+  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
+  }
+  int rc = WGT_OK;
+  if (hipMemcpyAsync(mem.p + off[kLen], state->len, part[kLen], hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(mem.p + off[kMom], state->moments, part[kMom], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a sample plan input failed");
+  const wgt_temporal_state dst{nullptr, (float*)(mem.p + off[kLen]), (float*)(mem.p + off[kMom])};
+  if (rc == WGT_OK)
+    rc = wgt_sample_plan_async(ctx, params, W, H, &dst, mem.p + off[kWs], ws_bytes, (uint8_t*)(mem.p + off[kMap]),
+                               (uint64_t*)(mem.p + off[kTotal]), ctx->stream);
+  if (rc == WGT_OK) rc = fetch(ctx, map_out, mem.p + off[kMap], n);
+  if (rc == WGT_OK && total_out) rc = fetch(ctx, total_out, mem.p + off[kTotal], 8);
+  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
+  return rc != WGT_OK ? rc : rs;
 }
 
 int wgt_denoise_defaults(wgt_denoise_params* out) {

@@ -29,6 +29,9 @@ filter guided by that G-buffer), computed on the device on the batch's stream.
 ranks of a distributed run see no consecutive frames.
 `--denoise-variance` (with `--accumulate`) also writes NNN_accum_vdenoised.png: the accumulated state
 through wgt_denoise_variance, the filter whose luminance weight follows each pixel's variance.
+`--adaptive` (with `--accumulate`) renders frame 0 uniformly at `--spp` and every later frame with the
+sample map wgt_sample_plan makes of the previous frame's accumulated state, capped at `--budget-spp`
+samples per pixel on average (default: `--spp`); one frame per launch, all on one stream.
 
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -219,6 +222,71 @@ class FrameRenderer:
         while pending:
             yield self._finish(pending.pop(0), streams, d_out, copies)
 
+    def stream_adaptive(self, frames, max_history=None, budget_spp=None, totals=None, **plan_params):
+        """Yield (frame, (H, W, 4) uint8 rendered, (H, W, 4) uint8 accumulated) for each of `frames`, in
+        order, rendering adaptively: the first frame uniformly at this renderer's spp, every later
+        frame with the sample map planned (wgt_sample_plan_async, `budget_spp` and `plan_params`) from
+        the state the previous frame left, its G-buffer with the same map.  A frame needs the frame
+        before it, so there is one frame per launch, and everything (render, G-buffer, accumulation,
+        plan) is queued on one pipeline stream: nothing leaves the device but the two rgba8 images and
+        the map's total.  budget_spp None: this renderer's spp, so no frame spends more than the plain
+        run's.  totals: a dict that receives {frame: samples traced}."""
+        import torch
+
+        from ._lib import TILE_DTYPE
+        from .tracer import sample_plan_workspace_bytes
+
+        dev = torch.device("cuda", self.ctx.device)
+        W, H = self.W, self.H
+        n = W * H
+        s = torch.cuda.ExternalStream(self.ctx.pipeline_stream(0), device=dev)
+        budget = float(self.spp if budget_spp is None else budget_spp)
+        side = int(np.sqrt(np.float32(self.spp)))  # the uniform frame's side: floor(sqrt(f32(spp))), as the kernels'
+        with torch.cuda.stream(s):
+            d_u8 = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+            d_acc = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+            d_f32 = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+            d_vec = [torch.empty((2, 3, n), dtype=torch.float32, device=dev) for _ in range(2)]
+            d_prim = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
+            d_flags = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+            d_state = [{"f32": torch.empty((H, W, 4), dtype=torch.float32, device=dev),
+                        "len": torch.empty(n, dtype=torch.float32, device=dev),
+                        "moments": torch.empty((2, n), dtype=torch.float32, device=dev)} for _ in range(2)]
+            d_map = torch.empty(n, dtype=torch.uint8, device=dev)
+            d_total = torch.zeros(1, dtype=torch.int64, device=dev)
+            ws_bytes = sample_plan_workspace_bytes(W, H)
+            d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        for history, f in enumerate(frames):
+            with torch.cuda.stream(s):  # left before the frame is handed out: the caller's stream stays its own
+                t = np.zeros(1, TILE_DTYPE)
+                t["seed"] = f
+                d_tile = torch.from_numpy(t.view(np.uint8).copy()).to(dev)
+                q, p = history % 2, 1 - history % 2
+                smap = d_map.data_ptr() if history else 0  # frame 0: uniform, cam's spp
+                guides = {"prim": d_prim[q].data_ptr(), "pos": d_vec[q][0].data_ptr(), "norm": d_vec[q][1].data_ptr(),
+                          "flags": d_flags[q].data_ptr()}
+                before = {"prim": d_prim[p].data_ptr(), "pos": d_vec[p][0].data_ptr(), "norm": d_vec[p][1].data_ptr(),
+                          "flags": d_flags[p].data_ptr()}
+                out = {key: b.data_ptr() for key, b in d_state[q].items()}
+                prev = {key: b.data_ptr() for key, b in d_state[p].items()}
+                self.ctx.render_tiles_async(self.cam, W, H, W, H, d_tile.data_ptr(), 1, d_u8=d_u8.data_ptr(),
+                                            d_f32=d_f32.data_ptr(), stream=s.cuda_stream, d_sample_map=smap)
+                self.ctx.render_gbuffer_async(self.cam, W, H, W, H, d_tile.data_ptr(), 1, stream=s.cuda_stream,
+                                              d_sample_map=smap, **guides)
+                self.ctx.temporal_accumulate_async(W, H, self.cam, d_f32.data_ptr(), guides, out, prev if history else None,
+                                                   before if history else None, self.cam if history else None,
+                                                   d_u8_out=d_acc.data_ptr(), max_history=max_history,
+                                                   stream=s.cuda_stream)
+                spent = int(d_total.cpu()[0]) if history else side * side * n  # the total of the map just rendered with
+                # the next frame's map, behind this frame's render on the stream (which has read the old one)
+                self.ctx.sample_plan_async(W, H, out, d_ws.data_ptr(), ws_bytes, d_map.data_ptr(), d_total.data_ptr(),
+                                           stream=s.cuda_stream, budget_spp=budget, **plan_params)
+                img, accum = d_u8.cpu().numpy(), d_acc.cpu().numpy()
+                d_tile.record_stream(s)
+            if totals is not None:
+                totals[f] = spent
+            yield f, img, accum
+
     @staticmethod
     def _finish(kb, streams, d_out, copies=()):
         """Batch k's images on the host; copies: (per-slot device rgba8 buffers, the dict they go to)."""
@@ -262,6 +330,14 @@ def main(argv=None):
     ap.add_argument("--denoise-variance", action="store_true",
                     help="with --accumulate, also write NNN_accum_vdenoised.png: the accumulated state through the "
                          "variance-guided filter (wgt_denoise_variance, default parameters) on the device")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --accumulate: render frame 0 uniformly at --spp and every later frame with the sample "
+                         "map planned from the previous frame's accumulated state (wgt_sample_plan, default "
+                         "parameters), all on the device; one frame per launch, one process, without --denoise, "
+                         "--denoise-variance and --gbuffer")
+    ap.add_argument("--budget-spp", type=float, default=None,
+                    help="--adaptive: the map's mean samples per pixel may not exceed this (default: --spp, so the "
+                         "option never spends more than the plain run)")
     ap.add_argument("--max-history", type=int, default=32, help="--accumulate: the history length's cap (1..65536)")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
@@ -272,6 +348,12 @@ def main(argv=None):
         ap.error("--accumulate needs --out")
     if a.denoise_variance and not (a.accumulate and a.out):
         ap.error("--denoise-variance needs --accumulate and --out: it filters the accumulated state")
+    if a.adaptive and not a.accumulate:
+        ap.error("--adaptive needs --accumulate: the map is planned from the accumulated state")
+    if a.adaptive and (a.denoise or a.denoise_variance or a.gbuffer):
+        ap.error("--adaptive runs without --denoise, --denoise-variance and --gbuffer")
+    if a.budget_spp is not None and not (a.adaptive and a.budget_spp > 0 and a.budget_spp < float("inf")):
+        ap.error("--budget-spp needs --adaptive and a finite value > 0")
     if a.accumulate and not 1 <= a.max_history <= 65536:
         ap.error("--max-history must be 1..65536")
     if a.accumulate and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -313,22 +395,30 @@ def main(argv=None):
     accumulated = {} if a.accumulate else None
     accumulated_denoised = {} if a.accumulate and a.denoise else None
     accumulated_vdenoised = {} if a.accumulate and a.denoise_variance else None
-    for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised, accumulated=accumulated,
-                             max_history=a.max_history, accumulated_denoised=accumulated_denoised,
-                             accumulated_vdenoised=accumulated_vdenoised):
-        if a.out:
-            for f in b:  # render.cpp:494-497
-                pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
-                for suffix, extra in (("denoised", denoised), ("accum", accumulated),
-                                      ("accum_denoised", accumulated_denoised),
-                                      ("accum_vdenoised", accumulated_vdenoised)):
-                    if extra is not None:
-                        pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_{suffix}.png"),
-                                                   extra.pop(f)))
-                if a.gbuffer:
-                    np.savez(os.path.join(a.out, f"{f:03d}_gbuffer.npz"), **fr.gbuffer(f))
+    totals = {}
+    if a.adaptive:
+        for f, img, accum in fr.stream_adaptive(mine, max_history=a.max_history, budget_spp=a.budget_spp, totals=totals):
+            pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), img))
+            pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_accum.png"), accum))
             while len(pending) > 4 * workers:
                 pending.popleft().result()
+    else:
+        for b, imgs in fr.stream(batches(mine, a.batch), depth=a.pipeline, denoised=denoised, accumulated=accumulated,
+                                 max_history=a.max_history, accumulated_denoised=accumulated_denoised,
+                                 accumulated_vdenoised=accumulated_vdenoised):
+            if a.out:
+                for f in b:  # render.cpp:494-497
+                    pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), imgs[f]))
+                    for suffix, extra in (("denoised", denoised), ("accum", accumulated),
+                                          ("accum_denoised", accumulated_denoised),
+                                          ("accum_vdenoised", accumulated_vdenoised)):
+                        if extra is not None:
+                            pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_{suffix}.png"),
+                                                       extra.pop(f)))
+                    if a.gbuffer:
+                        np.savez(os.path.join(a.out, f"{f:03d}_gbuffer.npz"), **fr.gbuffer(f))
+                while len(pending) > 4 * workers:
+                    pending.popleft().result()
     while pending:
         pending.popleft().result()
     dt = time.perf_counter() - t0
@@ -336,7 +426,7 @@ def main(argv=None):
         pool.shutdown()
     torch.cuda.synchronize()
     print(json.dumps({"rank": rank, "world": world, "frames": len(mine), "batch": a.batch, "pipeline": a.pipeline,
-                      "seconds": round(dt, 3),
+                      "seconds": round(dt, 3), **({"adaptive_samples": sum(totals.values())} if a.adaptive else {}),
                       "frames_per_s": round(len(mine) / dt, 3) if dt > 0 else None}), flush=True)
     ctx.close()
 

@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
-                   WgtHitBuffers, WgtMotionBuffers, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
+                   WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -191,6 +191,26 @@ def denoise_variance_workspace_bytes(W: int, H: int) -> int:
     return int(lib().wgt_denoise_variance_workspace_bytes(W, H))
 
 
+def sample_plan_defaults():
+    """wgt_sample_plan_defaults: a WgtSamplePlanParams of the library's defaults."""
+    p = WgtSamplePlanParams()
+    check(lib().wgt_sample_plan_defaults(ctypes.byref(p)))
+    return p
+
+
+def sample_plan_workspace_bytes(W: int, H: int) -> int:
+    """Bytes of device scratch Context.sample_plan_async needs for a W x H image (0: a size it refuses)."""
+    return int(lib().wgt_sample_plan_workspace_bytes(W, H))
+
+
+def _host_sample_map(sample_map, W, H):
+    """A (H, W) uint8 sample map as the contiguous host array the sampled calls read."""
+    m = np.ascontiguousarray(sample_map, np.uint8)
+    if m.shape != (H, W):
+        raise ValueError(f"sample_map has shape {m.shape}, not the frame's (H, W) = ({H}, {W})")
+    return m
+
+
 def temporal_defaults():
     """wgt_temporal_defaults: a WgtTemporalParams of the library's defaults."""
     p = WgtTemporalParams()
@@ -289,7 +309,11 @@ class Context:
                                          ctypes.byref(step)))
         return nodes, recs, cn, cr, step.value
 
-    def render_tile(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=("u8", "f32", "hit"), stats=False):
+    def render_tile(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=("u8", "f32", "hit"), stats=False,
+                    sample_map=None):
+        """wgt_render_tile; with sample_map, a (H, W) uint8 array of per-pixel sample-grid sides over the
+        whole frame, wgt_render_tile_sampled: pixel (x, y) is rendered at spp = sample_map[y, x] ** 2
+        and cam's spp is ignored."""
         tw = W if tw is None else tw
         th = H if th is None else th
         u8 = np.zeros((th, tw, 4), np.uint8) if "u8" in want else None
@@ -297,6 +321,12 @@ class Context:
         hit = np.zeros((th, tw), np.uint32) if "hit" in want else None
         st = WgtStats() if stats else None
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        if sample_map is not None:
+            m = _host_sample_map(sample_map, W, H)
+            self._check(self._L.wgt_render_tile_sampled(self.h, ptr(cam), W, H, x0, y0, tw, th, ptr(m), ptr(u8),
+                                                        ptr(f32), ptr(hit),
+                                                        ctypes.byref(st) if st is not None else None))
+            return {"u8": u8, "f32": f32, "hit": hit, "stats": st.as_dict() if st is not None else None}
         self._check(self._L.wgt_render_tile(self.h, ptr(cam), W, H, x0, y0, tw, th, ptr(u8), ptr(f32), ptr(hit),
                                             ctypes.byref(st) if st is not None else None))
         return {"u8": u8, "f32": f32, "hit": hit, "stats": st.as_dict() if st is not None else None}
@@ -311,9 +341,17 @@ class Context:
                                               ctypes.byref(st) if st is not None else None))
         return (out, st.as_dict()) if stats else out
 
-    def render_tiles_async(self, cam, W, H, tw, th, d_tiles, n_tiles, d_u8=0, d_f32=0, d_hit=0, stream=0):
-        """Device-pointer launch (ints are raw device addresses, 0 = NULL)."""
+    def render_tiles_async(self, cam, W, H, tw, th, d_tiles, n_tiles, d_u8=0, d_f32=0, d_hit=0, stream=0,
+                           d_sample_map=0):
+        """Device-pointer launch (ints are raw device addresses, 0 = NULL).  d_sample_map: the frame's
+        W x H uint8 sample map on the device (wgt_render_tiles_sampled_async; cam's spp is ignored)."""
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        if d_sample_map:
+            self._check(self._L.wgt_render_tiles_sampled_async(
+                self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles), n_tiles, ctypes.c_void_p(d_sample_map),
+                ctypes.c_void_p(d_u8 or None), ctypes.c_void_p(d_f32 or None), ctypes.c_void_p(d_hit or None),
+                ctypes.c_void_p(stream or None)))
+            return
         self._check(self._L.wgt_render_tiles_async(self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles),
                                                    n_tiles, ctypes.c_void_p(d_u8 or None),
                                                    ctypes.c_void_p(d_f32 or None), ctypes.c_void_p(d_hit or None),
@@ -391,16 +429,23 @@ class Context:
         self._check(self._L.wgt_trace_hits_async(self.h, ctypes.c_void_p(d_rays), n, ctypes.byref(bufs),
                                                  ctypes.c_void_p(stream or None)))
 
-    def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False):
+    def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False, sample_map=None):
         """First-hit G-buffer (wgt_render_gbuffer): the hit record of sample 0's primary ray of each
         pixel of the rectangle, (th, tw) and (th, tw, 3) arrays; rays=True adds that ray as
-        "origin" and "direction", (th, tw, 3) each."""
+        "origin" and "direction", (th, tw, 3) each.  sample_map: the (H, W) uint8 map of the sampled
+        frame this G-buffer belongs to (wgt_render_gbuffer_sampled; cam's spp is ignored)."""
         tw = W if tw is None else tw
         th = H if th is None else th
         arr, bufs = self._hit_arrays(want, (th, tw))
         r = np.zeros((6, th, tw), np.float32) if rays else None
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
-        self._check(self._L.wgt_render_gbuffer(self.h, ptr(cam), W, H, x0, y0, tw, th, ctypes.byref(bufs), ptr(r)))
+        if sample_map is not None:
+            m = _host_sample_map(sample_map, W, H)
+            self._check(self._L.wgt_render_gbuffer_sampled(self.h, ptr(cam), W, H, x0, y0, tw, th, ptr(m),
+                                                           ctypes.byref(bufs), ptr(r)))
+        else:
+            self._check(self._L.wgt_render_gbuffer(self.h, ptr(cam), W, H, x0, y0, tw, th, ctypes.byref(bufs),
+                                                   ptr(r)))
         out = self._hit_dict(arr)
         if rays:
             out["origin"] = np.ascontiguousarray(np.moveaxis(r[:3], 0, -1))
@@ -408,11 +453,17 @@ class Context:
         return out
 
     def render_gbuffer_async(self, cam, W, H, tw, th, d_tiles, n_tiles, prim=0, dist=0, pos=0, norm=0, col=0,
-                             flags=0, d_rays=0, stream=0):
+                             flags=0, d_rays=0, stream=0, d_sample_map=0):
         """Tile-list G-buffer launch with device buffers (raw device addresses, 0 = NULL): n =
-        n_tiles * tw * th records at render_tiles_async's pixel offsets; d_rays: 6 planes of n floats."""
+        n_tiles * tw * th records at render_tiles_async's pixel offsets; d_rays: 6 planes of n floats.
+        d_sample_map: the sampled frame's W x H uint8 map on the device (wgt_render_gbuffer_sampled_async)."""
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
         bufs = _device_hit_buffers(prim, dist, pos, norm, col, flags)
+        if d_sample_map:
+            self._check(self._L.wgt_render_gbuffer_sampled_async(
+                self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles), n_tiles, ctypes.c_void_p(d_sample_map),
+                ctypes.byref(bufs), ctypes.c_void_p(d_rays or None), ctypes.c_void_p(stream or None)))
+            return
         self._check(self._L.wgt_render_gbuffer_async(self.h, ptr(cam), W, H, tw, th, ctypes.c_void_p(d_tiles),
                                                      n_tiles, ctypes.byref(bufs), ctypes.c_void_p(d_rays or None),
                                                      ctypes.c_void_p(stream or None)))
@@ -733,6 +784,54 @@ class Context:
                                                        ctypes.c_void_p(d_u8_out or None),
                                                        ctypes.c_void_p(d_var_out or None),
                                                        ctypes.c_void_p(stream or None)))
+
+    @staticmethod
+    def _sample_plan_params(params):
+        """wgt_sample_plan_params: the library's defaults, with the keyword arguments given over them."""
+        p = sample_plan_defaults()
+        names = [n for n, _ in p._fields_]
+        for name, value in params.items():
+            if name not in names:
+                raise TypeError(f"sample_plan: unknown parameter {name!r}; choose from {names}")
+            if value is not None:
+                setattr(p, name, value)
+        return p
+
+    def sample_plan(self, state, **params):
+        """The next frame's sample map (wgt_sample_plan) from `state`, the dict temporal_accumulate
+        returns (its "len" and "moments" are read).  Keyword parameters: side_min, side_max, gain,
+        lum_floor, min_history, dilate, budget_spp (the library's defaults otherwise).  Returns
+        {"map": (H, W) uint8, "total": int}, total = the map's sum of squares."""
+        missing = [k for k in ("len", "moments") if state.get(k) is None]
+        if missing:
+            raise ValueError(f"sample_plan: state lacks {missing}")
+        length = np.ascontiguousarray(state["len"], np.float32)
+        if length.ndim != 2:
+            raise ValueError(f"sample_plan: state['len'] must be (H, W), got {length.shape}")
+        H, W = length.shape
+        moments = np.ascontiguousarray(state["moments"], np.float32)
+        if moments.size != 2 * H * W:
+            raise ValueError(f"sample_plan: state['moments'] has {moments.size} elements, not {2 * H * W}")
+        st = WgtTemporalState(None, length.ctypes.data, moments.ctypes.data)
+        out = np.zeros((H, W), np.uint8)
+        total = ctypes.c_uint64(0)
+        p = self._sample_plan_params(params)
+        self._check(self._L.wgt_sample_plan(self.h, ctypes.byref(p), W, H, ctypes.byref(st), ptr(out),
+                                            ctypes.byref(total)))
+        return {"map": out, "total": int(total.value)}
+
+    def sample_plan_async(self, W, H, state, d_workspace, workspace_bytes, d_map_out, d_total_out=0, stream=0, **params):
+        """Device-pointer launch (wgt_sample_plan_async; raw device addresses, 0 = NULL): `state`, a dict
+        {"len", "moments"} of addresses as temporal_accumulate_async's `out`, a workspace of
+        sample_plan_workspace_bytes(W, H) bytes that is the caller's, the W x H uint8 map and
+        (optionally) its uint64 total.  Ordered on `stream` (0 = the context's)."""
+        st = WgtTemporalState(None, state.get("len") or None, state.get("moments") or None)
+        p = self._sample_plan_params(params)
+        self._check(self._L.wgt_sample_plan_async(self.h, ctypes.byref(p), W, H, ctypes.byref(st),
+                                                  ctypes.c_void_p(d_workspace or None), workspace_bytes,
+                                                  ctypes.c_void_p(d_map_out or None),
+                                                  ctypes.c_void_p(d_total_out or None),
+                                                  ctypes.c_void_p(stream or None)))
 
     def stream(self) -> int:
         return self._L.wgt_stream(self.h) or 0
