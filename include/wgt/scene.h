@@ -34,6 +34,10 @@ class Scene {
   // InitBuffers (an update moves triangles; call InitBuffers to add or remove) or when the call
   // refuses the triangles.
   bool UpdateTriangles(wgt_ctx* ctx);
+  // Replaces the uploaded mesh by tris_ as it is now, of any count >= 1, and rebuilds its BVH on the
+  // device (wgt_rebuild_triangles); a later UpdateTriangles refits the rebuilt tree.  Returns false
+  // with an error message when the scene was not uploaded to ctx or when the call refuses the triangles.
+  bool RebuildTriangles(wgt_ctx* ctx);
   void Release();  // scene.cpp:41-50 (idempotent)
 
   // CreateQuadBuffer / CreateSphereBuffer / CreateTriangleBuffer packing

@@ -27,6 +27,8 @@
  *   camera.spp, one per frame path_tracer.wgsl:23     wgt_render_tile_sampled, ..._tiles_sampled_async,
  *                                                     wgt_render_gbuffer_sampled (a side per pixel)
  *   (none: the sides planned from the variance)       wgt_sample_plan
+ *   Scene::InitBuffers again, for a changed mesh      wgt_rebuild_triangles, wgt_rebuild_triangles_device
+ *                                                     (a new BVH made on the device, any triangle count)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -268,6 +270,46 @@ int wgt_bvh_read(wgt_ctx *ctx, float *nodes_out, uint32_t nodes_cap, float *tris
 int wgt_bvh_refit(const wgt_triangle *built_from, const wgt_triangle *now, uint32_t n_tris,
                   float *nodes_out, uint32_t nodes_cap, float *tris_out, uint32_t *cnodes_out,
                   int32_t *crefs_out, float *step_out, wgt_scene_info *info);
+
+/* ---- rebuilding the triangle BVH on the device (no reference counterpart) -- */
+/* Replaces the scene's triangles by n_tris >= 1 new ones and makes a new tree for them on the
+ * device.  n_tris may differ from the resident count, and a scene uploaded without triangles is
+ * accepted: this is how a simulation that tears, spawns or deletes triangles, or a mesh that has
+ * drifted far from the pose its tree was built for, stays on the device.  The tree is an LBVH over
+ * 63-bit Morton codes emitted directly as a BVH4 of at most 10 levels (DESIGN.md §4.12;
+ * wgt_bvh_build_morton below is its specification); a static scene is served better by
+ * wgt_upload_scene's SAH tree.
+ *   - Triangle i gets primitive id n_lights + n_quads + i, so sphere ids move when the count changes.
+ *   - Shading fields come from the records, as in wgt_update_triangles_device.
+ *   - Afterwards every render, sampled render, G-buffer, ray query, hit record and occlusion answer
+ *     equals that of wgt_upload_scene of the same quads, lights and spheres with these triangles, bit
+ *     for bit.  Only wgt_stats' visit counters and the tree fields of wgt_scene_info differ: sah_cost,
+ *     bvh2_nodes and bvh2_depth are 0 (no BVH2 exists), device_bytes counts what is in use.
+ *   - A rebuild drops the motion snapshot, as an upload does; a later wgt_update_* refits the
+ *     rebuilt tree; wgt_update_timing also reports a rebuild (the host part is everything before the
+ *     first build kernel).
+ *   - WGT_REBUILD_LEAF (4, 1..8) is the leaf target L.
+ * Both calls are SYNCHRONOUS, with wgt_update_triangles_device's stream rule: the input is read
+ * after everything queued on `stream` (NULL: the context's), the call then waits for every launch
+ * of the context, and it returns when the new tree is resident.  The input is never written.
+ * Order of checks: NULL context; WGT_E_NOSCENE; then WGT_E_INVALID for a NULL pointer, for
+ * n_tris == 0, for n_tris above L * 4^10 ("too many triangles for a rebuild"), for a misaligned
+ * device pointer (16 bytes); then the device pass of wgt_update_triangles_device names the
+ * lowest-numbered triangle beyond the scene limits in wgt_update_triangles' words.  A refusal
+ * leaves the scene exactly as it was, and so does a WGT_E_HIP failure: the new tree is made in a
+ * second allocation and swapped in on success (the old one is kept as the spare, so a steady stream
+ * of rebuilds allocates nothing). */
+/* d_tris: DEVICE array of n_tris wgt_triangle records, 16-byte aligned. */
+int wgt_rebuild_triangles_device(wgt_ctx *ctx, const wgt_triangle *d_tris, uint32_t n_tris, void *stream);
+/* The same from a HOST array: it is staged, then the same body runs. */
+int wgt_rebuild_triangles(wgt_ctx *ctx, const wgt_triangle *tris, uint32_t n_tris);
+/* Host only: the tree that wgt_upload_scene of any scene whose lights, quads and spheres lie within
+ * the triangles' extent, followed by a rebuild to tris[0..n_tris) alone, must hold, in wgt_bvh_read's
+ * layouts (any output may be NULL; info is required).  Call once with NULL outputs to size them,
+ * as wgt_bvh_refit.  tris is checked as the rebuild checks it. */
+int wgt_bvh_build_morton(const wgt_triangle *tris, uint32_t n_tris, float *nodes_out, uint32_t nodes_cap,
+                         float *tris_out, uint32_t *cnodes_out, int32_t *crefs_out, float *step_out,
+                         wgt_scene_info *info);
 
 /* ---- rendering (replaces the compute pass of Renderer::OnRender) --------- */
 /* Synchronous: render the rectangle [x0,x0+tw) x [y0,y0+th) of a W x H frame

@@ -126,6 +126,7 @@ EXPORTS = [
     "wgt_render_frames",
     "wgt_update_triangles", "wgt_update_timing", "wgt_bvh_read", "wgt_bvh_refit",
     "wgt_update_triangles_device", "wgt_update_vertices_device",
+    "wgt_rebuild_triangles", "wgt_rebuild_triangles_device", "wgt_bvh_build_morton",
     "wgt_denoise_defaults", "wgt_denoise_workspace_bytes", "wgt_denoise", "wgt_denoise_async",
     "wgt_temporal_defaults", "wgt_temporal_accumulate", "wgt_temporal_accumulate_async",
     "wgt_denoise_variance_defaults", "wgt_denoise_variance_workspace_bytes", "wgt_denoise_variance",
@@ -203,6 +204,10 @@ def lib():
         "wgt_update_timing": (I, [P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_read": (I, [P, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float)]),
         "wgt_bvh_refit": (I, [P, P, U32, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(WgtSceneInfo)]),
+        "wgt_rebuild_triangles": (I, [P, P, U32]),
+        "wgt_rebuild_triangles_device": (I, [P, P, U32, P]),
+        "wgt_bvh_build_morton": (I, [P, U32, P, U32, P, P, P, ctypes.POINTER(ctypes.c_float),
+                                     ctypes.POINTER(WgtSceneInfo)]),
         "wgt_denoise_defaults": (I, [ctypes.POINTER(WgtDenoiseParams)]),
         "wgt_denoise_workspace_bytes": (ctypes.c_size_t, [U32, U32]),
         "wgt_denoise": (I, [P, ctypes.POINTER(WgtDenoiseParams), U32, U32, P, ctypes.POINTER(WgtHitBuffers), P, P]),

@@ -7,6 +7,7 @@
 #include "bvh.h"
 
 #include "../wgt_compact.h"
+#include "../wgt_morton.h"
 
 #include <algorithm>
 #include <cmath>
@@ -692,6 +693,108 @@ bool RefitBvh(BvhOut& bvh, const wgt_triangle* tris, uint32_t n, double origin_b
   CompactForm(origin_bound, bvh);
   ShadeRecords(tris, n, bvh);
   return true;
+}
+
+uint32_t RebuildLeafFromEnv() {
+  const char* v = std::getenv("WGT_REBUILD_LEAF");
+  const int leaf = v && *v ? std::atoi(v) : (int)kRebuildLeafDefault;
+  return (uint32_t)std::max(1, std::min(leaf, kLeafMax));  // (4) 1..8
+}
+
+bool BuildMortonBvh(const wgt_triangle* tris, uint32_t n, uint32_t leaf, double origin_bound, BvhOut& out,
+                    std::vector<uint32_t>* level_count, std::string& err) {
+  out = BvhOut{};
+  const uint32_t L = std::max(1u, std::min(leaf, (uint32_t)kLeafMax));
+  if (n == 0) { err = "BuildMortonBvh: no triangles"; return false; }
+  if (n > rebuild_max_tris(L)) {
+    err = "BuildMortonBvh: too many triangles for a rebuild (max " + std::to_string(rebuild_max_tris(L)) + " at leaf target " +
+          std::to_string(L) + ")";
+    return false;
+  }
+  // keys: the centres of the padded boxes between their exact bounds
+  std::vector<float> c((size_t)n * 3);
+  float cmin[3] = {kInf, kInf, kInf}, cmax[3] = {-kInf, -kInf, -kInf};
+  for (uint32_t i = 0; i < n; ++i) {
+    const wgt_triangle& t = tris[i];
+    f3 lo, hi;
+    tri_box(f3{t.v0[0], t.v0[1], t.v0[2]}, f3{t.e1[0], t.e1[1], t.e1[2]}, f3{t.e2[0], t.e2[1], t.e2[2]}, lo, hi);
+    const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(l[a]) || !std::isfinite(h[a])) {
+        err = "BuildMortonBvh: non-finite triangle " + std::to_string(i);
+        return false;
+      }
+      const float v = morton_centre(l[a], h[a]);
+      c[(size_t)i * 3 + a] = v;
+      cmin[a] = std::min(cmin[a], v);
+      cmax[a] = std::max(cmax[a], v);
+    }
+  }
+  std::vector<unsigned long long> key(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t q[3];
+    for (int a = 0; a < 3; ++a) q[a] = morton_cell(c[(size_t)i * 3 + a], cmin[a], cmax[a]);
+    key[i] = morton_code(q[0], q[1], q[2]);
+  }
+  // the leaf order: ascending by (code, original index)
+  std::vector<uint32_t> order(n);
+  for (uint32_t i = 0; i < n; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b] || (key[a] == key[b] && a < b); });
+  std::vector<unsigned long long> code(n);
+  for (uint32_t i = 0; i < n; ++i) code[i] = key[order[i]];
+  out.tris.assign((size_t)n * kTriRecordFloats, 0.0f);
+  for (uint32_t i = 0; i < n; ++i) std::memcpy(&out.tris[(size_t)i * kTriRecordFloats + 3], &order[i], 4);
+
+  // the topology, level by level: a node's index is its level's first index + its place in the level
+  struct Range { uint32_t b, e, r, path; };
+  std::vector<Range> level{{0u, n, 2 * kRebuildLevels, 0u}}, next;
+  const auto add_node = [&]() {
+    out.nodes.resize(out.nodes.size() + kNode4Floats, 0.0f);
+    return Node4(out.nodes, out.n_nodes++);
+  };
+  const auto finish = [&](const Node4T<float>& o, const int* refs, int live) {
+    for (int s = 0; s < kBvhWidth; ++s) {
+      for (int a = 0; a < 3; ++a) o.lo(a, s) = o.hi(a, s) = s < live ? 0.0f : kEmptySlotCoord;  // a live box: the refit's
+      o.set_ref(s, s < live ? refs[s] : refs[0]);
+      o.pad(s) = 0.0f;
+    }
+  };
+  if (level_count) level_count->clear();
+  if (n <= L) {  // the single-leaf root with one empty slot, as BuildBvh2 makes it: two slots, so one stack entry
+    const int refs[kBvhWidth] = {leaf_ref(0, n)};
+    finish(add_node(), refs, 1);
+    out.n_leaves = 1; out.max_leaf = n; out.max_depth = 1; out.stack_need = 1;
+    if (level_count) level_count->push_back(1u);
+  } else {
+    while (!level.empty()) {
+      const uint32_t next_begin = out.n_nodes + (uint32_t)level.size();
+      next.clear();
+      for (const Range& g : level) {
+        uint32_t cut[kBvhWidth + 1];
+        const int slots = morton_slots(code.data(), g.b, g.e, g.r, L, cut);
+        const uint32_t path = g.path + (uint32_t)(slots - 1);
+        out.stack_need = std::max(out.stack_need, path);
+        int refs[kBvhWidth] = {};
+        for (int s = 0; s < slots; ++s) {
+          const uint32_t cnt = cut[s + 1] - cut[s];
+          if (cnt <= L) {
+            refs[s] = leaf_ref(cut[s], cnt);
+            out.n_leaves++;
+            out.max_leaf = std::max(out.max_leaf, cnt);
+          } else {
+            refs[s] = (int)(next_begin + (uint32_t)next.size());
+            next.push_back(Range{cut[s], cut[s + 1], g.r - 2, path});
+          }
+        }
+        finish(add_node(), refs, slots);
+      }
+      out.max_depth++;
+      if (level_count) level_count->push_back((uint32_t)level.size());
+      level.swap(next);
+    }
+  }
+  if (!CheckRefs(out, n, err)) return false;
+  return RefitBvh(out, tris, n, origin_bound, err);
 }
 
 BvhImage DeviceImage(const BvhOut& bvh) {

@@ -80,6 +80,18 @@ bool BuildBvh(const wgt_triangle* tris, uint32_t n, const BvhOptions& opt, BvhOu
 // (a non-finite triangle box, as in the build) err says why and bvh is unchanged.
 bool RefitBvh(BvhOut& bvh, const wgt_triangle* tris, uint32_t n, double origin_bound, std::string& err);
 
+// The leaf target of a rebuild, WGT_REBUILD_LEAF (4): 1..kLeafMax.
+uint32_t RebuildLeafFromEnv();
+
+// The tree of a rebuild, the specification of wgt_rebuild_triangles: an LBVH over
+// 63-bit Morton codes of the triangles' centres (wgt_morton.h), emitted directly as a BVH4 of at most
+// kRebuildLevels levels with leaves of at most `leaf` triangles, nodes numbered breadth-first; the
+// boxes, records and compact form are RefitBvh's for that topology.  No BVH2 exists: n_nodes2, depth2
+// and sah_cost stay 0.  level_count (may be null) receives the nodes of each level, root first.  On
+// failure (no triangles, more than rebuild_max_tris(leaf), a non-finite triangle box) err says why.
+bool BuildMortonBvh(const wgt_triangle* tris, uint32_t n, uint32_t leaf, double origin_bound, BvhOut& out,
+                    std::vector<uint32_t>* level_count, std::string& err);
+
 // The tree as the kernels read it: internal refs are byte offsets (one add to the uniform
 // base instead of an index multiply), leaf refs are unchanged.
 struct BvhImage {

@@ -262,6 +262,79 @@ std::string check_vertex_index(const uint32_t index[3], uint32_t n_verts, uint32
   return "";
 }
 
+std::string check_rebuild_records(const void* tris, uint32_t n_tris, uint32_t leaf, bool align) {
+  if (!tris) return "null triangles";
+  if (n_tris == 0) return "triangle count 0: a rebuild needs a triangle (upload a scene without triangles instead)";
+  if (n_tris > rebuild_max_tris(leaf))
+    return "too many triangles for a rebuild: " + std::to_string(n_tris) + " exceeds " +
+           std::to_string(rebuild_max_tris(leaf)) + " (leaf target " + std::to_string(leaf) + " x 4^" +
+           std::to_string(kRebuildLevels) + ")";
+  if (align && !aligned_to(tris, 16)) return "misaligned triangles: device wgt_triangle records must be 16-byte aligned";
+  return "";
+}
+
+std::string morton_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh,
+                       std::vector<uint32_t>* level_count) {
+  std::string err;
+  return BuildMortonBvh(tris, n_tris, RebuildLeafFromEnv(), kOriginBoundScale * extent, bvh, level_count, err) ? "" : err;
+}
+std::string morton_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh) {
+  return morton_bvh(tris, n_tris, scene_extent(nullptr, 0, nullptr, 0, tris, n_tris), bvh, nullptr);
+}
+
+uint32_t rebuild_node_cap(uint32_t n_tris) { return std::max(n_tris, 2u) - 1u; }
+
+static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+size_t tree_layout(uint32_t n_tris, uint32_t n_nodes, size_t off[]) {
+  const size_t bytes[kSceneParts] = {0, 0, (size_t)n_nodes * kNode4Floats * 4, (size_t)n_tris * kTriRecordBytes,
+                                     (size_t)n_tris * 32, (size_t)n_nodes * kCRecordFloat4s * 16, n_nodes};
+  size_t total = 0;
+  for (int i = kPartNodes; i < kSceneParts; ++i) {
+    off[i] = total;
+    total += align256(bytes[i]);
+  }
+  return total;
+}
+
+void bind_tree(DevScene& sc, const size_t off[], const void* base) {
+  const auto at = [&](ScenePart i) { return (const float4*)((const char*)base + off[i]); };
+  sc.nodes = at(kPartNodes); sc.tris = at(kPartTris); sc.tshade = at(kPartShade); sc.cnodes = at(kPartCNodes);
+  sc.node_level = (const uint8_t*)at(kPartLevel);
+}
+
+RebuildScratch plan_rebuild_scratch(uint32_t n_tris, size_t temp_bytes) {
+  RebuildScratch p{};
+  const size_t n = n_tris, nodes = rebuild_node_cap(n_tris);  // a level holds at most every node
+  size_t at = 0;
+  const auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+  for (int i = 0; i < 2; ++i) p.key[i] = take(n * 8);
+  for (int i = 0; i < 2; ++i) p.val[i] = take(n * 4);
+  for (int i = 0; i < 2; ++i) p.list[i] = take(nodes * sizeof(RebuildRange));
+  p.cuts = take(nodes * 16);
+  p.count = take((nodes + 1) * 4);
+  p.offset = take((nodes + 1) * 4);
+  p.bounds = take(sizeof(RebuildBounds));
+  p.stats = take(sizeof(RebuildStats));
+  p.temp = take(temp_bytes);
+  p.bytes = at;
+  return p;
+}
+
+void plan_tree_form(const BvhOut& bvh, uint32_t n_tris, DevScene& sc) {
+  const PsForm form = ps_form_for(bvh, n_tris);
+  sc.n_tris = n_tris;
+  sc.n_nodes = bvh.n_nodes;
+  sc.stack = stack_entries(bvh);
+  sc.ps_waves = form.waves; sc.ps_park = form.park; sc.ps_cap = form.cap;
+}
+
+std::vector<uint32_t> level_begin_of(const std::vector<uint32_t>& level_count) {
+  std::vector<uint32_t> begin(level_count.size() + 1, 0u);
+  for (size_t l = 0; l < level_count.size(); ++l) begin[l + 1] = begin[l] + level_count[l];
+  return begin;
+}
+
 double checked_extent(const RefitCheck& r) {
   double m;
   static_assert(sizeof m == sizeof r.extent_bits, "a double's bits");
@@ -320,18 +393,15 @@ ScenePlan pack_scene(const wgt_quad* lights, uint32_t n_lights, const wgt_quad* 
   for (int i = kPartSpheres; i < kSceneParts; ++i)  // a scene without triangles has empty (null) tree parts
     if (part[i].bytes) std::memcpy(p.host.data() + p.off[i], part[i].src, part[i].bytes);
 
-  const PsForm form = ps_form_for(bvh, n_tris);
   DevScene& sc = p.sc;
   sc.cstep = bvh.cstep; sc.cbound = bvh.cbound;
   sc.rcstep = 1.0f / sc.cstep;  // a power of two: exact
-  sc.n_lights = n_lights; sc.n_quads = n_quads; sc.n_spheres = n_spheres; sc.n_tris = n_tris;
-  sc.n_nodes = bvh.n_nodes;
+  sc.n_lights = n_lights; sc.n_quads = n_quads; sc.n_spheres = n_spheres;
+  plan_tree_form(bvh, n_tris, sc);
   sc.last_sphere_emissive = spheres[n_spheres - 1].emissive > 0.0f ? 1u : 0u;
   const f3 lr = f3{lights[0].right[0], lights[0].right[1], lights[0].right[2]};
   const f3 lu = f3{lights[0].up[0], lights[0].up[1], lights[0].up[2]};
   sc.light_area = length(cross(lr, lu));  // path_tracer.wgsl:205
-  sc.stack = stack_entries(bvh);
-  sc.ps_waves = form.waves; sc.ps_park = form.park; sc.ps_cap = form.cap;
   return p;
 }
 

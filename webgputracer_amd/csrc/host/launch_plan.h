@@ -11,6 +11,7 @@
 #include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
 #include "../wgt_motion.h"
+#include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
 #include "../wgt_temporal.h"
 #include "bvh.h"
@@ -97,6 +98,39 @@ double compact_bound(double extent, const float* root_node);
 // a level is saturated (255: the tree is deeper than levels are recorded for), empty when fine.
 std::string refit_levels(const uint8_t* level, uint32_t n_nodes, std::vector<uint32_t>& order,
                          std::vector<uint32_t>& begin);
+
+// The rebuild (wgt_rebuild_triangles and its device form).  Its argument checks after
+// the context and the scene, in the calls' order, for the leaf target `leaf` (RebuildLeafFromEnv): null,
+// n_tris == 0, more than rebuild_max_tris(leaf), then the alignment rule of the device records (16
+// bytes; the host form passes align = false).  Each returns the refusal's text, empty when fine.
+std::string check_rebuild_records(const void* tris, uint32_t n_tris, uint32_t leaf, bool align);
+// The specification's tree (BuildMortonBvh) under the origin-bound rule of build_bvh, and
+// wgt_bvh_build_morton: the tree an upload of any scene whose lights, quads and spheres lie within
+// the triangles' extent, followed by a rebuild to these triangles, holds.
+std::string morton_bvh(const wgt_triangle* tris, uint32_t n_tris, double extent, BvhOut& bvh,
+                       std::vector<uint32_t>* level_count);
+std::string morton_for_export(const wgt_triangle* tris, uint32_t n_tris, BvhOut& bvh);
+// The nodes a rebuilt tree of n_tris triangles can have at the most: every node has two slots or
+// more and every leaf a triangle or more, so there are fewer nodes than triangles.
+uint32_t rebuild_node_cap(uint32_t n_tris);
+// The device layout of a tree of its own allocation (a rebuild's): the five tree parts of ScenePart
+// for n_nodes nodes and n_tris triangles, each 256-B aligned; returns the bytes, fills off[kPartNodes..].
+size_t tree_layout(uint32_t n_tris, uint32_t n_nodes, size_t off[]);
+// Points sc's five tree parts into the allocation at `base` (bind_scene's tree half).
+void bind_tree(DevScene& sc, const size_t off[], const void* base);
+// The build's scratch: the sort's keys and values twice, two level lists, a level's cuts, counts and
+// child offsets, the centres' bounds and the reduced counts, then rocprim's temporary storage.
+struct RebuildScratch {
+  size_t key[2], val[2], list[2], cuts, count, offset, bounds, stats, temp, bytes;
+};
+RebuildScratch plan_rebuild_scratch(uint32_t n_tris, size_t temp_bytes);
+// What the tree's counts decide of a scene, in one statement for an upload (pack_scene) and a rebuild:
+// n_tris, n_nodes, the traversal stack (stack_entries) and the k_render_ps form (ps_form_for); the
+// counts are read from bvh (its arrays may be empty).
+void plan_tree_form(const BvhOut& bvh, uint32_t n_tris, DevScene& sc);
+// The refit's level lists of a tree numbered breadth-first (a rebuilt one): the order is the identity,
+// begin the running sum of the level counts.
+std::vector<uint32_t> level_begin_of(const std::vector<uint32_t>& level_count);
 
 // The scene's device layout, each part 256-B aligned: quads (lights first), spheres, then the
 // tree: both node forms stay resident (the compact one is 63% of the 128-B one; the launch

@@ -26,4 +26,20 @@ bool Scene::UpdateTriangles(wgt_ctx* ctx) {
   return true;
 }
 
+// The mirror of wgt_rebuild_triangles: the count may have changed since InitBuffers.
+bool Scene::RebuildTriangles(wgt_ctx* ctx) {
+  if (!uploaded_ || ctx != ctx_) {
+    std::cerr << "[WebGPUTracer] triangle rebuild failed: the scene is not uploaded to this context" << std::endl;
+    return false;
+  }
+  auto t = PackTriangles();
+  int rc = wgt_rebuild_triangles(ctx, t.empty() ? nullptr : t.data(), (uint32_t)t.size());
+  if (rc != WGT_OK) {
+    std::cerr << "[WebGPUTracer] triangle rebuild failed: " << wgt_last_error(ctx) << std::endl;
+    return false;
+  }
+  uploaded_tris_ = t.size();
+  return true;
+}
+
 }  // namespace wgt

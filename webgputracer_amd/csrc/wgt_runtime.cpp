@@ -50,7 +50,13 @@ struct wgt_ctx {
   double fixed_extent = 0.0;
   std::vector<uint32_t> level_begin;
   DevBuf level_order;
-  float refit_host_ms = 0.0f, refit_device_ms = 0.0f;  // of the last update (wgt_update_timing)
+  float refit_host_ms = 0.0f, refit_device_ms = 0.0f;  // of the last update or rebuild (wgt_update_timing)
+  // wgt_rebuild_triangles: a rebuilt tree lives in an allocation of its own, tree[tree_cur] (-1: the
+  // upload's tree, in scene_mem); the other one is the spare the next rebuild builds into, so a steady
+  // stream of rebuilds allocates nothing.  fixed_bytes: the scene's lights, quads and spheres, padded
+  DevBuf tree[2];
+  int tree_cur = -1;
+  size_t fixed_bytes = 0;
   // wgt_motion_snapshot: n_tris x 48 B (v0, e1, e2, face normal by original index), then n_tris leaf
   // slots; allocated by the first snapshot after an upload, dropped by the next upload
   DevBuf motion;
@@ -61,9 +67,9 @@ struct wgt_ctx {
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
   // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
   // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev;
-  // a sampled call's sample map
+  // a sampled call's sample map; a rebuild's keys, lists and sort storage (RebuildScratch)
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kRebuild, kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -371,6 +377,32 @@ int fetch_hits(wgt_ctx* ctx, const wgt_hit_buffers& out, const wgt_hit_buffers& 
   return WGT_OK;
 }
 
+// What an upload and a rebuild alike do once the new scene sc (bound to its allocations) is resident
+// and no launch reads the old one: the tree's counts are bvh's (its arrays may be empty), `resident`
+// is ps_resident_waves(sc), level_begin the refit's level lists when they are known (a rebuilt tree's;
+// empty: the next refit prepares them).  Nothing here can fail.
+void install_scene(wgt_ctx* ctx, const DevScene& sc, const BvhOut& bvh, uint32_t resident, size_t device_bytes,
+                   std::vector<uint32_t> level_begin) {
+  // a new scene: the workspaces' scheduling words are re-zeroed by the next launch's memset
+  for (auto& sl : ctx->slots) sl.clean_nb = 0;
+  ctx->level_begin = std::move(level_begin);
+  free_buf(ctx->motion);  // the old scene's snapshot: no launch reads it any more
+  ctx->has_snapshot = false;
+  ctx->sc = sc;
+  ctx->ps_resident = resident;
+  if (env_u32("WGT_DEBUG", 0))
+    std::fprintf(stderr, "[wgt] resident: k_render_ps %u waves; LDS stack %u of %u entries, parked %u\n",
+                 ctx->ps_resident, sc.ps_cap, sc.stack, sc.ps_park);
+  wgt_scene_info& in = ctx->info;
+  in = wgt_scene_info{};
+  fill_bvh_info(bvh, sc.n_tris, ps_form(sc), in);
+  in.n_lights = sc.n_lights; in.n_quads = sc.n_quads; in.n_spheres = sc.n_spheres;
+  in.device_bytes = device_bytes;
+  in.node_form = reference_node_form(sc);
+  in.ps_resident = ctx->ps_resident;
+  ctx->has_scene = true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -433,6 +465,7 @@ void wgt_destroy(wgt_ctx* ctx) {
     }
   if (ctx->scene_mem) (void)hipFree(ctx->scene_mem);
   for (DevBuf& b : ctx->buf) free_buf(b);
+  for (DevBuf& b : ctx->tree) free_buf(b);
   free_buf(ctx->level_order);
   free_buf(ctx->motion);
   free_buf(ctx->sample_tab);
@@ -541,31 +574,20 @@ int wgt_upload_scene(wgt_ctx* ctx, const wgt_quad* lights, uint32_t n_lights, co
     ctx->scene_mem = nullptr;
   }
   ctx->has_scene = false;
-  // a new scene: the workspaces' scheduling words are re-zeroed by the next launch's memset
-  for (auto& sl : ctx->slots) sl.clean_nb = 0;
+  for (DevBuf& b : ctx->tree) free_buf(b);  // a rebuilt tree and its spare: the upload's tree is in scene_mem
+  ctx->tree_cur = -1;
   ctx->fixed_extent = fixed_ext;
-  ctx->level_begin.clear();  // the next refit prepares the new tree's level lists
+  ctx->fixed_bytes = plan.off[kPartNodes];
+  ctx->level_begin.clear();
   free_buf(ctx->level_order);
-  free_buf(ctx->motion);  // the old scene's snapshot: no launch reads it any more
-  ctx->has_snapshot = false;
   WGT_HIP(ctx, hipMalloc(&ctx->scene_mem, plan.host.size()));
   WGT_HIP(ctx, hipMemcpy(ctx->scene_mem, plan.host.data(), plan.host.size(), hipMemcpyHostToDevice));
-  DevScene& sc = ctx->sc;
-  sc = plan.sc;
+  DevScene sc = plan.sc;
   bind_scene(sc, plan.off, ctx->scene_mem);
-  WGT_HIP(ctx, ps_resident_waves(sc, ctx->device, ctx->ps_resident));
-  if (env_u32("WGT_DEBUG", 0))
-    std::fprintf(stderr, "[wgt] resident: k_render_ps %u waves; LDS stack %u of %u entries, parked %u\n",
-                 ctx->ps_resident, sc.ps_cap, sc.stack, sc.ps_park);
-
-  wgt_scene_info& in = ctx->info;
-  in = wgt_scene_info{};
-  fill_bvh_info(bvh, n_tris, ps_form(sc), in);
-  in.n_lights = n_lights; in.n_quads = n_quads; in.n_spheres = n_spheres;
-  in.device_bytes = plan.host.size();
-  in.node_form = reference_node_form(sc);
-  in.ps_resident = ctx->ps_resident;
-  ctx->has_scene = true;
+  uint32_t resident = 0;
+  WGT_HIP(ctx, ps_resident_waves(sc, ctx->device, resident));
+  // the next refit prepares the new tree's level lists
+  install_scene(ctx, sc, bvh, resident, plan.host.size(), std::vector<uint32_t>());
   return WGT_OK;
 }
 
@@ -580,6 +602,33 @@ struct MovedInput {
   const wgt_triangle* d_tris;
   MovedVerts verts;
 };
+
+// The refit kernels on the tree of sc, on the context's stream: the records (from d_moved, or from
+// verts when verts.verts is set), the boxes level by level, deepest first (level l's nodes are
+// d_order[level_begin[l], level_begin[l + 1])), then the compact form for ray origins within the
+// scene's `extent`: its step and bound M come back.  An update runs them on the resident tree, a
+// rebuild on the tree it is making.
+int refit_tree(wgt_ctx* ctx, const DevScene& sc, const uint32_t* d_order, const std::vector<uint32_t>& level_begin,
+               uint32_t* d_max_exp, double extent, const wgt_triangle* d_moved, const MovedVerts& verts, float& step,
+               double& M) {
+  int rc;
+  hipStream_t s = ctx->stream;
+  WGT_HIP(ctx, hipMemsetAsync(d_max_exp, 0, 4, s));
+  if (verts.verts) WGT_HIP(ctx, launch_refit_verts(sc, verts, s));
+  else WGT_HIP(ctx, launch_refit_tris(sc, d_moved, s));
+  for (size_t l = level_begin.size() - 1; l-- > 0;)
+    WGT_HIP(ctx, launch_refit_nodes(sc, d_order + level_begin[l], level_begin[l + 1] - level_begin[l], s));
+  float root[kNode4Floats];
+  if ((rc = fetch(ctx, root, sc.nodes, sizeof root)) || (rc = sync_stream(ctx))) return rc;
+  M = compact_bound(extent, root);
+  const double G = std::ldexp(M, -21);
+  WGT_HIP(ctx, launch_refit_step(sc, G, d_max_exp, s));
+  uint32_t max_exp = 0;
+  if ((rc = fetch(ctx, &max_exp, d_max_exp, 4)) || (rc = sync_stream(ctx))) return rc;
+  step = pow2f(kCompactMinExp + (int)max_exp);
+  WGT_HIP(ctx, launch_refit_compact(sc, step, G, s));
+  return WGT_OK;
+}
 
 // The refit that the three updates share, after their checks: `extent` is the scene's with the new
 // triangles, t0 the call's start (the host part of wgt_update_timing ends at the first refit
@@ -612,19 +661,9 @@ int refit_resident(wgt_ctx* ctx, refit_clock::time_point t0, double extent, cons
   // from here on the resident tree changes: a HIP failure leaves it undefined until the next upload
   for (auto& sl : ctx->slots) sl.clean_nb = 0;  // as an upload
   WGT_HIP(ctx, hipEventRecord(e0, s));
-  WGT_HIP(ctx, hipMemsetAsync(d_max_exp, 0, 4, s));
-  if (in.verts.verts) WGT_HIP(ctx, launch_refit_verts(sc, in.verts, s));
-  else WGT_HIP(ctx, launch_refit_tris(sc, d_moved, s));
-  for (size_t l = ctx->level_begin.size() - 1; l-- > 0;)
-    WGT_HIP(ctx, launch_refit_nodes(sc, d_order + ctx->level_begin[l], ctx->level_begin[l + 1] - ctx->level_begin[l], s));
-  float root[kNode4Floats];
-  if ((rc = fetch(ctx, root, sc.nodes, sizeof root)) || (rc = sync_stream(ctx))) return rc;
-  const double M = compact_bound(extent, root), G = std::ldexp(M, -21);
-  WGT_HIP(ctx, launch_refit_step(sc, G, d_max_exp, s));
-  uint32_t max_exp = 0;
-  if ((rc = fetch(ctx, &max_exp, d_max_exp, 4)) || (rc = sync_stream(ctx))) return rc;
-  const float step = pow2f(kCompactMinExp + (int)max_exp);
-  WGT_HIP(ctx, launch_refit_compact(sc, step, G, s));
+  float step;
+  double M;
+  if ((rc = refit_tree(ctx, sc, d_order, ctx->level_begin, d_max_exp, extent, d_moved, in.verts, step, M))) return rc;
   WGT_HIP(ctx, hipEventRecord(e1, s));
   WGT_HIP(ctx, hipEventSynchronize(e1));
   WGT_HIP(ctx, hipEventElapsedTime(&ctx->refit_device_ms, e0, e1));
@@ -641,15 +680,128 @@ int refit_resident(wgt_ctx* ctx, refit_clock::time_point t0, double extent, cons
 // everything queued there), and its result read back; the stream has drained when it returns, so
 // the refit on the context's stream may read the input.  It writes a scratch word of the
 // context's alone: a refusal leaves the scene as it was.
-int check_on_device(wgt_ctx* ctx, hipStream_t s, const wgt_triangle* d_tris, const MovedVerts& verts, RefitCheck& out) {
+int check_on_device(wgt_ctx* ctx, hipStream_t s, const wgt_triangle* d_tris, uint32_t n_tris, const MovedVerts& verts,
+                    RefitCheck& out) {
   RefitCheck* d_check;
   if (int rc = scratch(ctx, wgt_ctx::kCheck, sizeof(RefitCheck), d_check)) return rc;
   WGT_HIP(ctx, hipMemsetAsync(&d_check->extent_bits, 0, sizeof d_check->extent_bits, s));
   WGT_HIP(ctx, hipMemsetAsync(&d_check->first_bad, 0xff, 2 * sizeof(uint32_t), s));  // kNoBadTriangle
   if (verts.verts) WGT_HIP(ctx, launch_check_verts(verts, d_check, s));
-  else WGT_HIP(ctx, launch_check_tris(d_tris, ctx->sc.n_tris, d_check, s));
+  else WGT_HIP(ctx, launch_check_tris(d_tris, n_tris, d_check, s));
   WGT_HIP(ctx, hipMemcpyAsync(&out, d_check, sizeof out, hipMemcpyDeviceToHost, s));
   WGT_HIP(ctx, hipStreamSynchronize(s));
+  return WGT_OK;
+}
+
+// The refusal of the device check's triangle `i` of the records d_tris, in check_triangle_limits' words.
+int refuse_checked(wgt_ctx* ctx, const wgt_triangle* d_tris, uint32_t n_tris, uint32_t i) {
+  if (i >= n_tris) return fail(ctx, WGT_E_HIP, "the device check named a triangle past the end");
+  wgt_triangle t;
+  WGT_HIP(ctx, hipMemcpy(&t, d_tris + i, sizeof t, hipMemcpyDeviceToHost));
+  const std::string bad = check_triangle_limits(t, i);
+  return fail(ctx, WGT_E_INVALID, bad.empty() ? "triangle " + std::to_string(i) + ": beyond the scene limits" : bad);
+}
+
+// The rebuild that both forms share, after their argument checks: d_tris are n device records that
+// everything queued on `cs` has written, `leaf` the leaf target.  The new tree is made in the spare
+// allocation and swapped in at the end, so a refusal or a HIP failure leaves the scene as it was.
+int rebuild_resident(wgt_ctx* ctx, refit_clock::time_point t0, const wgt_triangle* d_tris, uint32_t n, uint32_t leaf,
+                     hipStream_t cs) {
+  int rc;
+  RefitCheck chk;
+  if ((rc = check_on_device(ctx, cs, d_tris, n, MovedVerts{}, chk))) return rc;
+  if (chk.first_bad != kNoBadTriangle) return refuse_checked(ctx, d_tris, n, chk.first_bad);
+  const double extent = std::max(ctx->fixed_extent, checked_extent(chk));
+  if ((rc = use_drain(ctx))) return rc;  // every launch of the context has ended when the trees are swapped
+  hipStream_t s = ctx->stream;
+  const uint32_t cap = rebuild_node_cap(n);
+  size_t temp_bytes = 0;
+  WGT_HIP(ctx, rebuild_temp_bytes(n, cap, temp_bytes));
+  const RebuildScratch ws = plan_rebuild_scratch(n, temp_bytes);
+  char* w;
+  if ((rc = scratch(ctx, wgt_ctx::kRebuild, ws.bytes, w))) return rc;
+  const int spare = ctx->tree_cur == 0 ? 1 : 0;
+  size_t off[kSceneParts] = {};
+  if ((rc = ensure(ctx, ctx->tree[spare], tree_layout(n, cap, off)))) return rc;
+  DevScene sc = ctx->sc;  // the lights, quads and spheres stay
+  bind_tree(sc, off, ctx->tree[spare].p);
+  // the level lists' buffer is written below: the resident tree's lists are dropped first, so that its
+  // next refit prepares them again should this call fail
+  ctx->level_begin.clear();
+  if ((rc = ensure(ctx, ctx->level_order, ((size_t)cap + 1) * 4))) return rc;
+  uint32_t* d_order = (uint32_t*)ctx->level_order.p;
+  hipEvent_t e0 = pool_event(ctx, 0), e1 = pool_event(ctx, 1);
+  if (!e0 || !e1) return fail(ctx, WGT_E_HIP, "hipEventCreate failed");
+  unsigned long long* d_key[2] = {(unsigned long long*)(w + ws.key[0]), (unsigned long long*)(w + ws.key[1])};
+  uint32_t* d_val[2] = {(uint32_t*)(w + ws.val[0]), (uint32_t*)(w + ws.val[1])};
+  RebuildRange* d_list[2] = {(RebuildRange*)(w + ws.list[0]), (RebuildRange*)(w + ws.list[1])};
+  uint4* d_cuts = (uint4*)(w + ws.cuts);
+  uint32_t *d_count = (uint32_t*)(w + ws.count), *d_offset = (uint32_t*)(w + ws.offset);
+  RebuildBounds* d_bounds = (RebuildBounds*)(w + ws.bounds);
+  RebuildStats* d_stats = (RebuildStats*)(w + ws.stats);
+  const RebuildTree tree{(float4*)sc.nodes, (float4*)sc.tris, (uint4*)sc.cnodes, (uint8_t*)sc.node_level, n, cap, leaf};
+
+  const refit_clock::time_point t1 = refit_clock::now();
+  WGT_HIP(ctx, hipEventRecord(e0, s));
+  WGT_HIP(ctx, hipMemsetAsync(d_bounds->lo, 0xff, sizeof d_bounds->lo, s));
+  WGT_HIP(ctx, hipMemsetAsync(d_bounds->hi, 0, sizeof d_bounds->hi, s));
+  WGT_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof *d_stats, s));
+  WGT_HIP(ctx, launch_rebuild_bounds(d_tris, n, d_bounds, s));
+  WGT_HIP(ctx, launch_rebuild_keys(d_tris, n, d_bounds, d_key[0], d_val[0], s));
+  WGT_HIP(ctx, launch_rebuild_sort(w + ws.temp, temp_bytes, d_key[0], d_key[1], d_val[0], d_val[1], n, s));
+  BvhOut counts;  // the tree's counts, as a build reports them; no BVH2 exists
+  std::vector<uint32_t> level_count;
+  if (n <= leaf) {
+    WGT_HIP(ctx, launch_rebuild_single(tree, d_val[1], s));
+    counts.n_nodes = counts.n_leaves = counts.max_depth = counts.stack_need = 1;
+    counts.max_leaf = n;
+    level_count.push_back(1u);
+  } else {
+    const RebuildRange root{0u, n, 2 * kRebuildLevels, 0u};
+    WGT_HIP(ctx, hipMemcpyAsync(d_list[0], &root, sizeof root, hipMemcpyHostToDevice, s));
+    uint32_t first = 0, count = 1;
+    for (uint32_t level = 0; count != 0; ++level) {
+      if (level >= kRebuildLevels) return fail(ctx, WGT_E_HIP, "rebuild: the tree is deeper than its budget");  // never
+      const RebuildRange* cur = d_list[level & 1u];
+      WGT_HIP(ctx, launch_rebuild_count(d_key[1], cur, count, leaf, d_cuts, d_count, s));
+      WGT_HIP(ctx, launch_rebuild_scan(w + ws.temp, temp_bytes, d_count, d_offset, count, s));
+      uint32_t next = 0;
+      if ((rc = fetch(ctx, &next, d_offset + count, 4)) || (rc = sync_stream(ctx))) return rc;
+      if ((uint64_t)first + count + next > cap) return fail(ctx, WGT_E_HIP, "rebuild: more nodes than triangles");  // never
+      WGT_HIP(ctx, launch_rebuild_write(tree, cur, d_cuts, d_offset, d_val[1], first, count, level, d_list[~level & 1u],
+                                        d_stats, s));
+      level_count.push_back(count);
+      first += count;
+      count = next;
+    }
+    RebuildStats st;
+    if ((rc = fetch(ctx, &st, d_stats, sizeof st)) || (rc = sync_stream(ctx))) return rc;
+    counts.n_nodes = first;
+    counts.n_leaves = st.n_leaves;
+    counts.max_leaf = st.max_leaf;
+    counts.stack_need = st.stack_need;
+    counts.max_depth = (uint32_t)level_count.size();
+    if (st.stack_need > (uint32_t)kStackMax) return fail(ctx, WGT_E_HIP, "rebuild: the stack need exceeds the kernels' limit");  // never
+  }
+  plan_tree_form(counts, n, sc);
+  std::vector<uint32_t> level_begin = level_begin_of(level_count);
+  WGT_HIP(ctx, launch_rebuild_iota(d_order, sc.n_nodes, s));
+  float step;
+  double M;
+  if ((rc = refit_tree(ctx, sc, d_order, level_begin, d_order + sc.n_nodes, extent, d_tris, MovedVerts{}, step, M))) return rc;
+  WGT_HIP(ctx, hipEventRecord(e1, s));
+  WGT_HIP(ctx, hipEventSynchronize(e1));
+  WGT_HIP(ctx, hipEventElapsedTime(&ctx->refit_device_ms, e0, e1));
+  ctx->refit_host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  sc.cstep = counts.cstep = step;
+  sc.rcstep = 1.0f / step;  // a power of two: exact
+  sc.cbound = (float)M;
+  uint32_t resident = 0;
+  WGT_HIP(ctx, ps_resident_waves(sc, ctx->device, resident));
+  // the swap: the old tree's allocation (if it is one of the two) becomes the spare
+  ctx->tree_cur = spare;
+  size_t used[kSceneParts] = {};
+  install_scene(ctx, sc, counts, resident, ctx->fixed_bytes + tree_layout(n, sc.n_nodes, used), std::move(level_begin));
   return WGT_OK;
 }
 
@@ -679,14 +831,8 @@ int wgt_update_triangles_device(wgt_ctx* ctx, const wgt_triangle* d_tris, uint32
   WGT_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = stream_or_own(ctx, stream);
   RefitCheck chk;
-  if (int rc = check_on_device(ctx, s, d_tris, MovedVerts{}, chk)) return rc;
-  if (chk.first_bad != kNoBadTriangle) {
-    if (chk.first_bad >= n_tris) return fail(ctx, WGT_E_HIP, "the device check named a triangle past the end");
-    wgt_triangle t;
-    WGT_HIP(ctx, hipMemcpy(&t, d_tris + chk.first_bad, sizeof t, hipMemcpyDeviceToHost));
-    bad = check_triangle_limits(t, chk.first_bad);
-    return fail(ctx, WGT_E_INVALID, bad.empty() ? "triangle " + std::to_string(chk.first_bad) + ": beyond the scene limits" : bad);
-  }
+  if (int rc = check_on_device(ctx, s, d_tris, n_tris, MovedVerts{}, chk)) return rc;
+  if (chk.first_bad != kNoBadTriangle) return refuse_checked(ctx, d_tris, n_tris, chk.first_bad);
   const double extent = std::max(ctx->fixed_extent, checked_extent(chk));
   return refit_resident(ctx, t0, extent, MovedInput{nullptr, d_tris, MovedVerts{}});
 }
@@ -702,7 +848,7 @@ int wgt_update_vertices_device(wgt_ctx* ctx, const float* d_verts, uint32_t n_ve
   hipStream_t s = stream_or_own(ctx, stream);
   const MovedVerts verts{d_verts, n_verts, d_index, n_tris};
   RefitCheck chk;
-  if (int rc = check_on_device(ctx, s, nullptr, verts, chk)) return rc;
+  if (int rc = check_on_device(ctx, s, nullptr, n_tris, verts, chk)) return rc;
   if (chk.first_bad != kNoBadTriangle) {  // read that triangle back and word the refusal as the host form does
     const uint32_t i = chk.first_bad;
     if (i >= n_tris) return fail(ctx, WGT_E_HIP, "the device check named a triangle past the end");
@@ -721,6 +867,54 @@ int wgt_update_vertices_device(wgt_ctx* ctx, const float* d_verts, uint32_t n_ve
   }
   const double extent = std::max(ctx->fixed_extent, checked_extent(chk));
   return refit_resident(ctx, t0, extent, MovedInput{nullptr, nullptr, verts});
+}
+
+int wgt_rebuild_triangles_device(wgt_ctx* ctx, const wgt_triangle* d_tris, uint32_t n_tris, void* stream) {
+  const refit_clock::time_point t0 = refit_clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  const uint32_t leaf = RebuildLeafFromEnv();
+  const std::string bad = check_rebuild_records(d_tris, n_tris, leaf, true);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  return rebuild_resident(ctx, t0, d_tris, n_tris, leaf, stream_or_own(ctx, stream));
+}
+
+int wgt_rebuild_triangles(wgt_ctx* ctx, const wgt_triangle* tris, uint32_t n_tris) {
+  const refit_clock::time_point t0 = refit_clock::now();
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  if (!ctx->has_scene) return fail(ctx, WGT_E_NOSCENE, "no scene uploaded");
+  const uint32_t leaf = RebuildLeafFromEnv();
+  const std::string bad = check_rebuild_records(tris, n_tris, leaf, false);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  const wgt_triangle* d_tris;  // staged on the context's stream, which the body's check then reads on
+  if (int rc = stage(ctx, wgt_ctx::kMoved, tris, (size_t)n_tris * sizeof(wgt_triangle), d_tris)) return rc;
+  return rebuild_resident(ctx, t0, d_tris, n_tris, leaf, ctx->stream);
+}
+
+int wgt_bvh_build_morton(const wgt_triangle* tris, uint32_t n_tris, float* nodes_out, uint32_t nodes_cap,
+                         float* tris_out, uint32_t* cnodes_out, int32_t* crefs_out, float* step_out,
+                         wgt_scene_info* info) {
+  if (!tris || n_tris == 0 || !info) return fail(nullptr, WGT_E_INVALID, "null triangles or info");
+  // what a rebuild refuses before it builds
+  std::string bad = check_rebuild_records(tris, n_tris, RebuildLeafFromEnv(), false);
+  if (bad.empty()) bad = check_scene_limits(nullptr, 0, nullptr, 0, tris, n_tris);
+  if (!bad.empty()) return fail(nullptr, WGT_E_INVALID, bad);
+  BvhOut bvh;
+  const std::string err = morton_for_export(tris, n_tris, bvh);
+  if (!err.empty()) return fail(nullptr, WGT_E_INVALID, err);
+  *info = wgt_scene_info{};
+  fill_bvh_info(bvh, n_tris, ps_form_for(bvh, n_tris), *info);
+  info->device_bytes = (bvh.nodes.size() + bvh.tris.size() + bvh.tshade.size()) * 4;
+  if ((nodes_out || cnodes_out || crefs_out) && nodes_cap < bvh.n_nodes)
+    return fail(nullptr, WGT_E_INVALID, "node capacity too small");
+  if (nodes_out) std::memcpy(nodes_out, bvh.nodes.data(), bvh.nodes.size() * 4);
+  if (tris_out) std::memcpy(tris_out, bvh.tris.data(), bvh.tris.size() * 4);
+  if (cnodes_out) std::memcpy(cnodes_out, bvh.cnodes.data(), bvh.cnodes.size() * 4);
+  if (crefs_out) std::memcpy(crefs_out, bvh.crefs.data(), bvh.crefs.size() * 4);
+  if (step_out) *step_out = bvh.cstep;
+  return WGT_OK;
 }
 
 int wgt_update_timing(const wgt_ctx* ctx, float* host_ms, float* device_ms) {

@@ -136,6 +136,21 @@ def bvh_refit(built_from, now):
     return info.as_dict(), nodes, recs, cn, cr, step.value
 
 
+def bvh_build_morton(tris):
+    """Host-only specification of a rebuild (wgt_bvh_build_morton): the tree an upload followed by
+    Context.rebuild_triangles(tris) must hold, in bvh_refit's layouts: (info, nodes, leaf-ordered tris,
+    cnodes, crefs, step).  The leaf target is WGT_REBUILD_LEAF's, as the rebuild's."""
+    t = np.ascontiguousarray(tris, TRI_DTYPE)
+    L = lib()
+    info = WgtSceneInfo()
+    step = ctypes.c_float(0.0)
+    check(L.wgt_bvh_build_morton(ptr(t), len(t), None, 0, None, None, None, ctypes.byref(step), ctypes.byref(info)))
+    nodes, recs, cn, cr = _tree_arrays(info.bvh_nodes, len(t))
+    check(L.wgt_bvh_build_morton(ptr(t), len(t), ptr(nodes), info.bvh_nodes, ptr(recs), ptr(cn), ptr(cr),
+                                 ctypes.byref(step), ctypes.byref(info)))
+    return info.as_dict(), nodes, recs, cn, cr, step.value
+
+
 def camera_param(aspect: float, spp: int, seed: int, fovy: float = 40.0, origin=(278.0, 278.0, -800.0),
                  target=(278.0, 278.0, 0.0)):
     """Camera::Update (camera.cpp:64-70) with an explicit seed instead of RandSeed(); origin and
@@ -293,8 +308,29 @@ class Context:
                                                        ctypes.c_void_p(d_index or None), n_tris,
                                                        ctypes.c_void_p(stream or None)))
 
+    def _set_triangle_count(self, n_tris):
+        info = self.scene_info()
+        self.n_prims = info["n_lights"] + info["n_quads"] + n_tris + info["n_spheres"]
+
+    def rebuild_triangles(self, tris):
+        """Replace the scene's triangles by `tris` (any count >= 1) and rebuild their BVH on the device
+        (wgt_rebuild_triangles).  Triangle i gets primitive id n_lights + n_quads + i, so sphere ids move
+        when the count changes.  Synchronous; every render and query afterwards equals a fresh upload's,
+        bit for bit."""
+        tris = np.ascontiguousarray(tris, TRI_DTYPE)
+        self._check(self._L.wgt_rebuild_triangles(self.h, ptr(tris) if len(tris) else None, len(tris)))
+        self._set_triangle_count(len(tris))
+
+    def rebuild_triangles_device(self, d_tris, n_tris, stream=0):
+        """rebuild_triangles from device memory (wgt_rebuild_triangles_device): d_tris is the raw device
+        address of n_tris TRI_DTYPE records, 16-byte aligned.  Synchronous: the records are read after
+        everything queued on `stream` (0 = the context's), and may be overwritten once it returns."""
+        self._check(self._L.wgt_rebuild_triangles_device(self.h, ctypes.c_void_p(d_tris or None), n_tris,
+                                                         ctypes.c_void_p(stream or None)))
+        self._set_triangle_count(n_tris)
+
     def update_timing(self):
-        """(host_ms, device_ms) of the last update, of any form (wgt_update_timing)."""
+        """(host_ms, device_ms) of the last update or rebuild, of any form (wgt_update_timing)."""
         h, d = ctypes.c_float(0.0), ctypes.c_float(0.0)
         self._check(self._L.wgt_update_timing(self.h, ctypes.byref(h), ctypes.byref(d)))
         return h.value, d.value
