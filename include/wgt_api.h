@@ -342,10 +342,38 @@ int wgt_render_frames(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uin
  * waves fill the CUs the previous frame's end-of-launch drain leaves idle), so the
  * caller gives such calls distinct output buffers.  wgt_upload_scene
  * and wgt_destroy wait for every launch of the context before freeing what it
- * reads. */
+ * reads.
+ * Consecutive launches of one view share the pixel queue's order (see "the queue order" below): a
+ * device tile list is identified by its address and n_tiles, so rewriting the tiles' origins behind
+ * an unchanged pointer keeps a stale order (the frames are right, only scheduled worse) until
+ * wgt_order_reset or any change of view. */
 int wgt_render_tiles_async(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,
                            uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
                            void *d_rgba8, float *d_rgba32f, uint32_t *d_hit_id, void *stream);
+/* ---- the queue order across launches of one view (diagnostics) ------------- */
+/* The persistent kernel takes its 8x8 pixel blocks most expensive first, in an order made from a
+ * cheap cost pre-pass.  The order depends on the view (scene, camera, frame and tile geometry, spp,
+ * tuning knobs), not on the seeds, and never changes a pixel.  The first launch of a view makes an
+ * order of its own as every launch did before; the second consecutive one makes the order that is
+ * kept, from a pre-pass of WGT_PQ_REFINE^2 samples per pixel; every later launch of that view reads
+ * it and runs neither pre-pass nor sort, until the view or the scene changes (wgt_upload_scene, the
+ * wgt_update_* and wgt_rebuild_* calls).  Views that alternate or change every frame never reuse.
+ * WGT_PQ_REUSE=0 turns the reuse off.  DESIGN.md §4.2. */
+typedef struct {
+  uint64_t today, refine, reuse; /* launches of the persistent kernel since wgt_create, by how they
+                                  * got their order: their own, made and kept, reused */
+  uint64_t invalidations;        /* times a kept order was dropped by a scene change or a reset */
+  uint32_t nb;                   /* 8x8 blocks of the kept order, 0 when there is none */
+  uint32_t refine_side;          /* side of the pre-pass that made it (samples per pixel = side^2) */
+} wgt_order_stats;
+int wgt_order_info(const wgt_ctx *ctx, wgt_order_stats *out);
+/* Synchronous: copies the kept order, a permutation of [0, nb), to perm_out[0..cap) and sets
+ * *n_out = nb; *n_out = 0 (and nothing copied) when there is none.  WGT_E_INVALID for cap < nb. */
+int wgt_order_read(wgt_ctx *ctx, uint32_t *perm_out, uint32_t cap, uint32_t *n_out);
+/* Drops the kept order: the next launch counts as the first of its view.  For a caller that
+ * rewrites tile origins behind an unchanged device pointer. */
+int wgt_order_reset(wgt_ctx *ctx);
+
 /* Timing pass for the same launch: uninstrumented kernels with a hipEvent pair per
  * launch; fills kernel_ms / trace_ms / shade_ms / iterations (synchronous). */
 int wgt_render_tiles_profile(wgt_ctx *ctx, const wgt_camera_param *cam, uint32_t W, uint32_t H,

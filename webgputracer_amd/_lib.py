@@ -113,6 +113,15 @@ class WgtSceneInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WgtOrderStats(ctypes.Structure):
+    """wgt_order_stats (40 bytes): how the persistent kernel's launches got their queue order."""
+    _fields_ = [("today", ctypes.c_uint64), ("refine", ctypes.c_uint64), ("reuse", ctypes.c_uint64),
+                ("invalidations", ctypes.c_uint64), ("nb", ctypes.c_uint32), ("refine_side", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # Every symbol include/wgt_api.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "wgt_create", "wgt_destroy", "wgt_last_error", "wgt_version", "wgt_build_id", "wgt_device_count",
@@ -136,6 +145,7 @@ EXPORTS = [
     "wgt_render_tile_sampled", "wgt_render_tiles_sampled_async", "wgt_render_gbuffer_sampled",
     "wgt_render_gbuffer_sampled_async",
     "wgt_sample_plan_defaults", "wgt_sample_plan_workspace_bytes", "wgt_sample_plan", "wgt_sample_plan_async",
+    "wgt_order_info", "wgt_order_read", "wgt_order_reset",
 ]
 
 _lib = None
@@ -250,6 +260,9 @@ def lib():
                                 ctypes.POINTER(ctypes.c_uint64)]),
         "wgt_sample_plan_async": (I, [P, ctypes.POINTER(WgtSamplePlanParams), U32, U32,
                                       ctypes.POINTER(WgtTemporalState), P, ctypes.c_size_t, P, P, P]),
+        "wgt_order_info": (I, [P, ctypes.POINTER(WgtOrderStats)]),
+        "wgt_order_read": (I, [P, P, U32, ctypes.POINTER(U32)]),
+        "wgt_order_reset": (I, [P]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -151,6 +151,91 @@ DevFrame tile_frame(const wgt_camera_param& cam, uint32_t W, uint32_t H, uint32_
   return fr;
 }
 
+// WGT_PQ_REFINE: swept over 1, 2 and 4, the fastest on both scenes (DESIGN.md §4.2 item 32,
+// profiles/order_reuse/bench_ab.md)
+OrderKnobs order_knobs() { return OrderKnobs{env_u32("WGT_PQ_REUSE", 1), env_u32("WGT_PQ_REFINE", 4)}; }
+
+uint32_t order_blocks(const DevFrame& fr) {
+  const uint64_t bx = (fr.tw + 7u) / 8u, by = (fr.th + 7u) / 8u;
+  const uint64_t per_tile = bx * by;  // < 2^58
+  if (per_tile > 0x3ffffffull) return 0u;
+  const uint64_t nb = per_tile * fr.n_tiles;  // < 2^58
+  return nb * 64u > 0xffffffffull ? 0u : (uint32_t)nb;
+}
+
+bool order_lpt_on(const DevFrame& fr) { return fr.kernel == 2 && fr.pq_lpt != 0 && fr.sqrt_spp > fr.pq_lpt; }
+
+bool order_eligible(const DevFrame& fr, const OrderKnobs& knobs, bool sampled, uint32_t nb) {
+  return knobs.reuse != 0 && !sampled && nb != 0 && order_lpt_on(fr);
+}
+
+OrderKey order_key(const DevFrame& fr, uint32_t nb, const OrderKnobs& knobs, uint64_t epoch, uint64_t tiles,
+                   bool tiles_by_ptr) {
+  OrderKey k{};
+  k.fr = fr;
+  // what launch_render fills in per launch is no part of the view
+  k.fr.perm = nullptr;
+  k.fr.cost = nullptr;
+  k.fr.ps_spill = nullptr;
+  k.fr.ps_spill_stride = k.fr.n_slots = k.fr.div_bx = k.fr.div_bpt = 0u;
+  k.nb = nb;
+  k.refine = knobs.refine;
+  k.epoch = epoch;
+  k.tiles = tiles;
+  k.tiles_by_ptr = tiles_by_ptr ? 1u : 0u;
+  return k;
+}
+
+bool same_view(const OrderKey& a, const OrderKey& b) {
+  // the frame's 4-byte fields up to its pointers (no padding among them), by their bits: a camera
+  // that differs only in the sign of a zero is another view, which costs one pre-pass
+  static_assert(offsetof(DevFrame, perm) == 34 * 4, "DevFrame's scalar fields, then its pointers");
+  return std::memcmp(&a.fr, &b.fr, offsetof(DevFrame, perm)) == 0 && a.nb == b.nb && a.refine == b.refine &&
+         a.epoch == b.epoch && a.tiles == b.tiles && a.tiles_by_ptr == b.tiles_by_ptr;
+}
+
+uint64_t order_tiles_hash(const wgt_tile* tiles, uint32_t n) {
+  uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a over the origins
+  for (uint32_t i = 0; i < n; ++i)
+    for (const uint32_t v : {tiles[i].x0, tiles[i].y0})
+      for (int b = 0; b < 4; ++b) h = (h ^ ((v >> (8 * b)) & 0xffu)) * 0x100000001b3ull;
+  return h;
+}
+
+void OrderPlanner::invalidate() {
+  ++epoch_;
+  if (cur_ >= 0) ++n_invalid_;
+  cur_ = -1;
+  cur_side_ = 0;
+  seen_ = false;
+}
+
+void OrderPlanner::buffers_reset() {
+  // the kept order is gone with its buffer; the scene is what it was, so the epoch and the run of
+  // sightings stay (the launch that made the buffers grow is the one that refines)
+  if (cur_ >= 0) ++n_invalid_;
+  cur_ = -1;
+  cur_side_ = 0;
+  for (uint32_t& r : readers_) r = 0u;
+}
+
+bool OrderPlanner::refine_due(const OrderKey& key, bool eligible) const {
+  if (!eligible || (cur_ >= 0 && same_view(key, cur_key_))) return false;
+  return seen_ && same_view(key, last_);
+}
+
+void OrderPlanner::launch_failed(const OrderPlan& p) {
+  // a REFINE whose kernels were not queued left no order in its buffer
+  if (p.mode == kOrderRefine && cur_ == p.buf) invalidate();
+}
+
+void OrderPlanner::counts(uint64_t& today, uint64_t& refine, uint64_t& reuse, uint64_t& invalidations) const {
+  today = n_today_;
+  refine = n_refine_;
+  reuse = n_reuse_;
+  invalidations = n_invalid_;
+}
+
 uint32_t stack_entries(const BvhOut& bvh) { return std::max(bvh.stack_need, 1u) + 1u; }
 
 // Waves per SIMD: 6 with 3-byte stack entries when every ref fits them, else 5; WGT_PS_WAVES=5

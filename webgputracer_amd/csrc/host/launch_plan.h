@@ -4,6 +4,8 @@
 // of a scene.  tests/host_sanitize/host_fuzz.cpp runs them without a GPU.
 #pragma once
 
+#include <algorithm>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -239,5 +241,126 @@ SamplePlan plan_sample_plan(const wgt_sample_plan_params& params, uint32_t W, ui
 uint32_t sample_plan_cap(const SamplePlan& plan, const uint32_t* bins, uint64_t& total);
 TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
                            const wgt_camera_param* cam_prev);
+
+// The pixel queue's order across launches of one view.  The LPT order of
+// a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and
+// it shapes the schedule only: any permutation of [0, nb) renders the same pixels.  So the context
+// computes it once per view, into one of kOrderBufs buffers of its own that later launches of the
+// view read, instead of once per launch into the launch's workspace.
+// The knobs, read per launch like make_frame's: WGT_PQ_REUSE (1; 0: every launch orders itself) and
+// WGT_PQ_REFINE, the side of the pre-pass whose order is kept (the launch's own pre-pass runs at pq_lpt).
+struct OrderKnobs {
+  uint32_t reuse, refine;
+};
+OrderKnobs order_knobs();
+// What a launch looks at, without its seeds: make_frame's frame before launch_render fills in its
+// pointers, the launch's 8x8 block count, the planner's scene epoch (OrderPlanner::epoch) and the tile
+// list's identity: a hash of the host tiles' origins (order_tiles_hash) or the device pointer.
+struct OrderKey {
+  DevFrame fr;
+  uint32_t nb, refine;
+  uint64_t epoch, tiles;
+  uint32_t tiles_by_ptr;
+};
+OrderKey order_key(const DevFrame& fr, uint32_t nb, const OrderKnobs& knobs, uint64_t epoch, uint64_t tiles,
+                   bool tiles_by_ptr);
+bool same_view(const OrderKey& a, const OrderKey& b);
+uint64_t order_tiles_hash(const wgt_tile* tiles, uint32_t n);  // x0 and y0 of each; not seed, not frame
+// The launch's 8x8 block count as tile_grid computes it (0: more than the kernels' 32-bit slots hold).
+uint32_t order_blocks(const DevFrame& fr);
+// LPT is on for this launch (launch_render's rule for a plain launch of the persistent kernel).
+bool order_lpt_on(const DevFrame& fr);
+// The launch may share an order: WGT_PQ_REUSE set, no sample map (a sampled frame's costs follow its
+// map, which changes per frame), a block count the kernels accept, LPT on.
+bool order_eligible(const DevFrame& fr, const OrderKnobs& knobs, bool sampled, uint32_t nb);
+
+constexpr int kOrderBufs = 2;
+enum OrderMode : uint32_t {
+  kOrderToday,   // pre-pass at pq_lpt and the sort into the workspace's own order: a launch on its own
+  kOrderRefine,  // pre-pass at `side` and the sort into shared buffer `buf`, which the main kernel reads
+  kOrderReuse    // no pre-pass, no sort: the main kernel reads shared buffer `buf`
+};
+struct OrderPlan {
+  OrderMode mode;
+  int buf;        // the shared buffer (REFINE, REUSE), else -1
+  uint32_t side;  // the pre-pass's side (TODAY: pq_lpt; REUSE: 0)
+};
+// The planner: one per context, called once per launch of the persistent kernel, in launch order.
+// It calls no HIP function: whether a workspace slot's last launch has ended is `slot_done`'s answer
+// (the runtime's is hipEventQuery on the slot's event).
+class OrderPlanner {
+ public:
+  static constexpr int kSlots = 4;  // workspace slots (wgt_ctx::kMaxWsSlots)
+  // key: the launch's view.  eligible: order_eligible's answer; any other launch is TODAY and ends
+  // the run of consecutive sightings.  slot: the workspace slot the launch runs on.
+  // First sighting of a view: TODAY.  Second consecutive one:
+  // REFINE when a shared buffer has no reader left in flight, else TODAY (and the next sighting tries
+  // again).  A launch of the current view: REUSE.
+  template <class SlotDone>
+  OrderPlan plan(const OrderKey& key, bool eligible, int slot, SlotDone&& slot_done) {
+    const uint32_t lpt = key.fr.pq_lpt;
+    if (!eligible || slot < 0 || slot >= kSlots) {
+      seen_ = false;
+      ++n_today_;
+      return OrderPlan{kOrderToday, -1, lpt};
+    }
+    if (cur_ >= 0 && same_view(key, cur_key_)) {
+      readers_[cur_] |= 1u << slot;
+      seen_ = true;
+      last_ = key;
+      ++n_reuse_;
+      return OrderPlan{kOrderReuse, cur_, 0u};
+    }
+    if (seen_ && same_view(key, last_)) {
+      // a buffer may be rewritten once every launch that read it has ended; the other buffer than the
+      // current one first, so that a current order is dropped only when it has to be
+      for (int i = 0; i < kOrderBufs; ++i) {
+        const int b = cur_ >= 0 ? (cur_ + 1 + i) % kOrderBufs : i;
+        uint32_t left = 0;
+        for (int s = 0; s < kSlots; ++s)
+          if ((readers_[b] >> s & 1u) && !slot_done(s)) left |= 1u << s;
+        readers_[b] = left;
+        if (left) continue;
+        readers_[b] = 1u << slot;
+        cur_ = b;
+        cur_key_ = key;
+        // within [pq_lpt, sqrt_spp - 1]: an eligible launch has sqrt_spp > pq_lpt
+        cur_side_ = std::min(std::max(key.refine, lpt), key.fr.sqrt_spp - 1u);
+        ++n_refine_;
+        return OrderPlan{kOrderRefine, b, cur_side_};
+      }
+    }
+    seen_ = true;
+    last_ = key;
+    ++n_today_;
+    return OrderPlan{kOrderToday, -1, lpt};
+  }
+  // The scene changed (upload, refit, rebuild) or the caller asked (wgt_order_reset): no order is
+  // current and the next launch is a first sighting.  The buffers' readers stay: they are launches.
+  void invalidate();
+  // plan() would try a REFINE for this launch (its second consecutive sighting, not the kept view):
+  // the runtime makes room in the shared buffers before it plans, and only then.
+  bool refine_due(const OrderKey& key, bool eligible) const;
+  // The buffers were reallocated after every launch of the context had ended: no order is kept and
+  // no reader is left; the scene epoch and the run of sightings stay.
+  void buffers_reset();
+  // The launch that plan() planned could not be queued: its order is not to be relied on.
+  void launch_failed(const OrderPlan& p);
+  uint64_t epoch() const { return epoch_; }
+  int current() const { return cur_; }
+  const OrderKey& current_key() const { return cur_key_; }
+  uint32_t current_side() const { return cur_side_; }
+  uint32_t readers(int buf) const { return readers_[buf]; }
+  void counts(uint64_t& today, uint64_t& refine, uint64_t& reuse, uint64_t& invalidations) const;
+
+ private:
+  OrderKey last_{}, cur_key_{};
+  bool seen_ = false;
+  int cur_ = -1;
+  uint32_t cur_side_ = 0;
+  uint32_t readers_[kOrderBufs] = {};
+  uint64_t epoch_ = 1;
+  uint64_t n_today_ = 0, n_refine_ = 0, n_reuse_ = 0, n_invalid_ = 0;
+};
 
 }  // namespace wgt

@@ -232,10 +232,19 @@ size_t render_ws_bytes(const DevScene& sc, const DevFrame& fr, uint32_t resident
 // ws_clean_nb: in, the block count whose queues and costs the workspace's previous LPT launch left
 // zero (0: unknown, a memset clears them); out, the same for this launch
 // sm: the sampled frame's map and table (sm.map null: the plain kernels, at fr's uniform spp)
+// order: where the queue order of an LPT launch comes from (the context plans it per view,
+// host/launch_plan.h OrderPlanner); a launch without LPT ignores it.
+struct OrderArgs {
+  uint32_t* shared = nullptr;  // the order, nb words of the context's, that the sort writes (prepass) and the
+                               // main kernel reads; null: the workspace's own (a launch on its own)
+  uint32_t side = 0;           // the pre-pass's samples per pixel are side^2 (0: fr.pq_lpt)
+  bool prepass = true;         // the pre-pass and the sort run; else `shared` holds an order of these nb blocks
+  hipEvent_t sorted = nullptr;  // recorded on the stream right after the sort (prepass; may be null)
+};
 hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                          uchar4* out8, float4* out32, uint32_t* outhit,
                          unsigned long long* counters, uint32_t resident, void* ws, size_t ws_cap,
-                         hipStream_t stream, uint32_t& ws_clean_nb);
+                         hipStream_t stream, uint32_t& ws_clean_nb, const OrderArgs& order = OrderArgs{});
 // The node form k_render_ps reads for this scene and frame (DevFrame::cnode): 0 = 128-B
 // nodes, 1 = 80-B compact records.
 int node_form(const DevScene& sc, const DevFrame& fr);

@@ -537,7 +537,7 @@ size_t render_ws_bytes(const DevScene& sc, const DevFrame& fr, uint32_t resident
 hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                          uchar4* out8, float4* out32, uint32_t* outhit,
                          unsigned long long* counters, uint32_t resident, void* ws, size_t ws_cap,
-                         hipStream_t stream, uint32_t& ws_clean_nb) {
+                         hipStream_t stream, uint32_t& ws_clean_nb, const OrderArgs& order) {
   uint32_t blocks;
   DevFrame fm;  // + slot_setup's division multipliers
   const hipError_t eg = tile_grid(fr, blocks, fm);
@@ -572,27 +572,40 @@ hipError_t launch_render(const DevScene& sc, const DevFrame& fr, const SampleArg
     f.ps_spill_stride = grid.x * kBlock;
     // the queues and costs start at zero: a memset, unless the previous LPT launch on this workspace
     // had the same block count and left them zero (k_lpt_order; ws_clean_nb = nb)
-    hipError_t e = lpt && ws_clean_nb == nb ? hipSuccess : hipMemsetAsync(ws, 0, 256 + (lpt ? 4ull * nb : 0), stream);
-    if (e == hipSuccess && lpt) {
-      DevFrame fc = f;  // the pre-pass: fr.pq_lpt^2 samples per pixel
-      fc.sqrt_spp = fr.pq_lpt < fr.sqrt_spp ? fr.pq_lpt : fr.sqrt_spp;
+    // A launch that reuses its view's order (order.prepass false) runs neither pre-pass nor sort: only
+    // the queue words are zeroed (the previous main kernel on this workspace counted its queue up)
+    const bool reuse = lpt && !order.prepass;
+    if (reuse && !order.shared) return hipErrorInvalidValue;
+    const bool sort = lpt && !reuse;
+    hipError_t e = sort && ws_clean_nb == nb ? hipSuccess : hipMemsetAsync(ws, 0, 256 + (sort ? 4ull * nb : 0), stream);
+    if (e == hipSuccess && sort) {
+      DevFrame fc = f;  // the pre-pass: side^2 samples per pixel (fr.pq_lpt, or the side the order asks for)
+      const uint32_t side = order.side ? order.side : fr.pq_lpt;
+      fc.pq_lpt = side;
+      fc.sqrt_spp = side < fr.sqrt_spp ? side : fr.sqrt_spp;
       fc.recip_sqrt_spp = 1.0f / (float)fc.sqrt_spp;
       fc.fspp = (float)(fc.sqrt_spp * fc.sqrt_spp);
       fc.inv_fspp = pow2_recip(fc.sqrt_spp * fc.sqrt_spp);
       fc.cost = (uint32_t*)((char*)ws + 256);
       fc.n_slots = nb * (fr.pq_lpt_all ? 64u : 16u);  // by default a quarter of each block's pixels estimate its cost
+      uint32_t* perm = order.shared ? order.shared : fc.cost + nb;
       ps_kernel<false, true>(form, cn, sm)<<<grid, block, plds, stream>>>(sc, fc, d_tiles, nullptr, nullptr, nullptr, nullptr, q, fc.ps_spill, sm);
-      k_lpt_order<<<1, kLptThreads, 0, stream>>>(fc.cost, nb, fc.cost + nb, q);
-      f.perm = fc.cost + nb;
+      k_lpt_order<<<1, kLptThreads, 0, stream>>>(fc.cost, nb, perm, q);
+      f.perm = perm;
       e = hipGetLastError();
+      // the order is complete here, a few ms into the launch: what later launches of the view wait for
+      if (e == hipSuccess && order.sorted) e = hipEventRecord(order.sorted, stream);
     }
+    if (reuse) f.perm = order.shared;
     if (e == hipSuccess) {
       const PsKernel k = counters ? ps_kernel<true, false>(form, cn, sm) : ps_kernel<false, false>(form, cn, sm);
       k<<<grid, block, plds, stream>>>(sc, f, d_tiles, out8, out32, outhit, counters, q + 1, f.ps_spill, sm);
       e = hipGetLastError();
     }
-    // after an LPT launch k_lpt_order has left the queues and nb costs zero for the next one
-    ws_clean_nb = e == hipSuccess && lpt ? nb : 0u;
+    // after an LPT launch k_lpt_order has left the queues and nb costs zero for the next one; a launch
+    // that reused an order wrote no cost, so what was known of them stays true
+    if (e != hipSuccess || !lpt) ws_clean_nb = 0u;
+    else if (sort) ws_clean_nb = nb;
     return e;
   }
   const dim3 grid(blocks);

@@ -88,6 +88,14 @@ struct wgt_ctx {
   // full CU mask, which gives it a hardware queue of its own (two plain streams may
   // share one, and launches on one hardware queue never overlap)
   hipStream_t pipe[kMaxWsSlots] = {};
+  // The pixel queue's order per view (launch_plan.h OrderPlanner): the plan of
+  // each launch, the kOrderBufs shared orders of order_cap words each in one allocation, and per
+  // buffer the event recorded right after the sort that wrote it
+  static_assert(kMaxWsSlots == OrderPlanner::kSlots, "the planner tracks readers by workspace slot");
+  OrderPlanner order;
+  DevBuf order_mem;
+  uint32_t order_cap = 0;
+  hipEvent_t order_ev[kOrderBufs] = {};
   // recorded after every other launch that reads the scene (trace queries); each such
   // launch first waits for the previous one.  The scene
   // and the workspaces are freed (re-upload, destroy, regrow) only after this event
@@ -261,11 +269,39 @@ hipEvent_t pool_event(wgt_ctx* ctx, size_t i) {
   return ctx->evpool[i];
 }
 
+// The identity of a launch's tile list for the order's view key: the hash of a host list's origins
+// (the synchronous entry points, which stage it), or a device list's address.
+struct TilesId {
+  uint64_t id;
+  bool by_ptr;
+};
+TilesId tiles_at(const wgt_tile* d_tiles) { return TilesId{(uint64_t)(uintptr_t)d_tiles, true}; }
+TilesId tiles_of(const wgt_tile* host_tiles, uint32_t n) { return TilesId{order_tiles_hash(host_tiles, n), false}; }
+
+// The shared order buffers hold `nb` words each: regrown (both, after every launch of the context
+// has ended) when a launch that is to write one has more blocks than any such launch before it.
+int ensure_order(wgt_ctx* ctx, uint32_t nb) {
+  if (ctx->order_cap >= nb) return WGT_OK;
+  if (int rc = use_drain(ctx)) return rc;
+  free_buf(ctx->order_mem);
+  ctx->order_cap = 0;
+  ctx->order.buffers_reset();
+  const uint32_t cap = (nb + 63u) & ~63u;  // each buffer 256-B aligned
+  WGT_HIP(ctx, hipMalloc(&ctx->order_mem.p, (size_t)kOrderBufs * cap * 4));
+  ctx->order_mem.bytes = (size_t)kOrderBufs * cap * 4;
+  ctx->order_cap = cap;
+  for (hipEvent_t& e : ctx->order_ev)
+    if (!e) WGT_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return WGT_OK;
+}
+uint32_t* order_buf(const wgt_ctx* ctx, int b) { return (uint32_t*)ctx->order_mem.p + (size_t)b * ctx->order_cap; }
+
 // Render the tile list: one launch of the persistent kernel (or, WGT_KERNEL=1, of the
 // simple one), asynchronous on stream s unless timed (ms: the launch's time, waited for).
 // sm: a sampled frame's map and table (sample_args), SampleArgs{} for a plain one.
-int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, uchar4* out8, float4* out32,
-                 uint32_t* outhit, unsigned long long* counters, hipStream_t s, float* ms) {
+// tid: the tile list's identity (the queue order is planned per view, OrderPlanner).
+int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, TilesId tid, uchar4* out8,
+                 float4* out32, uint32_t* outhit, unsigned long long* counters, hipStream_t s, float* ms) {
   const uint64_t n64 = (uint64_t)fr.tw * fr.th * fr.n_tiles;
   if (n64 == 0) return WGT_OK;
   // 32-bit pixel offsets in the kernels (slot_setup)
@@ -280,7 +316,8 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const w
   // rank's share of a frame holds fewer pixels than the device has lanes)
   const uint32_t n_slots = std::min<uint32_t>(std::max<uint32_t>(env_u32("WGT_WS_SLOTS", wgt_ctx::kMaxWsSlots), 1u),
                                               (uint32_t)wgt_ctx::kMaxWsSlots);
-  wgt_ctx::WsSlot& sl = ctx->slots[ctx->next_slot % n_slots];
+  const int slot = (int)(ctx->next_slot % n_slots);
+  wgt_ctx::WsSlot& sl = ctx->slots[slot];
   ctx->next_slot = (ctx->next_slot + 1) % n_slots;
   const size_t ws_need = render_ws_bytes(ctx->sc, fr, ctx->ps_resident);
   if (sl.ws.bytes < ws_need && (rc = use_drain(ctx))) return rc;  // before regrowing
@@ -292,11 +329,41 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const w
   if (sl.ws.p != old_ws || sl.ws.bytes != old_bytes) sl.clean_nb = 0;
   if (!sl.ev) WGT_HIP(ctx, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
   else WGT_HIP(ctx, hipStreamWaitEvent(s, sl.ev, 0));
+  // the queue order: this launch's own (TODAY), or its view's shared one, which it writes (REFINE) or
+  // only reads (REUSE).  A shared buffer is rewritten only when the launches that read it have ended:
+  // they are the last launches of their slots or earlier ones, so the slots' events tell (never a wait)
+  const OrderKnobs knobs = order_knobs();
+  const uint32_t nb = order_blocks(fr);
+  const bool eligible = order_eligible(fr, knobs, sm.map != nullptr, nb);
+  const OrderKey key = order_key(fr, nb, knobs, ctx->order.epoch(), tid.id, tid.by_ptr);
+  // room in the shared buffers only for the launch that would write one: a first sighting and a launch
+  // on its own allocate nothing, and a reusing launch's buffer holds its nb already
+  if (ctx->order.refine_due(key, eligible) && (rc = ensure_order(ctx, nb))) return rc;
+  const OrderPlan op = ctx->order.plan(key, eligible, slot, [&](int i) {
+    if (!ctx->slots[i].ev) return true;
+    const hipError_t q = hipEventQuery(ctx->slots[i].ev);
+    // "not ready" is the answer, not a failure of this launch: it is not left behind as the last error
+    if (q != hipSuccess) (void)hipGetLastError();
+    return q == hipSuccess;
+  });
+  OrderArgs oa;
+  oa.side = op.side;
+  if (op.mode != kOrderToday) oa.shared = order_buf(ctx, op.buf);
+  if (op.mode == kOrderRefine) oa.sorted = ctx->order_ev[op.buf];
+  if (op.mode == kOrderReuse) {
+    oa.prepass = false;
+    // the sort that wrote the order ended a few ms into its own launch: no wait for a main kernel
+    WGT_HIP(ctx, hipStreamWaitEvent(s, ctx->order_ev[op.buf], 0));
+  }
   {
     const hipError_t e = launch_render(ctx->sc, fr, sm, d_tiles, out8, out32, outhit, counters, ctx->ps_resident,
-                                       sl.ws.p, sl.ws.bytes, s, sl.clean_nb);
+                                       sl.ws.p, sl.ws.bytes, s, sl.clean_nb, oa);
     if (e != hipSuccess) {
+      ctx->order.launch_failed(op);
       sl.clean_nb = 0;
+      // part of the launch may be queued (a pre-pass and a sort into a shared buffer): the slot's event
+      // covers it, so that the planner's reader of this slot is not taken for ended too early
+      (void)hipEventRecord(sl.ev, s);
       return fail(ctx, WGT_E_HIP, std::string("launch_render: ") + hipGetErrorString(e));
     }
   }
@@ -310,12 +377,12 @@ int render_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const w
 }
 
 // The counting pass of a launch (the instrumented kernels) over the tile list d_tiles, read back.
-int count_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, wgt_stats* stats) {
+int count_frame(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles, TilesId tid, wgt_stats* stats) {
   int rc;
   unsigned long long c[CNT_N], *d_c;
   if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
   WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
-  if ((rc = render_frame(ctx, fr, sm, d_tiles, nullptr, nullptr, nullptr, d_c, ctx->stream, nullptr))) return rc;
+  if ((rc = render_frame(ctx, fr, sm, d_tiles, tid, nullptr, nullptr, nullptr, d_c, ctx->stream, nullptr))) return rc;
   if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
   fill_stats(c, stats);
   return WGT_OK;
@@ -385,6 +452,7 @@ void install_scene(wgt_ctx* ctx, const DevScene& sc, const BvhOut& bvh, uint32_t
                    std::vector<uint32_t> level_begin) {
   // a new scene: the workspaces' scheduling words are re-zeroed by the next launch's memset
   for (auto& sl : ctx->slots) sl.clean_nb = 0;
+  ctx->order.invalidate();  // and its views' orders are the old scene's
   ctx->level_begin = std::move(level_begin);
   free_buf(ctx->motion);  // the old scene's snapshot: no launch reads it any more
   ctx->has_snapshot = false;
@@ -469,6 +537,9 @@ void wgt_destroy(wgt_ctx* ctx) {
   free_buf(ctx->level_order);
   free_buf(ctx->motion);
   free_buf(ctx->sample_tab);
+  free_buf(ctx->order_mem);
+  for (hipEvent_t e : ctx->order_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& sl : ctx->slots) {
     if (sl.ev) (void)hipEventSynchronize(sl.ev);
     free_buf(sl.ws);
@@ -660,6 +731,7 @@ int refit_resident(wgt_ctx* ctx, refit_clock::time_point t0, double extent, cons
   const refit_clock::time_point t1 = refit_clock::now();
   // from here on the resident tree changes: a HIP failure leaves it undefined until the next upload
   for (auto& sl : ctx->slots) sl.clean_nb = 0;  // as an upload
+  ctx->order.invalidate();
   WGT_HIP(ctx, hipEventRecord(e0, s));
   float step;
   double M;
@@ -975,12 +1047,43 @@ int wgt_scene_info_get(const wgt_ctx* ctx, wgt_scene_info* info) {
   return WGT_OK;
 }
 
+int wgt_order_info(const wgt_ctx* ctx, wgt_order_stats* out) {
+  if (!ctx || !out) return fail(nullptr, WGT_E_INVALID, "null argument");
+  *out = wgt_order_stats{};
+  ctx->order.counts(out->today, out->refine, out->reuse, out->invalidations);
+  if (ctx->order.current() >= 0) {
+    out->nb = ctx->order.current_key().nb;
+    out->refine_side = ctx->order.current_side();
+  }
+  return WGT_OK;
+}
+
+int wgt_order_read(wgt_ctx* ctx, uint32_t* perm_out, uint32_t cap, uint32_t* n_out) {
+  if (!ctx || !n_out) return fail(ctx, WGT_E_INVALID, "null argument");
+  *n_out = 0;
+  const int b = ctx->order.current();
+  if (b < 0) return WGT_OK;
+  const uint32_t nb = ctx->order.current_key().nb;
+  if (!perm_out || cap < nb) return fail(ctx, WGT_E_INVALID, "order capacity too small");
+  WGT_HIP(ctx, hipSetDevice(ctx->device));
+  WGT_HIP(ctx, hipEventSynchronize(ctx->order_ev[b]));  // the sort that wrote it
+  WGT_HIP(ctx, hipMemcpy(perm_out, order_buf(ctx, b), (size_t)nb * 4, hipMemcpyDeviceToHost));
+  *n_out = nb;
+  return WGT_OK;
+}
+
+int wgt_order_reset(wgt_ctx* ctx) {
+  if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
+  ctx->order.invalidate();
+  return WGT_OK;
+}
+
 int wgt_render_tiles_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H,
                            uint32_t tw, uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles,
                            void* d_rgba8, float* d_rgba32f, uint32_t* d_hit_id, void* stream) {
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, nullptr));
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
-  return render_frame(ctx, fr, SampleArgs{}, d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
+  return render_frame(ctx, fr, SampleArgs{}, d_tiles, tiles_at(d_tiles), (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
                       stream_or_own(ctx, stream), nullptr);
 }
 
@@ -988,7 +1091,7 @@ int wgt_render_tiles_stats(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W
                            uint32_t tw, uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles,
                            wgt_stats* stats) {
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, true, stats, nullptr));
-  return count_frame(ctx, tile_frame(*cam, W, H, tw, th, n_tiles), SampleArgs{}, d_tiles, stats);
+  return count_frame(ctx, tile_frame(*cam, W, H, tw, th, n_tiles), SampleArgs{}, d_tiles, tiles_at(d_tiles), stats);
 }
 
 int wgt_render_tiles_profile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H,
@@ -998,7 +1101,8 @@ int wgt_render_tiles_profile(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t
   int rc;
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, nullptr, nullptr, nullptr, nullptr, ctx->stream, &ms))) return rc;
+  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, tiles_at(d_tiles), nullptr, nullptr, nullptr, nullptr, ctx->stream, &ms)))
+    return rc;
   if ((rc = sync_stream(ctx))) return rc;
   fill_timing(ms, stats);
   return WGT_OK;
@@ -1022,7 +1126,8 @@ int wgt_render_frames(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uin
   if ((rc = stage(ctx, wgt_ctx::kTiles, tl.data(), n_frames * sizeof(wgt_tile), d_tiles))) return rc;
   const DevFrame fr = tile_frame(*cam, W, H, W, H, n_frames);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, d_out8, nullptr, nullptr, nullptr, ctx->stream, stats ? &ms : nullptr)))
+  if ((rc = render_frame(ctx, fr, SampleArgs{}, d_tiles, tiles_of(tl.data(), n_frames), d_out8, nullptr, nullptr, nullptr,
+                         ctx->stream, stats ? &ms : nullptr)))
     return rc;
   if ((rc = fetch(ctx, rgba8_out, d_out8, npx * n_frames * 4)) || (rc = sync_stream(ctx))) return rc;
   return stats ? stats_of_render(ctx, cam, W, H, W, H, n_frames, ms, stats) : WGT_OK;
@@ -1079,7 +1184,8 @@ int render_tile(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uint32
   }
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, 1);
   float ms = 0.0f;
-  if ((rc = render_frame(ctx, fr, sm, d_tile, d_out8, d_out32, d_hit, nullptr, ctx->stream, stats ? &ms : nullptr)))
+  if ((rc = render_frame(ctx, fr, sm, d_tile, tiles_of(&tile, 1), d_out8, d_out32, d_hit, nullptr, ctx->stream,
+                         stats ? &ms : nullptr)))
     return rc;
   if (d_out8 && (rc = fetch(ctx, rgba8_out, d_out8, npx * 4))) return rc;
   if (d_out32 && (rc = fetch(ctx, rgba32f_out, d_out32, npx * 16))) return rc;
@@ -1088,7 +1194,7 @@ int render_tile(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uint32
   if (!stats) return WGT_OK;
   if (!sampled) return stats_of_render(ctx, cam, W, H, tw, th, 1, ms, stats);
   std::memset(stats, 0, sizeof *stats);
-  if ((rc = count_frame(ctx, fr, sm, d_tile, stats))) return rc;
+  if ((rc = count_frame(ctx, fr, sm, d_tile, tiles_of(&tile, 1), stats))) return rc;
   fill_timing(ms, stats);
   return WGT_OK;
 }
@@ -1119,7 +1225,8 @@ int wgt_render_tiles_sampled_async(wgt_ctx* ctx, const wgt_camera_param* cam, ui
   }
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, check_sample_map(d_sample_map)));
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
-  return render_frame(ctx, fr, sample_args(ctx, d_sample_map), d_tiles, (uchar4*)d_rgba8, (float4*)d_rgba32f, d_hit_id, nullptr,
+  return render_frame(ctx, fr, sample_args(ctx, d_sample_map), d_tiles, tiles_at(d_tiles), (uchar4*)d_rgba8, (float4*)d_rgba32f,
+                      d_hit_id, nullptr,
                       stream_or_own(ctx, stream), nullptr);
 }
 

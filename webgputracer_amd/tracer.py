@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
-                   WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
+                   WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
 COL_WHITE = np.array([0.73, 0.73, 0.73], np.float32)  # color_util.h:8
 MESH_KINDS = {"bunny": (0, 69451), "sponza": (1, 262267)}
@@ -392,6 +392,25 @@ class Context:
                                                    n_tiles, ctypes.c_void_p(d_u8 or None),
                                                    ctypes.c_void_p(d_f32 or None), ctypes.c_void_p(d_hit or None),
                                                    ctypes.c_void_p(stream or None)))
+
+    def order_info(self):
+        """How the persistent kernel's launches got their queue order since the context was made
+        (wgt_order_info): counts of today / refine / reuse launches and of invalidations, and the kept
+        order's block count and pre-pass side (0 when none is kept)."""
+        st = WgtOrderStats()
+        self._check(self._L.wgt_order_info(self.h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def order_read(self):
+        """The kept queue order (wgt_order_read): a uint32 permutation of range(nb), empty when none is kept."""
+        out = np.zeros(max(self.order_info()["nb"], 1), np.uint32)
+        n = ctypes.c_uint32(0)
+        self._check(self._L.wgt_order_read(self.h, ptr(out), len(out), ctypes.byref(n)))
+        return out[:n.value]
+
+    def order_reset(self):
+        """Drop the kept queue order (wgt_order_reset): the next launch is the first of its view."""
+        self._check(self._L.wgt_order_reset(self.h))
 
     def render_tiles_stats(self, cam, W, H, tw, th, d_tiles, n_tiles):
         st = WgtStats()
