@@ -214,3 +214,26 @@ def test_2p20_triangles_get_5_waves():
     info, _, _ = w.bvh_build(am.clusters(am.CLUSTERS_2P20M8 + 1))
     assert info["n_tris"] == 1 << 20 and info["bvh_nodes"] < 1 << 16
     assert info["ps_waves"] == 5
+
+
+def test_rebuilt_trees_go_deeper_than_the_smallest_lds_stack():
+    """tests/test_gpu_rebuild_adversarial.py runs these meshes through the tree of a rebuild
+    (wgt_bvh_build_morton).  Its parked-cap8 form tests a spill only if primary rays of some mesh's
+    frames reach a stack top above 8 in that tree: the host walk over the restated camera rays
+    (test_gpu_gbuffer.camera_rays) shows it for geometric_up and copies300, within the tree's bound."""
+    from test_gpu_gbuffer import camera_rays
+
+    deep = {}
+    for name in am.GPU:
+        built = w.bvh_build_morton(am.small_mesh(name))[:3]
+        tr = ss.Tree(None, built=built)
+        assert built[0]["bvh_max_depth"] <= 10 and tr.stack <= 31
+        top = 0
+        for _, cam in am.cameras(name):
+            ro, rd = camera_rays(cam, am.W, am.H)
+            top = max(top, int(am.push_walk(tr, ro.reshape(-1, 3), rd.reshape(-1, 3))["depth"].max()))
+        print(f"{name}: {built[0]['bvh_nodes']} nodes, depth {built[0]['bvh_max_depth']}, stack {built[0]['bvh_stack']}, "
+              f"deepest primary stack top {top}")
+        assert top <= tr.stack
+        deep[name] = top
+    assert deep["geometric_up"] > 8 and deep["copies300"] > 8

@@ -10,6 +10,9 @@ entry (Stack24).
 Expected values: the C oracle bit for bit (its brute-force scan for the queries, which
 tests/test_bvh_adversarial.py shows equal to its BVH), tests/hit_records.py for whole records, and
 float64 geometry (tests/f64_truth.py) on the decided rays of the four meshes that have any.
+
+The query, render and G-buffer tests are bodies that take the way the mesh's tree is installed:
+here an upload (the SAH tree), in tests/test_gpu_rebuild_adversarial.py a rebuild on the device.
 """
 import numpy as np
 import pytest
@@ -30,7 +33,7 @@ FORMS = {"default": {}, "128B": {"WGT_CNODE": "0"}, "simple": {"WGT_KERNEL": "1"
 SHARE = {"geometric_up": 0.95, "huge_tiny": 0.95, "degenerate": 0.60, "slivers": 0.60}
 MESH_SHARE = 0.30  # of a frame's pixels, first hits on the mesh
 
-_SCENES, _RENDERS = {}, {}
+_SCENES, _RENDERS, _QUERIES = {}, {}, {}
 
 
 def _scene(oracle, name):
@@ -98,16 +101,33 @@ def _check_normals(name, truth, rec, T, nlq):
     return float(nerr[j] / allowed[j])
 
 
-@pytest.mark.parametrize("name", am.GPU)
-def test_queries(ctx, oracle, name):
-    """trace_rays, trace_hits and occluded on 4,000 rays: the oracle's brute-force prim and dist bits,
-    hit_records' restatement of every field, occlusion at 0.5 x and 2 x the oracle's distance; on
-    the truth meshes float64 geometry on the decided rays of the first 2,000; on the tie meshes
-    the winner's index itself."""
-    (L, Q, S, T), osc, nlq = _scene(oracle, name)
+def _query_reference(oracle, name):
+    """The rays of a mesh with what does not depend on the tree, computed once: the oracle's brute-force
+    (prim, dist), hit_records' restatement of every field, and on the truth meshes the float64 scan of
+    the first 2,000 rays."""
+    if name not in _QUERIES:
+        (L, Q, S, T), osc, nlq = _scene(oracle, name)
+        o, d = _query_rays(name)
+        rp, rd = osc.trace(o, d, brute=True)
+        want, is_tri = hr.expected_records(osc, L, Q, S, T, o, d)
+        truth = ft.scan(o[:2000], d[:2000], L, Q, S, T) if name in am.TRUTH else None
+        _QUERIES[name] = (o, d, rp, rd, want, is_tri, truth)
+    return _QUERIES[name]
+
+
+def upload(ctx, L, Q, S, T):
+    """install: a fresh upload, the SAH tree."""
     ctx.upload_scene(L, Q, S, T)
-    o, d = _query_rays(name)
-    rp, rd = osc.trace(o, d, brute=True)
+
+
+def queries_body(ctx, oracle, name, install):
+    """trace_rays, trace_hits and occluded on 4,000 rays through the tree that install(ctx, L, Q, S, T)
+    leaves: the oracle's brute-force prim and dist bits, hit_records' restatement of every field,
+    occlusion at 0.5 x and 2 x the oracle's distance; on the truth meshes float64 geometry on the
+    decided rays of the first 2,000; on the tie meshes the winner's index itself."""
+    (L, Q, S, T), osc, nlq = _scene(oracle, name)
+    install(ctx, L, Q, S, T)
+    o, d, rp, rd, want, is_tri, truth = _query_reference(oracle, name)
     gp, gd = ctx.trace_rays(o, d)
     assert np.array_equal(gp, rp), f"{int(np.sum(gp != rp))} prims differ; first: ray {np.flatnonzero(gp != rp)[0]}"
     # a NaN distance (the dummy sphere under a ray with |d| |o - c| beyond 1.8e19, f64_truth.sphere_terms;
@@ -115,7 +135,6 @@ def test_queries(ctx, oracle, name):
     nan = np.isnan(rd)
     assert np.array_equal(np.isnan(gd), nan) and np.array_equal(hr.bits(gd)[~nan], hr.bits(rd)[~nan])
     assert nan.sum() == 0 or name == "geometric_up"
-    want, is_tri = hr.expected_records(osc, L, Q, S, T, o, d)
     assert np.array_equal(want["prim"], rp)
     got = ctx.trace_hits(o, d)
     # assert_records_equal compares NaN fields loosely only on rays it takes for NaN rays: name those
@@ -137,7 +156,6 @@ def test_queries(ctx, oracle, name):
         assert (tid < 2048).all()  # the lower of the two duplicates
     if name in am.TRUTH:
         k = slice(0, 2000)
-        truth = ft.scan(o[k], d[k], L, Q, S, T)
         share = ft.check_share(name, truth, SHARE[name])
         worst = ft.check_closest(f"{name}: trace_rays", truth, gp[k], dist32=gd[k])
         rec = {f: got[f][k] for f in ("pos", "norm", "flags")}
@@ -146,26 +164,44 @@ def test_queries(ctx, oracle, name):
         print(f"{name}: decided {share:.3f}, max error / E_t {worst:.3f}, pos {pos_r:.3f}, norm error / allowed {norm_r:.3f}")
 
 
-@pytest.mark.parametrize("form", list(FORMS))
 @pytest.mark.parametrize("name", am.GPU)
-def test_render(ctx, oracle, name, form, monkeypatch):
-    """One 48 x 27 frame at 4 spp (geometric_up: two) against the oracle under each stack form: the
-    radiance and hit ids bit for bit, the counters (stack_overflows == 0), at least 30 % of the
-    pixels on the mesh; on geometric_up the forms whose LDS stack is smaller than the tree's bound
-    spill.  scene_info's node_form is the upload's (the reference camera's): both cameras of
-    geometric_up are inside the compact codes' bound of 4 x the scene's extent."""
+def test_queries(ctx, oracle, name):
+    """queries_body on the uploaded tree."""
+    queries_body(ctx, oracle, name, upload)
+
+
+def uploaded_tree(ctx, name, form, info):
+    """tree: what test_render states about the SAH tree of an upload, from the scene report."""
+    if name == "geometric_up":
+        assert info["bvh_stack"] == 31 or (form == "narrow" and info["bvh_stack"] <= 25)
+
+
+def uploaded_spills(ctx, name, form, info, spills):
+    """spilled: on geometric_up the forms whose LDS stack is smaller than the tree's bound spill."""
+    if name == "geometric_up" and info["ps_park"]:
+        assert info["ps_stack"] < info["bvh_stack"] + 1 and spills > 0
+
+
+def render_body(ctx, oracle, name, form, monkeypatch, install, tree, spilled):
+    """One 48 x 27 frame at 4 spp (geometric_up: two) against the oracle under each stack form, through
+    the tree that install(ctx, L, Q, S, T) leaves: the radiance and hit ids bit for bit, the counters
+    (stack_overflows == 0), at least 30 % of the pixels on the mesh.  What depends on the tree is the
+    caller's: tree(ctx, name, form, info) with the scene report after the install, and spilled(ctx,
+    name, form, info, spills) with the frames' stack spills.  scene_info's node_form is the upload's
+    (the reference camera's): both cameras of geometric_up are inside the compact codes' bound of 4 x
+    the scene's extent."""
     env = FORMS[form]
     _set_env(monkeypatch, env)
     (L, Q, S, T), _, nlq = _scene(oracle, name)
-    ctx.upload_scene(L, Q, S, T)
+    install(ctx, L, Q, S, T)
     info = ctx.scene_info()
     assert info["ps_waves"] == (5 if form == "5waves" else 6) and info["ps_park"] == (1 if "WGT_PARK" in env else 0)
     if form == "parked-cap8":
         assert info["ps_stack"] == 8
     if not info["ps_park"]:
         assert info["ps_stack"] == info["bvh_stack"] + 1  # the whole stack in LDS, no bound check
+    tree(ctx, name, form, info)
     if name == "geometric_up":
-        assert info["bvh_stack"] == 31 or (form == "narrow" and info["bvh_stack"] <= 25)
         assert info["node_form"] == (0 if form == "128B" else 1)
     spills = refills = 0
     for tag, cam in am.cameras(name):
@@ -180,19 +216,25 @@ def test_render(ctx, oracle, name, form, monkeypatch):
         refills += g["stats"]["stack_refills"]
         print(f"{name} {tag} {form}: on the mesh {share:.3f}, traced rays {g['stats']['traced_rays']}, "
               f"spills {g['stats']['stack_spills']}, refills {g['stats']['stack_refills']}")
-    if name == "geometric_up" and info["ps_park"]:
-        assert info["ps_stack"] < info["bvh_stack"] + 1 and spills > 0
+    spilled(ctx, name, form, info, spills)
     if not info["ps_park"] or form == "simple":
         assert spills == 0 and refills == 0
 
 
+@pytest.mark.parametrize("form", list(FORMS))
 @pytest.mark.parametrize("name", am.GPU)
-def test_gbuffer(ctx, oracle, name, monkeypatch):
-    """render_gbuffer(rays=True) of the same frames: prim is the oracle's hit id, and every field
-    equals trace_hits on the returned rays."""
+def test_render(ctx, oracle, name, form, monkeypatch):
+    """render_body on the uploaded tree: geometric_up meets the stack bound exactly (31; the narrow tree
+    at most 25), and on it the forms whose LDS stack is smaller than the tree's bound spill."""
+    render_body(ctx, oracle, name, form, monkeypatch, upload, uploaded_tree, uploaded_spills)
+
+
+def gbuffer_body(ctx, oracle, name, monkeypatch, install):
+    """render_gbuffer(rays=True) of the same frames through the tree that install leaves: prim is the
+    oracle's hit id, and every field equals trace_hits on the returned rays."""
     _set_env(monkeypatch, {})
     (L, Q, S, T), _, nlq = _scene(oracle, name)
-    ctx.upload_scene(L, Q, S, T)
+    install(ctx, L, Q, S, T)
     for tag, cam in am.cameras(name):
         g = ctx.render_gbuffer(cam, W, H, rays=True)
         assert np.array_equal(g["prim"], _oracle_render(oracle, name, tag, cam)["hit"])
@@ -200,6 +242,12 @@ def test_gbuffer(ctx, oracle, name, monkeypatch):
         got = {k: g[k].reshape((-1, 3) if g[k].ndim == 3 else (-1,)) for k in hr.FIELDS}
         hr.assert_records_equal(got, ctx.trace_hits(ro, rd), ro, rd, what=f"{name} {tag}")
         assert _mesh_share(g["prim"], nlq, len(T)) >= MESH_SHARE
+
+
+@pytest.mark.parametrize("name", am.GPU)
+def test_gbuffer(ctx, oracle, name, monkeypatch):
+    """gbuffer_body on the uploaded tree."""
+    gbuffer_body(ctx, oracle, name, monkeypatch, upload)
 
 
 def _limit_camera(name):

@@ -3,8 +3,9 @@
 The closest hit does not depend on the tree, so after a rebuild every render and query must equal a
 fresh upload's bit for bit; and the device tree itself must equal the host specification
 (wgt_bvh_build_morton) bit for bit.  Meshes: tests/rebuild_cases.py; scenes, camera and rays:
-tests/test_gpu_refit.py; device tensors: tests/test_gpu_refit_device.py.  The largest mesh has 3000
-triangles, every case takes milliseconds.
+tests/test_gpu_refit.py; device tensors: tests/test_gpu_refit_device.py.  The largest mesh has 4096
+triangles, every case takes milliseconds; larger trees, the other leaf targets and the limits of the
+kernel forms are in tests/test_gpu_rebuild_scale.py.
 """
 import functools
 
@@ -111,13 +112,11 @@ def _assert_everything_equal(got, want, what):
     assert np.array_equal(got[4], want[4]), (what, "occlusion")
 
 
-@pytest.mark.parametrize("form", ["default", "WGT_KERNEL=1"])
-def test_everything_equals_a_fresh_upload(ctx, fresh, wgt, monkeypatch, form):
-    """2. upload(A) then rebuild(B) against a fresh context's upload(B), B of another count than A: a
+def everything_equals_a_fresh_upload(ctx, fresh, wgt, form):
+    """upload(A) then rebuild(B) against a fresh context's upload(B), B of another count than A: a
     32x32, 4 spp Cornell-plus-mesh frame (f32 words, u8, hit ids), a sampled frame with a non-uniform
-    map, the G-buffer, hit records and occlusion answers of 4096 seeded rays, and the stats' ray counts."""
-    if form != "default":
-        monkeypatch.setenv(*form.split("="))
+    map, the G-buffer, hit records and occlusion answers of 4096 seeded rays, and the stats' ray counts.
+    The knobs in force are the caller's; `form` names them in the messages."""
     A, B = rc.mesh("nine"), _shaded(rc.mesh("bunny2000"), 2)
     L, Q, S = host_form._walls(wgt)
     W = H = 32
@@ -135,6 +134,14 @@ def test_everything_equals_a_fresh_upload(ctx, fresh, wgt, monkeypatch, form):
     got = _everything(ctx, cam, W, H, o, d, lim)
     _assert_everything_equal(got, want, form)
     print(f"{form}: node visits rebuilt {got[0]['stats']['node_visits']}, uploaded {want[0]['stats']['node_visits']}")
+
+
+@pytest.mark.parametrize("form", ["default", "WGT_KERNEL=1"])
+def test_everything_equals_a_fresh_upload(ctx, fresh, wgt, monkeypatch, form):
+    """2. everything_equals_a_fresh_upload under the default kernel and the simple one."""
+    if form != "default":
+        monkeypatch.setenv(*form.split("="))
+    everything_equals_a_fresh_upload(ctx, fresh, wgt, form)
 
 
 def test_count_goes_down_and_up(ctx, fresh, wgt):
