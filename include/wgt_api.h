@@ -29,6 +29,7 @@
  *   (none: the sides planned from the variance)       wgt_sample_plan
  *   Scene::InitBuffers again, for a changed mesh      wgt_rebuild_triangles, wgt_rebuild_triangles_device
  *                                                     (a new BVH made on the device, any triangle count)
+ *   (none: the triangle nearest to a point)           wgt_nearest_points (closest-point query)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -491,6 +492,51 @@ int wgt_render_gbuffer_sampled_async(wgt_ctx *ctx, const wgt_camera_param *cam, 
                                      uint32_t tw, uint32_t th, const wgt_tile *d_tiles, uint32_t n_tiles,
                                      const uint8_t *d_sample_map, const wgt_hit_buffers *d_out, float *d_rays,
                                      void *stream);
+
+/* ---- closest-point queries (no reference counterpart; Embree's rtcPointQuery) -- */
+/* Planar outputs for n records; any pointer may be NULL (that field is not written), at least one
+ * must be set. */
+typedef struct {
+  uint32_t *prim;  /* n */
+  float *dist;     /* n */
+  float *pos;      /* 3 planes of n: the closest point q */
+  float *uv;       /* 2 planes of n: the weights (v, w) of e1 and e2 */
+} wgt_nearest_buffers;   /* 32 bytes */
+
+/* Record i = the triangle of the scene nearest to point i (points: 3 planes of n floats, x, y, z):
+ * the minimum of (d2, primitive id) over the scene's triangles, d2 the fp32 squared distance to the
+ * closest point q = (v0 + v e1) + w e2 of the triangle's resident record (after an upload the
+ * caller's v0, e1, e2; after wgt_update_* or a rebuild what wgt_bvh_read's tris_out returns), by the
+ * seven-region test stated operation by operation in DESIGN.md §4.13; ties go to the lower id, a
+ * triangle whose d2 is NaN or infinite is never the answer.  prim as wgt_trace_rays numbers triangles,
+ * dist = sqrt(d2) correctly rounded.  The record is reported iff dist < max_dist[i] (an IEEE f32
+ * comparison: a NaN, zero or negative limit reports nothing, +inf or a NULL max_dist anything);
+ * otherwise, and for a point with a NaN or infinite component or a scene without triangles, it is the
+ * miss record: prim = 0xffffffff, dist = +inf, pos = 0, uv = 0.  Only triangles are searched: no quads,
+ * lights or spheres; no signed distance; one nearest triangle, not k or all within the radius.
+ * The answers equal wgt_nearest_points_spec on the resident triangles bit for bit; the BVH and the
+ * radius only cull (DESIGN.md §4.13 states for which triangle shapes that is proved).
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
+ * WGT_E_NOSCENE; n == 0 (success, nothing done); NULL points; NULL out or an out without a field.  n has
+ * no limit of its own, as wgt_trace_rays' has none.  Pointers are not validated.
+ * The synchronous form takes host pointers and stages through the context's scratch; the async form
+ * takes device pointers and a host struct of device pointers, and follows wgt_trace_rays_async's rules:
+ * ordered on `stream` (NULL = the context's) after every earlier query, update and rebuild of the
+ * context, returns once queued. */
+int wgt_nearest_points(wgt_ctx *ctx, const float *points, const float *max_dist, uint32_t n,
+                       const wgt_nearest_buffers *out);
+int wgt_nearest_points_async(wgt_ctx *ctx, const float *d_points, const float *d_max_dist, uint32_t n,
+                             const wgt_nearest_buffers *d_out, void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation;
+ * counts[0] = node visits, counts[1] = triangle tests, summed over the n points.  NULL counts is
+ * refused last. */
+int wgt_nearest_points_stats(wgt_ctx *ctx, const float *d_points, const float *d_max_dist, uint32_t n,
+                             const wgt_nearest_buffers *d_out, uint64_t counts[2]);
+/* Host only, no device: the definition by brute force over tris[0..n_tris) in index order, primitive
+ * ids first_prim + i.  n_tris == 0 gives misses.  WGT_E_INVALID for NULL tris with n_tris > 0, NULL
+ * points, a NULL or empty out (n == 0 succeeds first). */
+int wgt_nearest_points_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *points,
+                            const float *max_dist, uint32_t n, const wgt_nearest_buffers *out);
 
 /* ---- denoising (no reference counterpart) --------------------------------- */
 /* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered W x H image, guided

@@ -38,6 +38,14 @@ class WgtHitBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in HIT_FIELDS]
 
 
+NEAREST_FIELDS = ("prim", "dist", "pos", "uv")
+
+
+class WgtNearestBuffers(ctypes.Structure):
+    """wgt_nearest_buffers (32 bytes): planar outputs of the closest-point queries (None / 0 = not written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in NEAREST_FIELDS]
+
+
 WGT_DENOISE_DEMODULATE = 1  # wgt_denoise_params.flags
 
 
@@ -146,6 +154,7 @@ EXPORTS = [
     "wgt_render_gbuffer_sampled_async",
     "wgt_sample_plan_defaults", "wgt_sample_plan_workspace_bytes", "wgt_sample_plan", "wgt_sample_plan_async",
     "wgt_order_info", "wgt_order_read", "wgt_order_reset",
+    "wgt_nearest_points", "wgt_nearest_points_async", "wgt_nearest_points_stats", "wgt_nearest_points_spec",
 ]
 
 _lib = None
@@ -263,6 +272,11 @@ def lib():
         "wgt_order_info": (I, [P, ctypes.POINTER(WgtOrderStats)]),
         "wgt_order_read": (I, [P, P, U32, ctypes.POINTER(U32)]),
         "wgt_order_reset": (I, [P]),
+        "wgt_nearest_points": (I, [P, P, P, U32, ctypes.POINTER(WgtNearestBuffers)]),
+        "wgt_nearest_points_async": (I, [P, P, P, U32, ctypes.POINTER(WgtNearestBuffers), P]),
+        "wgt_nearest_points_stats": (I, [P, P, P, U32, ctypes.POINTER(WgtNearestBuffers),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_nearest_points_spec": (I, [P, U32, U32, P, P, U32, ctypes.POINTER(WgtNearestBuffers)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -853,4 +853,60 @@ TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32
   return p;
 }
 
+const char* check_nearest_args(const void* points, const wgt_nearest_buffers* out, uint64_t n) {
+  if (!points) return "null points";
+  if (!out) return "null output buffers";
+  if (!out->prim && !out->dist && !out->pos && !out->uv) return "no nearest field asked for";
+  if (n > kNearestMaxPoints) return "too many points";
+  return nullptr;
+}
+
+NearestStage plan_nearest_stage(const wgt_nearest_buffers& out, bool has_radius, uint32_t n) {
+  NearestStage s{};
+  const size_t N = n;
+  s.points = N * 12;
+  s.limits = has_radius ? N * 4 : 0;
+  s.prim = out.prim ? N * 4 : 0;
+  s.dist = out.dist ? N * 4 : 0;
+  s.uv_at = out.pos ? 3 * N : 0;
+  s.vec = (s.uv_at + (out.uv ? 2 * N : 0)) * 4;
+  return s;
+}
+
+void nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
+                         const float* max_dist, uint32_t n, const wgt_nearest_buffers& out) {
+  const size_t N = n;
+  const float inf = __builtin_inff();
+  for (size_t i = 0; i < N; ++i) {
+    const f3 p{points[i], points[N + i], points[2 * N + i]};
+    float best = inf;
+    uint32_t bi = kNoHit;
+    NearestTri b{};
+    for (uint32_t k = 0; k < n_tris; ++k) {
+      const wgt_triangle& t = tris[k];
+      const NearestTri c = nearest_on_tri(p, f3{t.v0[0], t.v0[1], t.v0[2]}, f3{t.e1[0], t.e1[1], t.e1[2]},
+                                          f3{t.e2[0], t.e2[1], t.e2[2]});
+      // in index order the tie rule never fires (k only grows); it is the definition all the same
+      if (nearest_better(c.d2, k, best, bi)) {
+        best = c.d2;
+        bi = k;
+        b = c;
+      }
+    }
+    const float dist = sqrt_rn(best);
+    const bool hit = nearest_reported(bi, dist, max_dist ? max_dist[i] : inf);
+    if (out.prim) out.prim[i] = hit ? first_prim + bi : kNoHit;
+    if (out.dist) out.dist[i] = hit ? dist : inf;
+    if (out.pos) {
+      out.pos[i] = hit ? b.q.x : 0.0f;
+      out.pos[N + i] = hit ? b.q.y : 0.0f;
+      out.pos[2 * N + i] = hit ? b.q.z : 0.0f;
+    }
+    if (out.uv) {
+      out.uv[i] = hit ? b.v : 0.0f;
+      out.uv[N + i] = hit ? b.w : 0.0f;
+    }
+  }
+}
+
 }  // namespace wgt

@@ -13,6 +13,7 @@
 #include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
 #include "../wgt_motion.h"
+#include "../wgt_nearest.h"
 #include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
 #include "../wgt_temporal.h"
@@ -241,6 +242,24 @@ SamplePlan plan_sample_plan(const wgt_sample_plan_params& params, uint32_t W, ui
 uint32_t sample_plan_cap(const SamplePlan& plan, const uint32_t* bins, uint64_t& total);
 TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
                            const wgt_camera_param* cam_prev);
+
+// The closest-point queries (wgt_nearest_points and its forms).  Their own checks
+// after the context, the scene and n == 0, in the calls' order: null points; null out or an out without
+// a field; n above kNearestMaxPoints, which no uint32_t is: the ray queries put no limit on n, and the
+// kernel's 64-bit plane offsets need none.  Returns the refusal's text, null when fine.
+constexpr uint64_t kNearestMaxPoints = 0xffffffffull;
+const char* check_nearest_args(const void* points, const wgt_nearest_buffers* out, uint64_t n);
+// What the synchronous form stages in the context's scratch for the fields `out` asks for: the byte
+// counts of the points, the limits (0 without a radius), prim, dist, and pos | uv as one buffer with uv
+// at float offset uv_at.
+struct NearestStage {
+  size_t points, limits, prim, dist, vec, uv_at;
+};
+NearestStage plan_nearest_stage(const wgt_nearest_buffers& out, bool has_radius, uint32_t n);
+// wgt_nearest_points_spec: the definition by brute force (wgt_nearest.h) over tris[0..n_tris) in index
+// order for the n points, ids first_prim + index; writes the fields `out` asks for.
+void nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
+                         const float* max_dist, uint32_t n, const wgt_nearest_buffers& out);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

@@ -271,6 +271,13 @@ hipError_t launch_trace_hits(const DevScene& sc, const float* d_rays, uint32_t n
 hipError_t launch_gbuffer(const DevScene& sc, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                           const wgt_hit_buffers& out, float* d_rays, hipStream_t stream);
 
+// Launcher implemented in wgt_nearest.hip
+// Record i = the scene's triangle nearest to point i (k_nearest; d_points: three planes of n floats;
+// d_max_dist may be null: no radius); out: device pointers, a null field is not written.  d_counts
+// (may be null) selects the counting instantiation: += node visits, triangle tests.
+hipError_t launch_nearest(const DevScene& sc, const float* d_points, const float* d_max_dist, uint32_t n,
+                          const wgt_nearest_buffers& out, unsigned long long* d_counts, hipStream_t stream);
+
 // The scene limits of coordinates and of triangle edge components (host/launch_plan.h states why),
 // here because the device check of moved triangles applies them as the host's check_scene_limits does.
 constexpr double kCoordLimit = 1099511627776.0;  // 2^40

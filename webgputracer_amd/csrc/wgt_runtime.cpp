@@ -397,6 +397,11 @@ int occluded_launch(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, 
 int hits_launch(wgt_ctx* ctx, const float* d_rays, uint32_t n, const wgt_hit_buffers& dev, hipStream_t s) {
   return launch_on(ctx, s, "launch_trace_hits", [&] { return launch_trace_hits(ctx->sc, d_rays, n, dev, s); });
 }
+int nearest_launch(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n,
+                   const wgt_nearest_buffers& dev, unsigned long long* d_counts, hipStream_t s) {
+  return launch_on(ctx, s, "launch_nearest",
+                   [&] { return launch_nearest(ctx->sc, d_points, d_max_dist, n, dev, d_counts, s); });
+}
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                    const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
@@ -1286,6 +1291,60 @@ int wgt_trace_hits(wgt_ctx* ctx, const float* rays, uint32_t n, const wgt_hit_bu
   if ((rc = hits_launch(ctx, d_rays, n, dev, ctx->stream))) return rc;
   if ((rc = fetch_hits(ctx, *out, dev, n))) return rc;
   return sync_stream(ctx);
+}
+
+int wgt_nearest_points_async(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n,
+                             const wgt_nearest_buffers* d_out, void* stream) {
+  WGT_BEGIN(query_begin(ctx, n, check_nearest_args(d_points, d_out, n)));
+  return nearest_launch(ctx, d_points, d_max_dist, n, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_nearest_points(wgt_ctx* ctx, const float* points, const float* max_dist, uint32_t n,
+                       const wgt_nearest_buffers* out) {
+  WGT_BEGIN(query_begin(ctx, n, check_nearest_args(points, out, n)));
+  const NearestStage st = plan_nearest_stage(*out, max_dist != nullptr, n);
+  wgt_nearest_buffers dev{};
+  const float *d_points, *d_limit = nullptr;
+  float* d_vec = nullptr;
+  int rc;
+  if (st.prim && (rc = scratch(ctx, wgt_ctx::kPrim, st.prim, dev.prim))) return rc;
+  if (st.dist && (rc = scratch(ctx, wgt_ctx::kDist, st.dist, dev.dist))) return rc;
+  if (st.vec && (rc = scratch(ctx, wgt_ctx::kHitVec, st.vec, d_vec))) return rc;
+  if (out->pos) dev.pos = d_vec;
+  if (out->uv) dev.uv = d_vec + st.uv_at;
+  if ((rc = stage(ctx, wgt_ctx::kRays, points, st.points, d_points))) return rc;
+  if (max_dist && (rc = stage(ctx, wgt_ctx::kOccLimit, max_dist, st.limits, d_limit))) return rc;
+  if ((rc = nearest_launch(ctx, d_points, d_limit, n, dev, nullptr, ctx->stream))) return rc;
+  if (out->prim && (rc = fetch(ctx, out->prim, dev.prim, st.prim))) return rc;
+  if (out->dist && (rc = fetch(ctx, out->dist, dev.dist, st.dist))) return rc;
+  if (out->pos && (rc = fetch(ctx, out->pos, dev.pos, (size_t)n * 12))) return rc;
+  if (out->uv && (rc = fetch(ctx, out->uv, dev.uv, (size_t)n * 8))) return rc;
+  return sync_stream(ctx);
+}
+
+int wgt_nearest_points_stats(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n,
+                             const wgt_nearest_buffers* d_out, uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;  // what n == 0 leaves
+  const char* bad = check_nearest_args(d_points, d_out, n);
+  WGT_BEGIN(query_begin(ctx, n, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[2], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = nearest_launch(ctx, d_points, d_max_dist, n, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  counts[0] = c[0];
+  counts[1] = c[1];
+  return WGT_OK;
+}
+
+int wgt_nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
+                            const float* max_dist, uint32_t n, const wgt_nearest_buffers* out) {
+  if (n == 0) return WGT_OK;
+  if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
+  if (const char* bad = check_nearest_args(points, out, n)) return fail(nullptr, WGT_E_INVALID, bad);
+  nearest_points_spec(tris, n_tris, first_prim, points, max_dist, n, *out);
+  return WGT_OK;
 }
 
 int wgt_render_gbuffer_async(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw,

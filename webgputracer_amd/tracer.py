@@ -7,6 +7,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   Renderer::InitDevice / OnRender dispatch  -> Context.render_tile / render_tiles_async
   sample_hit (path_tracer.wgsl:290-310)     -> Context.trace_rays, Context.occluded (dist < a limit)
   HitInfo (path_tracer.wgsl:27-36)          -> Context.trace_hits, Context.render_gbuffer (whole records)
+  (none: the triangle nearest to a point)   -> Context.nearest_points, nearest_points_spec (host brute force)
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, NEAREST_FIELDS, WgtNearestBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
@@ -175,6 +176,41 @@ def _ray_soa(start, direction):
 def _device_hit_buffers(*fields):
     """wgt_hit_buffers of raw device addresses, in HIT_FIELDS' order (0 = field not written)."""
     return WgtHitBuffers(*(f or None for f in fields))
+
+
+def _nearest_arrays(want, n):
+    """Host arrays of the closest-point fields in `want` (planar: pos (3, n), uv (2, n)) and their struct."""
+    bad = set(want) - set(NEAREST_FIELDS)
+    if bad:
+        raise ValueError(f"unknown nearest field(s) {sorted(bad)}; choose from {NEAREST_FIELDS}")
+    shape = {"prim": (n,), "dist": (n,), "pos": (3, n), "uv": (2, n)}
+    arr = {k: np.zeros(shape[k], np.uint32 if k == "prim" else np.float32) for k in NEAREST_FIELDS if k in want}
+    return arr, WgtNearestBuffers(**{k: a.ctypes.data for k, a in arr.items()})
+
+
+def _nearest_inputs(points, max_dist):
+    """The closest-point queries' input: 3 planes of n floats, the limits (a scalar broadcasts) or None, n."""
+    points = np.asarray(points, np.float32).reshape(-1, 3)
+    n = len(points)
+    lim = None if max_dist is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float32), (n,)))
+    return np.ascontiguousarray(points.T), lim, n
+
+
+def _nearest_dict(arr):
+    """Vectors last: pos (n, 3), uv (n, 2)."""
+    return {k: np.ascontiguousarray(a.T) if k in ("pos", "uv") else a for k, a in arr.items()}
+
+
+def nearest_points_spec(tris, points, max_dist=None, first_prim=0, want=NEAREST_FIELDS):
+    """The closest-point query's definition by brute force on the host (wgt_nearest_points_spec, no
+    device): for each point the nearest of `tris` (TRI_DTYPE, ids first_prim + index), as
+    Context.nearest_points returns it for a scene that holds these triangles."""
+    tris = np.ascontiguousarray(tris, TRI_DTYPE)
+    soa, lim, n = _nearest_inputs(points, max_dist)
+    arr, bufs = _nearest_arrays(want, n)
+    check(lib().wgt_nearest_points_spec(ptr(tris) if len(tris) else None, len(tris), first_prim, ptr(soa), ptr(lim), n,
+                                        ctypes.byref(bufs)))
+    return _nearest_dict(arr)
 
 
 def build_id() -> str:
@@ -483,6 +519,34 @@ class Context:
         bufs = _device_hit_buffers(prim, dist, pos, norm, col, flags)
         self._check(self._L.wgt_trace_hits_async(self.h, ctypes.c_void_p(d_rays), n, ctypes.byref(bufs),
                                                  ctypes.c_void_p(stream or None)))
+
+    def nearest_points(self, points, max_dist=None, want=NEAREST_FIELDS):
+        """Closest-point query (wgt_nearest_points): for each point the scene's nearest triangle, a dict of
+        the fields in `want`: prim (n,) uint32 as trace_rays numbers triangles, dist (n,), pos (n, 3) the
+        closest point, uv (n, 2) its weights of e1 and e2.  max_dist (scene units; a scalar broadcasts;
+        None = no radius): a record is reported iff dist < max_dist, else prim = 0xffffffff, dist = inf,
+        zeros.  Equals nearest_points_spec on the resident triangles bit for bit."""
+        soa, lim, n = _nearest_inputs(points, max_dist)
+        arr, bufs = _nearest_arrays(want, n)
+        self._check(self._L.wgt_nearest_points(self.h, ptr(soa), ptr(lim), n, ctypes.byref(bufs)))
+        return _nearest_dict(arr)
+
+    def nearest_points_async(self, d_points, n, d_max_dist=0, prim=0, dist=0, pos=0, uv=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_points 3 planes of n floats, d_max_dist
+        n floats or 0; pos receives 3 planes of n floats, uv 2."""
+        bufs = WgtNearestBuffers(prim or None, dist or None, pos or None, uv or None)
+        self._check(self._L.wgt_nearest_points_async(self.h, ctypes.c_void_p(d_points or None),
+                                                     ctypes.c_void_p(d_max_dist or None), n, ctypes.byref(bufs),
+                                                     ctypes.c_void_p(stream or None)))
+
+    def nearest_points_stats(self, d_points, n, d_max_dist=0, prim=0, dist=0, pos=0, uv=0):
+        """The same answers from the counting kernel (wgt_nearest_points_stats; synchronous, device
+        pointers): -> (node visits, triangle tests) summed over the n points."""
+        bufs = WgtNearestBuffers(prim or None, dist or None, pos or None, uv or None)
+        counts = (ctypes.c_uint64 * 2)()
+        self._check(self._L.wgt_nearest_points_stats(self.h, ctypes.c_void_p(d_points or None),
+                                                     ctypes.c_void_p(d_max_dist or None), n, ctypes.byref(bufs), counts))
+        return int(counts[0]), int(counts[1])
 
     def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False, sample_map=None):
         """First-hit G-buffer (wgt_render_gbuffer): the hit record of sample 0's primary ray of each
