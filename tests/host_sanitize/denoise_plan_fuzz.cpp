@@ -2,7 +2,7 @@
 // built and run by tests/test_denoise_sanitize.py): the argument checks in their order, the
 // workspace size and layout, and each pass's kz (launch_plan.h check_denoise_args,
 // check_denoise_workspace, denoise_workspace_bytes, plan_denoise) over seeded random and boundary
-// arguments.  Exits non-zero on a failed invariant; the sanitizers abort on the first finding.
+// arguments, and the synchronous form's staging layout (stage_denoise; stage_check.h).  Exits non-zero on a failed invariant; the sanitizers abort on the first finding.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -15,6 +15,7 @@
 
 #include "../../include/wgt_api.h"
 #include "../../webgputracer_amd/csrc/host/launch_plan.h"
+#include "stage_check.h"
 
 static int g_fail = 0;
 #define CHECK(c)                                                         \
@@ -116,8 +117,34 @@ static void fuzz() {
   }
 }
 
+// wgt_denoise's staging layout (stage_denoise): seeded sizes and the largest the checks accept (as
+// arithmetic: nothing is allocated), with every combination of outputs that passes them.
+static void fuzz_stage() {
+  std::mt19937 g(11);
+  for (int round = 0; round < 300; ++round) {
+    const uint32_t W = round ? 1 + g() % 70 : 32768, H = round ? 1 + g() % 70 : 1024;
+    CHECK(size_ok(W, H));
+    const uint64_t n = (uint64_t)W * H;
+    wgt_hit_buffers gb{};
+    gb.prim = (uint32_t*)fake_ptr(1); gb.pos = (float*)fake_ptr(2); gb.norm = (float*)fake_ptr(3);
+    gb.col = (float*)fake_ptr(4); gb.flags = (uint8_t*)fake_ptr(5);
+    gb.dist = (float*)fake_ptr(6);  // ignored
+    for (int o = 1; o < 4; ++o) {
+      void* const o32 = o & 1 ? fake_ptr(7) : nullptr;
+      void* const o8 = o & 2 ? fake_ptr(8) : nullptr;
+      // the image is filtered in place: its part is the rgba32f output's too
+      const StageWant want[] = {{n * 16, fake_ptr(0), o32}, {n * 4, gb.prim, nullptr}, {n * 12, gb.pos, nullptr},
+                                {n * 12, gb.norm, nullptr}, {n * 12, gb.col, nullptr}, {n, gb.flags, nullptr},
+                                {o8 ? n * 4 : 0, nullptr, o8}, {wgt::denoise_workspace_bytes(W, H), nullptr, nullptr}};
+      static_assert(sizeof want / sizeof *want == wgt::kDnsParts, "one per part");
+      g_fail += check_stage("stage_denoise", wgt::stage_denoise(W, H, fake_ptr(0), gb, o32, o8), want, wgt::kDnsParts);
+    }
+  }
+}
+
 int main() {
   fuzz();
+  fuzz_stage();
   if (g_fail) {
     std::fprintf(stderr, "denoise_plan_fuzz: %d checks failed\n", g_fail);
     return 1;

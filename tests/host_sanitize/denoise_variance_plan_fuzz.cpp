@@ -2,7 +2,8 @@
 // AddressSanitizer + UBSan (CPU only; built and run by tests/test_denoise_variance_sanitize.py): the
 // argument checks in their order, the workspace size and layout, each pass's kz and min_history as a
 // float (launch_plan.h check_denoise_variance_args, check_denoise_variance_workspace,
-// denoise_variance_workspace_bytes, plan_denoise_variance) over seeded random and boundary arguments.
+// denoise_variance_workspace_bytes, plan_denoise_variance) over seeded random and boundary arguments,
+// and the synchronous form's staging layout (stage_denoise_variance; stage_check.h).
 // Exits non-zero on a failed invariant; the sanitizers abort on the first finding.
 #include <algorithm>
 #include <cmath>
@@ -16,6 +17,7 @@
 
 #include "../../include/wgt_api.h"
 #include "../../webgputracer_amd/csrc/host/launch_plan.h"
+#include "stage_check.h"
 
 static int g_fail = 0;
 #define CHECK(c)                                                         \
@@ -145,8 +147,40 @@ static void fuzz() {
   }
 }
 
+// wgt_denoise_variance's staging layout (stage_denoise_variance): seeded sizes and the largest the checks
+// accept (as arithmetic: nothing is allocated), with every combination of outputs that passes them.
+static void fuzz_stage() {
+  std::mt19937 g(12);
+  for (int round = 0; round < 300; ++round) {
+    const uint32_t W = round ? 1 + g() % 70 : 32768, H = round ? 1 + g() % 70 : 1024;
+    CHECK(size_ok(W, H));
+    const uint64_t n = (uint64_t)W * H;
+    const wgt_temporal_state st{(float*)fake_ptr(0), (float*)fake_ptr(1), (float*)fake_ptr(2)};
+    wgt_hit_buffers gb{};
+    gb.prim = (uint32_t*)fake_ptr(3); gb.pos = (float*)fake_ptr(4); gb.norm = (float*)fake_ptr(5);
+    gb.col = (float*)fake_ptr(6); gb.flags = (uint8_t*)fake_ptr(7);
+    gb.dist = (float*)fake_ptr(8);  // ignored
+    for (int o = 1; o < 8; ++o) {
+      if (!(o & 3)) continue;  // a colour output is required
+      void* const o32 = o & 1 ? fake_ptr(9) : nullptr;
+      void* const o8 = o & 2 ? fake_ptr(10) : nullptr;
+      void* const var = o & 4 ? fake_ptr(11) : nullptr;
+      // the state's image is filtered in place: its part is the rgba32f output's too
+      const StageWant want[] = {{n * 16, st.rgba32f, o32}, {n * 4, st.len, nullptr}, {n * 8, st.moments, nullptr},
+                                {n * 4, gb.prim, nullptr}, {n * 12, gb.pos, nullptr}, {n * 12, gb.norm, nullptr},
+                                {n * 12, gb.col, nullptr}, {n, gb.flags, nullptr}, {o8 ? n * 4 : 0, nullptr, o8},
+                                {var ? n * 4 : 0, nullptr, var},
+                                {wgt::denoise_variance_workspace_bytes(W, H), nullptr, nullptr}};
+      static_assert(sizeof want / sizeof *want == wgt::kDvsParts, "one per part");
+      g_fail += check_stage("stage_denoise_variance", wgt::stage_denoise_variance(W, H, st, gb, o32, o8, var), want,
+                            wgt::kDvsParts);
+    }
+  }
+}
+
 int main() {
   fuzz();
+  fuzz_stage();
   if (g_fail) {
     std::fprintf(stderr, "denoise_variance_plan_fuzz: %d checks failed\n", g_fail);
     return 1;

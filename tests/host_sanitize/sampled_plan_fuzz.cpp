@@ -3,7 +3,8 @@
 // checks in their documented order (launch_plan.h check_sample_map after check_frame_args with spp
 // taken as 1; check_sample_plan_args, check_sample_plan_workspace), the plan (the budget in double,
 // the workspace layout), the budget cap from a histogram against a brute-force search, and the table
-// of the sides' constants against make_frame.  Exits non-zero on a failed invariant; the sanitizers
+// of the sides' constants against make_frame, and wgt_sample_plan's staging layout (stage_sample_plan;
+// stage_check.h).  Exits non-zero on a failed invariant; the sanitizers
 // abort on the first finding.
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 
 #include "../../include/wgt_api.h"
 #include "../../webgputracer_amd/csrc/host/launch_plan.h"
+#include "stage_check.h"
 
 static int g_fail = 0;
 #define CHECK(c)                                                         \
@@ -177,11 +179,32 @@ static void fuzz_cap() {
   }
 }
 
+// wgt_sample_plan's staging layout (stage_sample_plan): seeded sizes and the largest the checks accept
+// (as arithmetic: nothing is allocated), with and without total_out.
+static void fuzz_stage() {
+  std::mt19937 g(13);
+  for (int round = 0; round < 300; ++round) {
+    const uint32_t W = round ? 1 + g() % 70 : 32768, H = round ? 1 + g() % 70 : 1024;
+    const uint64_t n = (uint64_t)W * H;
+    CHECK(wgt::sample_plan_workspace_bytes(W, H) != 0);
+    const wgt_temporal_state st{(float*)fake_ptr(0), (float*)fake_ptr(1), (float*)fake_ptr(2)};  // rgba32f: ignored
+    for (int o = 0; o < 2; ++o) {
+      void* const total = o ? fake_ptr(4) : nullptr;
+      // the pass is always handed a total to write: its 8 bytes are there, fetched or not
+      const StageWant want[] = {{n * 4, st.len, nullptr}, {n * 8, st.moments, nullptr}, {n, nullptr, fake_ptr(3)},
+                                {8, nullptr, total}, {wgt::sample_plan_workspace_bytes(W, H), nullptr, nullptr}};
+      static_assert(sizeof want / sizeof *want == wgt::kSpsParts, "one per part");
+      g_fail += check_stage("stage_sample_plan", wgt::stage_sample_plan(W, H, st, fake_ptr(3), total), want, wgt::kSpsParts);
+    }
+  }
+}
+
 int main() {
   check_sampled_order();
   check_constants();
   fuzz_plan_args();
   fuzz_cap();
+  fuzz_stage();
   if (g_fail) {
     std::fprintf(stderr, "sampled_plan_fuzz: %d failed checks\n", g_fail);
     return 1;

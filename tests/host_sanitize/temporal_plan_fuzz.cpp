@@ -2,7 +2,8 @@
 // (CPU only; built and run by tests/test_temporal_sanitize.py): the argument checks in their order
 // and the cameras' projection constants (launch_plan.h check_temporal_args, temporal_camera,
 // plan_temporal) over seeded random and boundary arguments: overlapping ranges, sizes at the limits,
-// NaN parameters, degenerate cameras.  Exits non-zero on a failed invariant; the sanitizers abort on
+// NaN parameters, degenerate cameras; and the synchronous forms' staging layout (stage_temporal;
+// stage_check.h).  Exits non-zero on a failed invariant; the sanitizers abort on
 // the first finding.
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,7 @@
 
 #include "../../include/wgt_api.h"
 #include "../../webgputracer_amd/csrc/host/launch_plan.h"
+#include "stage_check.h"
 
 static int g_fail = 0;
 #define CHECK(c)                                                         \
@@ -206,8 +208,51 @@ static void fuzz() {
   }
 }
 
+// The accumulation's staging layout (stage_temporal), both forms: seeded sizes and the largest the checks
+// accept (as arithmetic: nothing is allocated); first frame or not, moments or not, rgba8_out or not.
+static void fuzz_stage() {
+  std::mt19937 g(14);
+  for (int round = 0; round < 300; ++round) {
+    const uint32_t W = round ? 1 + g() % 70 : 32768, H = round ? 1 + g() % 70 : 1024;
+    CHECK(size_ok(W, H));
+    const uint64_t n = (uint64_t)W * H;
+    wgt_hit_buffers gb{}, gp{};
+    gb.prim = (uint32_t*)fake_ptr(1); gb.pos = (float*)fake_ptr(2); gb.norm = (float*)fake_ptr(3); gb.flags = (uint8_t*)fake_ptr(4);
+    gb.col = (float*)fake_ptr(20);  // ignored
+    gp.prim = (uint32_t*)fake_ptr(8); gp.pos = (float*)fake_ptr(9); gp.norm = (float*)fake_ptr(10); gp.flags = (uint8_t*)fake_ptr(11);
+    const wgt_motion_buffers mb{(float*)fake_ptr(12), (float*)fake_ptr(13)};
+    for (int o = 0; o < 16; ++o) {
+      const bool first = o & 1, mom = o & 2, motion_form = o & 8;
+      void* const o8 = o & 4 ? fake_ptr(17) : nullptr;
+      const wgt_temporal_state prev{(float*)fake_ptr(5), (float*)fake_ptr(6), mom ? (float*)fake_ptr(7) : nullptr};
+      const wgt_temporal_state out{(float*)fake_ptr(14), (float*)fake_ptr(15), mom ? (float*)fake_ptr(16) : nullptr};
+      // the motion form's first frame does not look at its motion buffers: the runtime passes none
+      const bool mot = motion_form && !first;
+      const uint64_t p = first ? 0 : n, m = mot ? n : 0;
+      // the image is accumulated in place: its part is out->rgba32f's too
+      const StageWant want[] = {{n * 16, fake_ptr(0), out.rgba32f}, {n * 4, gb.prim, nullptr}, {n * 12, gb.pos, nullptr},
+                                {n * 12, gb.norm, nullptr}, {n, gb.flags, nullptr}, {p * 16, prev.rgba32f, nullptr},
+                                {p * 4, prev.len, nullptr}, {mom ? p * 8 : 0, prev.moments, nullptr},
+                                {p * 4, gp.prim, nullptr}, {p * 12, gp.pos, nullptr}, {p * 12, gp.norm, nullptr},
+                                {p, gp.flags, nullptr}, {m * 12, mb.pos_prev, nullptr}, {m * 12, mb.norm_prev, nullptr},
+                                {n * 4, nullptr, out.len}, {mom ? n * 8 : 0, nullptr, out.moments},
+                                {o8 ? n * 4 : 0, nullptr, o8}};
+      static_assert(sizeof want / sizeof *want == wgt::kTpsParts, "one per part");
+      g_fail += check_stage("stage_temporal",
+                            wgt::stage_temporal(W, H, fake_ptr(0), gb, mot ? &mb : nullptr, first ? nullptr : &prev,
+                                                first ? nullptr : &gp, out, o8),
+                            want, wgt::kTpsParts);
+      // a first frame's layout is the same whatever stands in for the buffers it does not look at
+      if (first)
+        g_fail += check_stage("stage_temporal (first frame, stale buffers)",
+                              wgt::stage_temporal(W, H, fake_ptr(0), gb, &mb, nullptr, &gp, out, o8), want, wgt::kTpsParts);
+    }
+  }
+}
+
 int main() {
   fuzz();
+  fuzz_stage();
   if (g_fail) {
     std::fprintf(stderr, "temporal_plan_fuzz: %d checks failed\n", g_fail);
     return 1;

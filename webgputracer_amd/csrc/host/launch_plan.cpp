@@ -853,6 +853,58 @@ TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32
   return p;
 }
 
+// A layout of the parts in order; a part of no bytes has no source and no destination either.
+static StageLayout stage_of(const char* what, std::initializer_list<StagePart> parts) {
+  StageLayout l;
+  l.what = what;
+  for (const StagePart& p : parts) {
+    l.part[l.n] = p.bytes ? p : StagePart{};
+    l.off[l.n + 1] = l.off[l.n] + align_up(p.bytes, kDenoiseAlign);
+    ++l.n;
+  }
+  return l;
+}
+
+StageLayout stage_sample_plan(uint32_t W, uint32_t H, const wgt_temporal_state& state, void* map_out, void* total_out) {
+  const size_t n = (size_t)W * H;
+  // the total's 8 bytes are always there: the pass is handed a total to write, fetched or not
+  return stage_of("a sample plan", {{n * 4, state.len, nullptr}, {n * 8, state.moments, nullptr}, {n, nullptr, map_out},
+                                    {8, nullptr, total_out}, {sample_plan_workspace_bytes(W, H), nullptr, nullptr}});
+}
+
+StageLayout stage_denoise(uint32_t W, uint32_t H, const void* in, const wgt_hit_buffers& g, void* out32, void* out8) {
+  const size_t n = (size_t)W * H;
+  return stage_of("a denoiser", {{n * 16, in, out32}, {n * 4, g.prim, nullptr}, {n * 12, g.pos, nullptr},
+                                 {n * 12, g.norm, nullptr}, {n * 12, g.col, nullptr}, {n, g.flags, nullptr},
+                                 {out8 ? n * 4 : 0, nullptr, out8}, {denoise_workspace_bytes(W, H), nullptr, nullptr}});
+}
+
+StageLayout stage_temporal(uint32_t W, uint32_t H, const void* in, const wgt_hit_buffers& g,
+                           const wgt_motion_buffers* motion, const wgt_temporal_state* prev,
+                           const wgt_hit_buffers* gp, const wgt_temporal_state& out, void* out8) {
+  // p, m: the pixels of the previous frame's parts and of the motion buffers' (0: absent, nothing is read)
+  const size_t n = (size_t)W * H, p = prev ? n : 0, m = prev && motion ? n : 0, pm = out.moments ? p : 0;
+  const wgt_temporal_state sp = p ? *prev : wgt_temporal_state{};
+  const wgt_hit_buffers sg = p ? *gp : wgt_hit_buffers{};
+  const wgt_motion_buffers sm = m ? *motion : wgt_motion_buffers{};
+  return stage_of("a temporal accumulation",
+                  {{n * 16, in, out.rgba32f}, {n * 4, g.prim, nullptr}, {n * 12, g.pos, nullptr}, {n * 12, g.norm, nullptr},
+                   {n, g.flags, nullptr}, {p * 16, sp.rgba32f, nullptr}, {p * 4, sp.len, nullptr}, {pm * 8, sp.moments, nullptr},
+                   {p * 4, sg.prim, nullptr}, {p * 12, sg.pos, nullptr}, {p * 12, sg.norm, nullptr}, {p, sg.flags, nullptr},
+                   {m * 12, sm.pos_prev, nullptr}, {m * 12, sm.norm_prev, nullptr}, {n * 4, nullptr, out.len},
+                   {out.moments ? n * 8 : 0, nullptr, out.moments}, {out8 ? n * 4 : 0, nullptr, out8}});
+}
+
+StageLayout stage_denoise_variance(uint32_t W, uint32_t H, const wgt_temporal_state& state, const wgt_hit_buffers& g,
+                                   void* out32, void* out8, void* variance_out) {
+  const size_t n = (size_t)W * H;
+  return stage_of("a denoiser", {{n * 16, state.rgba32f, out32}, {n * 4, state.len, nullptr}, {n * 8, state.moments, nullptr},
+                                 {n * 4, g.prim, nullptr}, {n * 12, g.pos, nullptr}, {n * 12, g.norm, nullptr},
+                                 {n * 12, g.col, nullptr}, {n, g.flags, nullptr}, {out8 ? n * 4 : 0, nullptr, out8},
+                                 {variance_out ? n * 4 : 0, nullptr, variance_out},
+                                 {denoise_variance_workspace_bytes(W, H), nullptr, nullptr}});
+}
+
 const char* check_nearest_args(const void* points, const wgt_nearest_buffers* out, uint64_t n) {
   if (!points) return "null points";
   if (!out) return "null output buffers";

@@ -1,7 +1,8 @@
 // launch_plan.h — what the C-ABI (wgt_runtime.cpp) decides before it touches the device, as
 // functions that call no HIP runtime function: the numeric limits of scenes and cameras, the
-// frame constants and their tuning knobs, the k_render_ps form of a tree, and the device layout
-// of a scene.  tests/host_sanitize/host_fuzz.cpp runs them without a GPU.
+// frame constants and their tuning knobs, the k_render_ps form of a tree, the device layout of a
+// scene, the image passes' checks and plans, and the staging layout of their synchronous forms
+// (StageLayout).  The programs of tests/host_sanitize run them without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -242,6 +243,43 @@ SamplePlan plan_sample_plan(const wgt_sample_plan_params& params, uint32_t W, ui
 uint32_t sample_plan_cap(const SamplePlan& plan, const uint32_t* bins, uint64_t& total);
 TemporalPlan plan_temporal(const wgt_temporal_params& params, uint32_t W, uint32_t H, const wgt_camera_param& cam,
                            const wgt_camera_param* cam_prev);
+
+// The synchronous image passes (wgt_sample_plan, wgt_denoise, wgt_temporal_accumulate and its motion
+// form, wgt_denoise_variance) stage their host buffers through one device allocation of the call's own.
+// Its layout: the parts in order, each kDenoiseAlign-aligned, of `bytes` bytes (0: absent), uploaded from
+// `src` before the pass and fetched to `dst` after it (null: not).  `what` words a failed upload's refusal.
+struct StagePart {
+  size_t bytes;
+  const void* src;
+  void* dst;
+};
+struct StageLayout {
+  static constexpr int kMaxParts = 17;  // the temporal accumulation's
+  const char* what = "";
+  int n = 0;
+  StagePart part[kMaxParts] = {};
+  size_t off[kMaxParts + 1] = {};  // off[n]: the allocation's bytes
+  size_t bytes() const { return off[n]; }
+  // part k of the allocation at `base`; null for no bytes, which the asynchronous forms read as absent
+  void* at(void* base, int k) const { return part[k].bytes ? (char*)base + off[k] : nullptr; }
+};
+// The four layouts, of arguments that passed the calls' checks (no pointer is dereferenced but the structs'
+// own); the enums name the parts.  A pass that works in place fetches its rgba32f from the input image's part.
+enum SamplePlanStage { kSpsLen, kSpsMom, kSpsMap, kSpsTotal, kSpsWs, kSpsParts };
+StageLayout stage_sample_plan(uint32_t W, uint32_t H, const wgt_temporal_state& state, void* map_out, void* total_out);
+enum DenoiseStage { kDnsIn, kDnsPrim, kDnsPos, kDnsNorm, kDnsCol, kDnsFlags, kDnsOut8, kDnsWs, kDnsParts };
+StageLayout stage_denoise(uint32_t W, uint32_t H, const void* in, const wgt_hit_buffers& guides, void* out32, void* out8);
+// prev null: the first frame (guides_prev and motion are then not looked at); motion null: the plain form
+enum TemporalStage { kTpsIn, kTpsPrim, kTpsPos, kTpsNorm, kTpsFlags, kTpsPrevRgba, kTpsPrevLen, kTpsPrevMom, kTpsPPrim,
+                     kTpsPPos, kTpsPNorm, kTpsPFlags, kTpsMPos, kTpsMNorm, kTpsLen, kTpsMom, kTpsOut8, kTpsParts };
+static_assert(kTpsParts == StageLayout::kMaxParts, "the longest list");
+StageLayout stage_temporal(uint32_t W, uint32_t H, const void* in, const wgt_hit_buffers& guides,
+                           const wgt_motion_buffers* motion, const wgt_temporal_state* prev,
+                           const wgt_hit_buffers* guides_prev, const wgt_temporal_state& out, void* out8);
+enum DenoiseVarianceStage { kDvsIn, kDvsLen, kDvsMom, kDvsPrim, kDvsPos, kDvsNorm, kDvsCol, kDvsFlags, kDvsOut8, kDvsVar,
+                            kDvsWs, kDvsParts };
+StageLayout stage_denoise_variance(uint32_t W, uint32_t H, const wgt_temporal_state& state, const wgt_hit_buffers& guides,
+                                   void* out32, void* out8, void* variance_out);
 
 // The closest-point queries (wgt_nearest_points and its forms).  Their own checks
 // after the context, the scene and n == 0, in the calls' order: null points; null out or an out without

@@ -183,6 +183,31 @@ int sync_stream(wgt_ctx* ctx) {
 }
 hipStream_t stream_or_own(wgt_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
+// The synchronous image passes: one allocation of the call's own, laid out by `lay` (launch_plan.h
+// StageLayout); its sources uploaded on the context's stream, then `pass(at)` (the asynchronous form on
+// the parts, at(k) the device address of part k or null), then its destinations fetched.  The stream is
+// drained before the allocation is freed, whatever was queued; the first error is the call's.
+template <class Pass>
+int run_staged(wgt_ctx* ctx, const StageLayout& lay, Pass&& pass) {
+  char* base = nullptr;
+  if (hipMalloc((void**)&base, lay.bytes()) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(lay.bytes()) + " bytes failed");
+  }
+  int rc = WGT_OK;
+  for (int k = 0; k < lay.n && rc == WGT_OK; ++k) {
+    const StagePart& p = lay.part[k];
+    if (p.src && hipMemcpyAsync(lay.at(base, k), p.src, p.bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+      rc = fail(ctx, WGT_E_HIP, std::string("hipMemcpyAsync of ") + lay.what + " input failed");
+  }
+  if (rc == WGT_OK) rc = pass([&](int k) { return lay.at(base, k); });
+  for (int k = 0; k < lay.n && rc == WGT_OK; ++k)
+    if (lay.part[k].dst) rc = fetch(ctx, lay.part[k].dst, lay.at(base, k), lay.part[k].bytes);
+  const int rs = sync_stream(ctx);
+  (void)hipFree(base);
+  return rc != WGT_OK ? rc : rs;
+}
+
 int check_render_args(wgt_ctx* ctx, const wgt_camera_param* cam, uint32_t W, uint32_t H, uint32_t tw, uint32_t th) {
   if (!ctx) return fail(nullptr, WGT_E_INVALID, "null context");
   if (!cam) return fail(ctx, WGT_E_INVALID, "null camera");
@@ -447,6 +472,17 @@ int fetch_hits(wgt_ctx* ctx, const wgt_hit_buffers& out, const wgt_hit_buffers& 
   if (out.col && (rc = fetch(ctx, out.col, dev.col, n * 12))) return rc;
   if (out.flags && (rc = fetch(ctx, out.flags, dev.flags, n))) return rc;
   return WGT_OK;
+}
+// wgt_trace_hits, and with two fields wgt_trace_rays, behind their preambles.
+int trace_hits_sync(wgt_ctx* ctx, const float* rays, uint32_t n, const wgt_hit_buffers& out) {
+  wgt_hit_buffers dev;
+  const float* d_rays;
+  int rc;
+  if ((rc = stage_hits(ctx, out, n, dev))) return rc;
+  if ((rc = stage(ctx, wgt_ctx::kRays, rays, (size_t)n * 24, d_rays))) return rc;
+  if ((rc = hits_launch(ctx, d_rays, n, dev, ctx->stream))) return rc;
+  if ((rc = fetch_hits(ctx, out, dev, n))) return rc;
+  return sync_stream(ctx);
 }
 
 // What an upload and a rebuild alike do once the new scene sc (bound to its allocations) is resident
@@ -1146,6 +1182,13 @@ namespace {
 SampleArgs sample_args(const wgt_ctx* ctx, const uint8_t* d_map) {
   return SampleArgs{d_map, (const float4*)ctx->sample_tab.p};
 }
+// ... and their camera: cam's with its spp taken as 1, kept in `store`; a null one stays null for the
+// checks to refuse in their order.
+const wgt_camera_param* sampled_cam(const wgt_camera_param* cam, wgt_camera_param& store) {
+  if (!cam) return nullptr;
+  store = sampled_camera(*cam);
+  return &store;
+}
 
 // wgt_render_tile, and with a host sample map (sampled) wgt_render_tile_sampled: the map is checked
 // last and staged on the context's stream; the camera's spp is then taken as 1.
@@ -1153,11 +1196,7 @@ int render_tile(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uint32
                 uint32_t tw, uint32_t th, bool sampled, const uint8_t* sample_map, uint8_t* rgba8_out,
                 float* rgba32f_out, uint32_t* hit_id_out, wgt_stats* stats) {
   wgt_camera_param c1;
-  const wgt_camera_param* cam = cam_in;
-  if (sampled && ctx && cam_in) {
-    c1 = sampled_camera(*cam_in);
-    cam = &c1;
-  }
+  const wgt_camera_param* cam = sampled ? sampled_cam(cam_in, c1) : cam_in;
   int rc = check_render_args(ctx, cam, W, H, tw, th);
   if (rc) return rc;
   if (x0 >= W || y0 >= H) return fail(ctx, WGT_E_INVALID, "tile origin outside the frame");
@@ -1224,10 +1263,7 @@ int wgt_render_tiles_sampled_async(wgt_ctx* ctx, const wgt_camera_param* cam, ui
                                    uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles, const uint8_t* d_sample_map,
                                    void* d_rgba8, float* d_rgba32f, uint32_t* d_hit_id, void* stream) {
   wgt_camera_param c1;
-  if (cam) {
-    c1 = sampled_camera(*cam);
-    cam = &c1;
-  }
+  cam = sampled_cam(cam, c1);
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, check_sample_map(d_sample_map)));
   const DevFrame fr = tile_frame(*cam, W, H, tw, th, n_tiles);
   return render_frame(ctx, fr, sample_args(ctx, d_sample_map), d_tiles, tiles_at(d_tiles), (uchar4*)d_rgba8, (float4*)d_rgba32f,
@@ -1245,16 +1281,7 @@ int wgt_trace_rays_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, uint32_t
 
 int wgt_trace_rays(wgt_ctx* ctx, const float* rays, uint32_t n, uint32_t* prim_id, float* dist) {
   WGT_BEGIN(query_begin(ctx, n, null_buffer(!rays || !prim_id || !dist)));
-  wgt_hit_buffers out{}, dev;
-  out.prim = prim_id;
-  out.dist = dist;
-  const float* d_rays;
-  int rc;
-  if ((rc = stage_hits(ctx, out, n, dev))) return rc;
-  if ((rc = stage(ctx, wgt_ctx::kRays, rays, (size_t)n * 24, d_rays))) return rc;
-  if ((rc = hits_launch(ctx, d_rays, n, dev, ctx->stream))) return rc;
-  if ((rc = fetch_hits(ctx, out, dev, n))) return rc;
-  return sync_stream(ctx);
+  return trace_hits_sync(ctx, rays, n, wgt_hit_buffers{prim_id, dist, nullptr, nullptr, nullptr, nullptr});
 }
 
 int wgt_occluded_rays_async(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n,
@@ -1283,14 +1310,7 @@ int wgt_trace_hits_async(wgt_ctx* ctx, const float* d_rays, uint32_t n, const wg
 
 int wgt_trace_hits(wgt_ctx* ctx, const float* rays, uint32_t n, const wgt_hit_buffers* out) {
   WGT_BEGIN(query_begin(ctx, n, !rays ? "null buffer" : bad_hits(out)));
-  wgt_hit_buffers dev;
-  const float* d_rays;
-  int rc;
-  if ((rc = stage_hits(ctx, *out, n, dev))) return rc;
-  if ((rc = stage(ctx, wgt_ctx::kRays, rays, (size_t)n * 24, d_rays))) return rc;
-  if ((rc = hits_launch(ctx, d_rays, n, dev, ctx->stream))) return rc;
-  if ((rc = fetch_hits(ctx, *out, dev, n))) return rc;
-  return sync_stream(ctx);
+  return trace_hits_sync(ctx, rays, n, *out);
 }
 
 int wgt_nearest_points_async(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n,
@@ -1359,10 +1379,7 @@ int wgt_render_gbuffer_sampled_async(wgt_ctx* ctx, const wgt_camera_param* cam, 
                                      uint32_t th, const wgt_tile* d_tiles, uint32_t n_tiles, const uint8_t* d_sample_map,
                                      const wgt_hit_buffers* d_out, float* d_rays, void* stream) {
   wgt_camera_param c1;
-  if (cam) {
-    c1 = sampled_camera(*cam);
-    cam = &c1;
-  }
+  cam = sampled_cam(cam, c1);
   const char* bad = bad_hits(d_out);
   if (!bad) bad = check_sample_map(d_sample_map);
   WGT_BEGIN(tiles_begin(ctx, cam, W, H, tw, th, d_tiles, n_tiles, false, nullptr, bad));
@@ -1379,11 +1396,7 @@ int render_gbuffer(wgt_ctx* ctx, const wgt_camera_param* cam_in, uint32_t W, uin
                    uint32_t tw, uint32_t th, bool sampled, const uint8_t* sample_map, const wgt_hit_buffers* out,
                    float* rays_out) {
   wgt_camera_param c1;
-  const wgt_camera_param* cam = cam_in;
-  if (sampled && ctx && cam_in) {
-    c1 = sampled_camera(*cam_in);
-    cam = &c1;
-  }
+  const wgt_camera_param* cam = sampled ? sampled_cam(cam_in, c1) : cam_in;
   int rc = check_render_args(ctx, cam, W, H, tw, th);
   if (rc) return rc;
   if (const char* bad = bad_hits(out)) return fail(ctx, WGT_E_INVALID, bad);
@@ -1461,34 +1474,12 @@ int wgt_sample_plan(wgt_ctx* ctx, const wgt_sample_plan_params* params, uint32_t
   const std::string bad = check_sample_plan_args(params, W, H, state, map_out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  // one allocation of the call's own, freed before it returns: len, the moments, the map, its total, the workspace
-  const size_t n = (size_t)W * H, ws_bytes = sample_plan_workspace_bytes(W, H);
-  enum { kLen, kMom, kMap, kTotal, kWs, kParts };
-  const size_t part[kParts] = {n * 4, n * 8, n, 8, ws_bytes};
-  size_t off[kParts + 1] = {0};
-  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
-  struct Alloc {
-    char* p = nullptr;
-    ~Alloc() {
-      if (p) (void)hipFree(p);
-    }
-  } mem;
-  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
-  }
-  int rc = WGT_OK;
-  if (hipMemcpyAsync(mem.p + off[kLen], state->len, part[kLen], hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(mem.p + off[kMom], state->moments, part[kMom], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a sample plan input failed");
-  const wgt_temporal_state dst{nullptr, (float*)(mem.p + off[kLen]), (float*)(mem.p + off[kMom])};
-  if (rc == WGT_OK)
-    rc = wgt_sample_plan_async(ctx, params, W, H, &dst, mem.p + off[kWs], ws_bytes, (uint8_t*)(mem.p + off[kMap]),
-                               (uint64_t*)(mem.p + off[kTotal]), ctx->stream);
-  if (rc == WGT_OK) rc = fetch(ctx, map_out, mem.p + off[kMap], n);
-  if (rc == WGT_OK && total_out) rc = fetch(ctx, total_out, mem.p + off[kTotal], 8);
-  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
-  return rc != WGT_OK ? rc : rs;
+  const StageLayout lay = stage_sample_plan(W, H, *state, map_out, total_out);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_temporal_state dst{nullptr, (float*)at(kSpsLen), (float*)at(kSpsMom)};
+    return wgt_sample_plan_async(ctx, params, W, H, &dst, at(kSpsWs), lay.part[kSpsWs].bytes, (uint8_t*)at(kSpsMap),
+                                 (uint64_t*)at(kSpsTotal), ctx->stream);
+  });
 }
 
 int wgt_denoise_defaults(wgt_denoise_params* out) {
@@ -1520,39 +1511,14 @@ int wgt_denoise(wgt_ctx* ctx, const wgt_denoise_params* params, uint32_t W, uint
   const std::string bad = check_denoise_args(params, W, H, rgba32f_in, guides, rgba32f_out, rgba8_out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  // one allocation of the call's own, freed before it returns: the image (filtered in place), the
-  // guides' planes (prim, pos, norm, col, flags), the rgba8 output, the workspace
-  const size_t n = (size_t)W * H, ws_bytes = denoise_workspace_bytes(W, H);
-  const size_t part[] = {n * 16, n * 4, n * 12, n * 12, n * 12, n, n * 4, ws_bytes};
-  const void* src[] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->col, guides->flags};
-  size_t off[9] = {0};
-  for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
-  struct Alloc {
-    char* p = nullptr;
-    ~Alloc() {
-      if (p) (void)hipFree(p);
-    }
-  } mem;
-  if (hipMalloc((void**)&mem.p, off[8]) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[8]) + " bytes failed");
-  }
-  for (int k = 0; k < 6; ++k)
-    WGT_HIP(ctx, hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream));
-  wgt_hit_buffers dev{};
-  dev.prim = (uint32_t*)(mem.p + off[1]);
-  dev.pos = (float*)(mem.p + off[2]);
-  dev.norm = (float*)(mem.p + off[3]);
-  dev.col = (float*)(mem.p + off[4]);
-  dev.flags = (uint8_t*)(mem.p + off[5]);
-  float* const d_img = (float*)mem.p;
-  void* const d_out8 = rgba8_out ? mem.p + off[6] : nullptr;
-  int rc = wgt_denoise_async(ctx, params, W, H, d_img, &dev, mem.p + off[7], ws_bytes, rgba32f_out ? d_img : nullptr,
-                             d_out8, ctx->stream);
-  if (rc == WGT_OK && rgba32f_out) rc = fetch(ctx, rgba32f_out, d_img, n * 16);
-  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, d_out8, n * 4);
-  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
-  return rc != WGT_OK ? rc : rs;
+  const StageLayout lay = stage_denoise(W, H, rgba32f_in, *guides, rgba32f_out, rgba8_out);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_hit_buffers dev{(uint32_t*)at(kDnsPrim), nullptr, (float*)at(kDnsPos), (float*)at(kDnsNorm),
+                              (float*)at(kDnsCol), (uint8_t*)at(kDnsFlags)};
+    float* const d_img = (float*)at(kDnsIn);  // filtered in place
+    return wgt_denoise_async(ctx, params, W, H, d_img, &dev, at(kDnsWs), lay.part[kDnsWs].bytes,
+                             rgba32f_out ? d_img : nullptr, at(kDnsOut8), ctx->stream);
+  });
 }
 
 int wgt_temporal_defaults(wgt_temporal_params* out) {
@@ -1596,55 +1562,19 @@ int temporal_sync(wgt_ctx* ctx, const wgt_temporal_params* params, uint32_t W, u
                   : check_temporal_args(params, W, H, cam, cam_prev, rgba32f_in, guides, prev, guides_prev, out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  // one allocation of the call's own, freed before it returns: the image (accumulated in place), the
-  // guides' planes (prim, pos, norm, flags), the previous state and guides, the motion form's pos_prev
-  // and norm_prev, the new len and moments, the rgba8 output
-  const size_t n = (size_t)W * H;
-  const bool first = !prev, mom = out->moments != nullptr, mot = motion_form && !first;
-  enum { kIn, kPrim, kPos, kNorm, kFlags, kPrevRgba, kPrevLen, kPrevMom, kPPrim, kPPos, kPNorm, kPFlags, kMPos, kMNorm,
-         kLen, kMom, kOut8, kParts };
-  const size_t part[kParts] = {n * 16, n * 4, n * 12, n * 12, n, first ? 0 : n * 16, first ? 0 : n * 4,
-                               first || !mom ? 0 : n * 8, first ? 0 : n * 4, first ? 0 : n * 12, first ? 0 : n * 12,
-                               first ? 0 : n, mot ? n * 12 : 0, mot ? n * 12 : 0, n * 4, mom ? n * 8 : 0,
-                               rgba8_out ? n * 4 : 0};
-  const void* src[kMNorm + 1] = {rgba32f_in, guides->prim, guides->pos, guides->norm, guides->flags,
-                                 first ? nullptr : prev->rgba32f, first ? nullptr : prev->len,
-                                 first ? nullptr : prev->moments, first ? nullptr : guides_prev->prim,
-                                 first ? nullptr : guides_prev->pos, first ? nullptr : guides_prev->norm,
-                                 first ? nullptr : guides_prev->flags, mot ? motion->pos_prev : nullptr,
-                                 mot ? motion->norm_prev : nullptr};
-  size_t off[kParts + 1] = {0};
-  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
-  struct Alloc {
-    char* p = nullptr;
-    ~Alloc() {
-      if (p) (void)hipFree(p);
-    }
-  } mem;
-  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
-  }
-  int rc = WGT_OK;
-  for (int k = 0; k <= kMNorm && rc == WGT_OK; ++k)
-    if (part[k] && hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a temporal accumulation input failed");
-  const auto at = [&](int k) { return part[k] ? mem.p + off[k] : nullptr; };
-  wgt_hit_buffers dg{}, dgp{};
-  dg.prim = (uint32_t*)at(kPrim); dg.pos = (float*)at(kPos); dg.norm = (float*)at(kNorm); dg.flags = (uint8_t*)at(kFlags);
-  dgp.prim = (uint32_t*)at(kPPrim); dgp.pos = (float*)at(kPPos); dgp.norm = (float*)at(kPNorm); dgp.flags = (uint8_t*)at(kPFlags);
-  const wgt_motion_buffers dmot{(float*)at(kMPos), (float*)at(kMNorm)};
-  const wgt_temporal_state dprev{(float*)at(kPrevRgba), (float*)at(kPrevLen), (float*)at(kPrevMom)};
-  const wgt_temporal_state dout{(float*)at(kIn), (float*)at(kLen), (float*)at(kMom)};
-  if (rc == WGT_OK)
-    rc = temporal_async(ctx, params, W, H, cam, cam_prev, (const float*)at(kIn), &dg, motion_form, mot ? &dmot : nullptr,
-                        first ? nullptr : &dprev, first ? nullptr : &dgp, &dout, at(kOut8), ctx->stream);
-  if (rc == WGT_OK) rc = fetch(ctx, out->rgba32f, at(kIn), n * 16);
-  if (rc == WGT_OK) rc = fetch(ctx, out->len, at(kLen), n * 4);
-  if (rc == WGT_OK && mom) rc = fetch(ctx, out->moments, at(kMom), n * 8);
-  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, at(kOut8), n * 4);
-  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
-  return rc != WGT_OK ? rc : rs;
+  const bool first = !prev, mot = motion_form && !first;
+  const StageLayout lay = stage_temporal(W, H, rgba32f_in, *guides, mot ? motion : nullptr, prev, guides_prev, *out, rgba8_out);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_hit_buffers dg{(uint32_t*)at(kTpsPrim), nullptr, (float*)at(kTpsPos), (float*)at(kTpsNorm), nullptr,
+                             (uint8_t*)at(kTpsFlags)};
+    const wgt_hit_buffers dgp{(uint32_t*)at(kTpsPPrim), nullptr, (float*)at(kTpsPPos), (float*)at(kTpsPNorm), nullptr,
+                              (uint8_t*)at(kTpsPFlags)};
+    const wgt_motion_buffers dmot{(float*)at(kTpsMPos), (float*)at(kTpsMNorm)};
+    const wgt_temporal_state dprev{(float*)at(kTpsPrevRgba), (float*)at(kTpsPrevLen), (float*)at(kTpsPrevMom)};
+    const wgt_temporal_state dout{(float*)at(kTpsIn), (float*)at(kTpsLen), (float*)at(kTpsMom)};  // accumulated in place
+    return temporal_async(ctx, params, W, H, cam, cam_prev, dout.rgba32f, &dg, motion_form, mot ? &dmot : nullptr,
+                          first ? nullptr : &dprev, first ? nullptr : &dgp, &dout, at(kTpsOut8), ctx->stream);
+  });
 }
 
 // The reproject's launch on stream s (behind the calls' checks): a reader of the scene and of the snapshot.
@@ -1801,43 +1731,14 @@ int wgt_denoise_variance(wgt_ctx* ctx, const wgt_denoise_variance_params* params
   const std::string bad = check_denoise_variance_args(params, W, H, state, guides, rgba32f_out, rgba8_out);
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   WGT_HIP(ctx, hipSetDevice(ctx->device));
-  // one allocation of the call's own, freed before it returns: the state (its image filtered in
-  // place), the guides' planes, the rgba8 and variance outputs, the workspace
-  const size_t n = (size_t)W * H, ws_bytes = denoise_variance_workspace_bytes(W, H);
-  enum { kIn, kLen, kMom, kPrim, kPos, kNorm, kCol, kFlags, kOut8, kVar, kWs, kParts };
-  const size_t part[kParts] = {n * 16, n * 4, n * 8, n * 4, n * 12, n * 12, n * 12, n, rgba8_out ? n * 4 : 0,
-                               variance_out ? n * 4 : 0, ws_bytes};
-  const void* src[kFlags + 1] = {state->rgba32f, state->len, state->moments, guides->prim,
-                                 guides->pos,    guides->norm, guides->col,  guides->flags};
-  size_t off[kParts + 1] = {0};
-  for (int k = 0; k < kParts; ++k) off[k + 1] = off[k] + (part[k] + kDenoiseAlign - 1) / kDenoiseAlign * kDenoiseAlign;
-  struct Alloc {
-    char* p = nullptr;
-    ~Alloc() {
-      if (p) (void)hipFree(p);
-    }
-  } mem;
-  if (hipMalloc((void**)&mem.p, off[kParts]) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, WGT_E_NOMEM, "device allocation of " + std::to_string(off[kParts]) + " bytes failed");
-  }
-  int rc = WGT_OK;
-  for (int k = 0; k <= kFlags && rc == WGT_OK; ++k)
-    if (hipMemcpyAsync(mem.p + off[k], src[k], part[k], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      rc = fail(ctx, WGT_E_HIP, "hipMemcpyAsync of a denoiser input failed");
-  const auto at = [&](int k) { return part[k] ? mem.p + off[k] : nullptr; };
-  wgt_hit_buffers dg{};
-  dg.prim = (uint32_t*)at(kPrim); dg.pos = (float*)at(kPos); dg.norm = (float*)at(kNorm); dg.col = (float*)at(kCol);
-  dg.flags = (uint8_t*)at(kFlags);
-  const wgt_temporal_state dst{(float*)at(kIn), (float*)at(kLen), (float*)at(kMom)};
-  if (rc == WGT_OK)
-    rc = wgt_denoise_variance_async(ctx, params, W, H, &dst, &dg, at(kWs), ws_bytes, rgba32f_out ? dst.rgba32f : nullptr,
-                                    at(kOut8), (float*)at(kVar), ctx->stream);
-  if (rc == WGT_OK && rgba32f_out) rc = fetch(ctx, rgba32f_out, at(kIn), n * 16);
-  if (rc == WGT_OK && rgba8_out) rc = fetch(ctx, rgba8_out, at(kOut8), n * 4);
-  if (rc == WGT_OK && variance_out) rc = fetch(ctx, variance_out, at(kVar), n * 4);
-  const int rs = sync_stream(ctx);  // before the allocation is freed, whatever was queued
-  return rc != WGT_OK ? rc : rs;
+  const StageLayout lay = stage_denoise_variance(W, H, *state, *guides, rgba32f_out, rgba8_out, variance_out);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_hit_buffers dg{(uint32_t*)at(kDvsPrim), nullptr, (float*)at(kDvsPos), (float*)at(kDvsNorm),
+                             (float*)at(kDvsCol), (uint8_t*)at(kDvsFlags)};
+    const wgt_temporal_state dst{(float*)at(kDvsIn), (float*)at(kDvsLen), (float*)at(kDvsMom)};  // filtered in place
+    return wgt_denoise_variance_async(ctx, params, W, H, &dst, &dg, at(kDvsWs), lay.part[kDvsWs].bytes,
+                                      rgba32f_out ? dst.rgba32f : nullptr, at(kDvsOut8), (float*)at(kDvsVar), ctx->stream);
+  });
 }
 
 int wgt_selftest_math(wgt_ctx* ctx, uint32_t n, uint32_t seed, uint64_t counts[8]) {
