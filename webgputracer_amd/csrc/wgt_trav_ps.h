@@ -82,31 +82,42 @@ __device__ __forceinline__ void park_get(const Park& P, Trav& t) {
   unpark_leaf(P.ld(10), t);
 }
 
-// Place `cand` (a child ref, or kNoRef = take the next stack entry).
+// Place `cand` (a child ref, or kNoRef = take the next stack entry): an internal node becomes
+// t.ref; a leaf becomes the pending leaf when there is none, and the next stack entry is then
+// placed the same way, or it waits on the stack when there is one, and the lane has no node.
+// Nested ifs, the common case (an internal node) falling straight through: as a loop of up to
+// three rounds left by break, continue and return, the same steps compiled to flags and copies
+// of (ref, lf, le, sp) at every exit, and to a third round that no lane ever ran (the first leaf
+// placed leaves a pending leaf, so the second round ends); DESIGN.md §4.2 item 33.
 template <class STK>
 __device__ __forceinline__ void trav_resolve(const DevScene& sc, Trav& t, int cand, const STK& lds) {
-#pragma unroll
-  for (int it = 0; it < 3; ++it) {
-    if (cand == kNoRef) {
-      if (t.sp == 0) break;
-      --t.sp;
-      cand = lds.ld(t.sp);
-    }
-    if (cand >= 0) {
-      t.ref = cand;
+  if (cand == kNoRef) {
+    if (t.sp == 0) {
+      t.ref = kNoRef;
       return;
     }
-    if (t.lf >= t.le) {  // no pending leaf: this one becomes it; keep looking for a node
+    --t.sp;
+    cand = lds.ld(t.sp);
+  }
+  if (cand < 0) {
+    if (t.lf >= t.le) {  // no pending leaf: this one becomes it; look for a node once more
       t.lf = leaf_first(cand) * kTriRecordBytes;
       t.le = t.lf + leaf_count(cand) * kTriRecordBytes;
       cand = kNoRef;
-      continue;
+      if (t.sp != 0) {
+        const int next = lds.ld(t.sp - 1);
+        if (next >= 0) {  // (a second leaf stays where it is)
+          --t.sp;
+          cand = next;
+        }
+      }
+    } else {
+      lds.st(t.sp, cand);  // a second leaf waits on the stack
+      ++t.sp;
+      cand = kNoRef;
     }
-    lds.st(t.sp, cand);  // a second leaf waits on the stack
-    ++t.sp;
-    break;
   }
-  t.ref = kNoRef;
+  t.ref = cand;
 }
 
 __device__ __forceinline__ bool trav_done(const Trav& t) { return t.ref == kNoRef && t.lf >= t.le && t.sp == 0; }
