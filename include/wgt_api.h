@@ -30,6 +30,7 @@
  *   Scene::InitBuffers again, for a changed mesh      wgt_rebuild_triangles, wgt_rebuild_triangles_device
  *                                                     (a new BVH made on the device, any triangle count)
  *   (none: the triangle nearest to a point)           wgt_nearest_points (closest-point query)
+ *   raytrace loop of compute_sample :386-393          wgt_trace_radiance (a path per caller ray and RNG state)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -537,6 +538,56 @@ int wgt_nearest_points_stats(wgt_ctx *ctx, const float *d_points, const float *d
  * points, a NULL or empty out (n == 0 succeeds first). */
 int wgt_nearest_points_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *points,
                             const float *max_dist, uint32_t n, const wgt_nearest_buffers *out);
+
+/* ---- radiance queries (compute_sample's path loop on the caller's rays) ---- */
+/* Planar outputs for n rays; any pointer may be NULL (that field is not written), at least one must
+ * be set. */
+typedef struct {
+  float *rgb;         /* 3 planes of n: r, g, b */
+  uint32_t *prim;     /* n: the primitive the first sample's ray hits (as wgt_trace_rays) */
+  uint32_t *seed_out; /* n: the RNG state after the last sample */
+} wgt_radiance_buffers;  /* 24 bytes */
+
+/* How much light arrives along ray i: `samples` paths traced with the renderer's own raytrace()
+ * (path_tracer.wgsl:264-288), from origin o and direction d (rays as for wgt_trace_rays: six planes of
+ * n floats; d is not normalised and not validated) and RNG state s:
+ *
+ *   seed = s; col = (0,0,0); prim = 0xffffffff
+ *   for j in 0 .. samples-1:
+ *     p = Path{ray = (o, d), col = (1,1,1), end = false}
+ *     for depth in 0 .. 49:
+ *       p = raytrace(p, depth, &seed)
+ *       if j == 0 and depth == 0: prim = that hit's primitive id
+ *       if p.end: break
+ *     col += max(p.col, 0) / f32(samples)            (path_tracer.wgsl:393)
+ *
+ * which is compute_sample with the camera ray replaced by the caller's and without the two jitter
+ * draws: a frame rendered at spp = 1 is, per pixel, this query on the ray wgt_render_gbuffer exports,
+ * from the state two rand() past the pixel's seed, bit for bit.  samples == 0 gives zero colour,
+ * prim = 0xffffffff and the seed unchanged.  A ray with a NaN component behaves as in the renderer: it
+ * hits the last sphere, and unless that sphere is emissive the state advances by 3 draws per remaining
+ * bounce and the sample adds 0.  The arithmetic is the renderer's (its short divisions), exact against
+ * the reference for origins within 2^40 and directions within 2^32 per component.
+ * seeds == NULL: ray i starts from seed0 + i (32-bit wrap-around); else from seeds[i], and seed0 is
+ * ignored.  seed_out makes calls composable: one call with S samples equals S chained one-sample calls
+ * whose colours the caller sums as col = col + c_j / f32(S) in fp32, in order.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
+ * WGT_E_NOSCENE; n == 0 (success, nothing done); NULL rays; NULL out or an out without a field;
+ * samples above 65536; in the stats form NULL counts last.
+ * The synchronous form takes host pointers and stages through the context's scratch; the async form
+ * takes device pointers and a host struct of device pointers, and follows wgt_trace_rays_async's rules:
+ * ordered on `stream` (NULL = the context's) after every earlier query, update and rebuild of the
+ * context, returns once queued. */
+int wgt_trace_radiance(wgt_ctx *ctx, const float *rays, const uint32_t *seeds, uint32_t seed0, uint32_t samples,
+                       uint32_t n, const wgt_radiance_buffers *out);
+int wgt_trace_radiance_async(wgt_ctx *ctx, const float *d_rays, const uint32_t *d_seeds, uint32_t seed0,
+                             uint32_t samples, uint32_t n, const wgt_radiance_buffers *d_out, void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation (the
+ * timed path carries no atomics); counts = sample_hit calls, those on rays without a NaN component,
+ * paths started, those on NaN rays (the oracle's O_CNT_QUERIES, TRACED, SAMPLES, NAN_RAYS), summed
+ * over the n rays. */
+int wgt_trace_radiance_stats(wgt_ctx *ctx, const float *d_rays, const uint32_t *d_seeds, uint32_t seed0,
+                             uint32_t samples, uint32_t n, const wgt_radiance_buffers *d_out, uint64_t counts[4]);
 
 /* ---- denoising (no reference counterpart) --------------------------------- */
 /* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered W x H image, guided

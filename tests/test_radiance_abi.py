@@ -1,0 +1,117 @@
+"""The radiance query's C-ABI surface (include/wgt_api.h: wgt_trace_radiance and its forms): declared,
+exported, bound, the struct's layout against the header, the order of the argument checks as the planning
+function (host/launch_plan.h check_radiance_args) applies it, and the refusal that needs no scene.  No
+compute on a device (no GPU needed)."""
+import ctypes
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "wgt_api.h")
+FUNCTIONS = ("wgt_trace_radiance", "wgt_trace_radiance_async", "wgt_trace_radiance_stats")
+FIELDS = ["rgb", "prim", "seed_out"]
+
+
+def test_header_declares_the_entry_points():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    flat = " ".join(text.split())
+    assert ("int wgt_trace_radiance(wgt_ctx *ctx, const float *rays, const uint32_t *seeds, uint32_t seed0, "
+            "uint32_t samples, uint32_t n, const wgt_radiance_buffers *out);") in flat
+    assert ("int wgt_trace_radiance_async(wgt_ctx *ctx, const float *d_rays, const uint32_t *d_seeds, uint32_t seed0, "
+            "uint32_t samples, uint32_t n, const wgt_radiance_buffers *d_out, void *stream);") in flat
+    assert ("int wgt_trace_radiance_stats(wgt_ctx *ctx, const float *d_rays, const uint32_t *d_seeds, uint32_t seed0, "
+            "uint32_t samples, uint32_t n, const wgt_radiance_buffers *d_out, uint64_t counts[4]);") in flat
+    assert "#define WGT_API_VERSION 2" in text  # adding functions keeps the version
+
+
+def test_library_exports_and_binding_names_them(wgt):
+    from webgputracer_amd import _lib
+
+    L = _lib.lib()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True)
+    exported = set(re.findall(r"\bT (wgt_\w+)", out.stdout))
+    for name in FUNCTIONS:
+        assert name in exported and name in _lib.EXPORTS, name
+        assert getattr(L, name).argtypes is not None, name  # a prototype, not ctypes' default
+    assert [len(getattr(L, n).argtypes) for n in FUNCTIONS] == [7, 8, 8]
+    assert L.wgt_version() == 2
+
+
+def test_struct_layout_matches_the_header(tmp_path):
+    from webgputracer_amd import _lib
+
+    lines = ['printf("size %zu\\n", sizeof(wgt_radiance_buffers));', 'printf("hits %zu\\n", sizeof(wgt_hit_buffers));',
+             'printf("nearest %zu\\n", sizeof(wgt_nearest_buffers));']
+    lines += [f'printf("{f} %zu\\n", offsetof(wgt_radiance_buffers, {f}));' for f in FIELDS]
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wgt_api.h"\nint main(void) {\n' +
+                   "\n".join(lines) + "\nreturn 0;\n}\n")
+    exe = tmp_path / "sizes"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = dict(ln.split() for ln in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    assert [f for f, _ in _lib.WgtRadianceBuffers._fields_] == FIELDS
+    assert int(got["size"]) == 24 == ctypes.sizeof(_lib.WgtRadianceBuffers)
+    assert [int(got[f]) for f in FIELDS] == [0, 8, 16] == [getattr(_lib.WgtRadianceBuffers, f).offset for f in FIELDS]
+    assert int(got["hits"]) == 48 and int(got["nearest"]) == 32  # unchanged
+
+
+def test_null_context_is_refused_first(wgt):
+    from webgputracer_amd import _lib
+
+    L = _lib.lib()
+    for f, args in ((L.wgt_trace_radiance, (None, None, None, 0, 1 << 20, 1, None)),
+                    (L.wgt_trace_radiance_async, (None, None, None, 0, 1 << 20, 1, None, None)),
+                    (L.wgt_trace_radiance_stats, (None, None, None, 0, 1 << 20, 1, None, None))):
+        assert f(*args) == _lib.WGT_E_INVALID
+        assert b"null context" in L.wgt_last_error(None)
+
+
+PLAN_PROBE = r"""
+#include <cstdint>
+#include <cstdio>
+#include "wgt_api.h"
+namespace wgt { const char* check_radiance_args(const void* rays, const wgt_radiance_buffers* out, uint64_t samples); }
+int main() {
+  float ray = 0.0f; uint32_t word = 0;
+  const wgt_radiance_buffers none{}, some{nullptr, nullptr, &word};
+  const struct { const void* rays; const wgt_radiance_buffers* out; uint64_t samples; } c[] = {
+      {nullptr, nullptr, 1u << 20}, {&ray, nullptr, 1u << 20}, {&ray, &none, 1u << 20}, {&ray, &some, 65537},
+      {&ray, &some, 65536}, {&ray, &some, 0}};
+  for (const auto& k : c) {
+    const char* r = wgt::check_radiance_args(k.rays, k.out, k.samples);
+    std::printf("%s\n", r ? r : "fine");
+  }
+  return 0;
+}
+"""
+
+
+def test_the_order_of_the_argument_checks(wgt, tmp_path):
+    """After the context, the scene and n == 0, which the entry points check themselves: null rays, a null
+    struct, a struct without a field, then the sample count; each refusal names its argument.  The planning
+    function is the library's own (the entry points pass its text to the caller), called from a small program."""
+    from webgputracer_amd import _lib
+
+    src = tmp_path / "probe.cpp"
+    src.write_text(PLAN_PROBE)
+    exe = tmp_path / "probe"
+    libdir = os.path.dirname(os.path.abspath(_lib.LIB_PATH))
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe), "-L", libdir,
+                    "-l:" + os.path.basename(_lib.LIB_PATH), "-Wl,-rpath," + libdir], check=True)
+    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+    want = ["null rays", "null output buffers", "no radiance field", "too many samples", "fine", "fine"]
+    assert len(got) == len(want) and all(w in g for w, g in zip(want, got)), got
+
+
+def test_python_face(wgt):
+    import pytest
+
+    for name in ("trace_radiance", "trace_radiance_async", "trace_radiance_stats"):
+        assert callable(getattr(wgt.Context, name)), name
+    from webgputracer_amd import _lib, frames
+
+    assert _lib.RADIANCE_FIELDS == ("rgb", "prim", "seed")
+    assert callable(frames.panorama_directions) and callable(frames.render_panorama)
+    with pytest.raises(SystemExit):  # --panorama excludes the other outputs, before any device is touched
+        frames.main(["--panorama", "--gbuffer", "--out", "x"])

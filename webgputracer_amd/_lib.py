@@ -46,6 +46,14 @@ class WgtNearestBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in NEAREST_FIELDS]
 
 
+RADIANCE_FIELDS = ("rgb", "prim", "seed")  # the Python names; the struct's third field is seed_out
+
+
+class WgtRadianceBuffers(ctypes.Structure):
+    """wgt_radiance_buffers (24 bytes): planar outputs of the radiance queries (None / 0 = not written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rgb", "prim", "seed_out")]
+
+
 WGT_DENOISE_DEMODULATE = 1  # wgt_denoise_params.flags
 
 
@@ -155,6 +163,7 @@ EXPORTS = [
     "wgt_sample_plan_defaults", "wgt_sample_plan_workspace_bytes", "wgt_sample_plan", "wgt_sample_plan_async",
     "wgt_order_info", "wgt_order_read", "wgt_order_reset",
     "wgt_nearest_points", "wgt_nearest_points_async", "wgt_nearest_points_stats", "wgt_nearest_points_spec",
+    "wgt_trace_radiance", "wgt_trace_radiance_async", "wgt_trace_radiance_stats",
 ]
 
 _lib = None
@@ -277,6 +286,10 @@ def lib():
         "wgt_nearest_points_stats": (I, [P, P, P, U32, ctypes.POINTER(WgtNearestBuffers),
                                          ctypes.POINTER(ctypes.c_uint64)]),
         "wgt_nearest_points_spec": (I, [P, U32, U32, P, P, U32, ctypes.POINTER(WgtNearestBuffers)]),
+        "wgt_trace_radiance": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtRadianceBuffers)]),
+        "wgt_trace_radiance_async": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtRadianceBuffers), P]),
+        "wgt_trace_radiance_stats": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtRadianceBuffers),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -961,4 +961,44 @@ void nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t fir
   }
 }
 
+const char* check_radiance_args(const void* rays, const wgt_radiance_buffers* out, uint64_t samples) {
+  if (!rays) return "null rays";
+  if (!out) return "null output buffers";
+  if (!out->rgb && !out->prim && !out->seed_out) return "no radiance field asked for";
+  if (samples > kRadianceMaxSamples) return "too many samples (at most 65536)";
+  return nullptr;
+}
+
+RadianceStage plan_radiance_stage(const wgt_radiance_buffers& out, bool has_seeds, uint32_t n) {
+  const size_t N = n;
+  return RadianceStage{N * 24, has_seeds ? N * 4 : 0, out.rgb ? N * 12 : 0, out.prim ? N * 4 : 0,
+                       out.seed_out ? N * 4 : 0};
+}
+
+std::string plan_radiance(const DevScene& sc, uint32_t seed0, uint32_t samples, uint32_t n, uint32_t resident,
+                          RadianceArgs& a) {
+  a = RadianceArgs{};
+  a.n = n; a.samples = samples; a.seed0 = seed0;
+  a.fs = (float)samples;
+  a.inv_fs = pow2_recip(samples);
+  const PsForm form = ps_form(sc);
+  a.persistent = form.tris && env_u32("WGT_KERNEL", 2) == 2 && resident != 0 &&
+                 (uint64_t)n + 64ull * resident <= 0xffffffffull;
+  if (!a.persistent) return "";
+  if (form.cap < sc.stack)
+    return "the scene's launch form keeps " + std::to_string(form.cap) + " of " + std::to_string(sc.stack) +
+           " stack entries in LDS (WGT_PARK): the radiance query has no parked form";
+  // node_form's rule without its camera test: the origins are the caller's rays, tested on the device
+  const uint32_t cnode = env_u32("WGT_CNODE", 1);
+  a.compact = cnode == 1 || (cnode >= 2 && (size_t)sc.n_nodes * kNode4Floats * 4 > kCompactNodeBytes) ? 1u : 0u;
+  const uint32_t to_trav = env_u32("WGT_PS_TO_TRAV", 0), to_service = env_u32("WGT_PS_TO_SERVICE", 0);
+  a.to_trav = to_trav ? to_trav : form.to_trav();
+  a.to_service = to_service ? to_service : form.to_service();
+  a.svc_frac = env_u32("WGT_PS_SVC_FRAC", 16);
+  a.tri_ratio = std::max<uint32_t>(env_u32("WGT_TRI_RATIO", 100), 1u);
+  const uint32_t refill = env_u32("WGT_PQ_REFILL", 0);
+  a.refill = refill ? refill : 2u;
+  return "";
+}
+
 }  // namespace wgt

@@ -15,6 +15,7 @@
 #include "../wgt_internal.h"
 #include "../wgt_motion.h"
 #include "../wgt_nearest.h"
+#include "../wgt_radiance.h"
 #include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
 #include "../wgt_temporal.h"
@@ -298,6 +299,25 @@ NearestStage plan_nearest_stage(const wgt_nearest_buffers& out, bool has_radius,
 // order for the n points, ids first_prim + index; writes the fields `out` asks for.
 void nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
                          const float* max_dist, uint32_t n, const wgt_nearest_buffers& out);
+
+// The radiance queries (wgt_trace_radiance and its forms).  Their own checks after the
+// context, the scene and n == 0, in the calls' order: null rays; null out or an out without a field;
+// samples above kRadianceMaxSamples.  Returns the refusal's text, null when fine.
+const char* check_radiance_args(const void* rays, const wgt_radiance_buffers* out, uint64_t samples);
+// What the synchronous form stages in the context's scratch for the fields `out` asks for, in bytes:
+// the rays, the seeds (0 without), rgb, prim and seed_out (0: not asked for).
+struct RadianceStage {
+  size_t rays, seeds, rgb, prim, seed_out;
+};
+RadianceStage plan_radiance_stage(const wgt_radiance_buffers& out, bool has_seeds, uint32_t n);
+// The launch's uniform arguments and its form, from the decision the render launch takes (WGT_KERNEL,
+// WGT_CNODE, the scene's ps_waves and the phase knobs of make_frame): the persistent phase-split kernel
+// for a scene with triangles unless WGT_KERNEL=1, when the ray queue's 32-bit counter holds n and a
+// refill of each of `resident` waves; the flat kernel otherwise.  Returns a refusal when the scene's
+// launch form keeps fewer LDS stack entries than the tree needs (the parked form, WGT_PARK, which the
+// radiance kernel does not have): such a launch is never queued.  Empty when fine.
+std::string plan_radiance(const DevScene& sc, uint32_t seed0, uint32_t samples, uint32_t n, uint32_t resident,
+                          RadianceArgs& a);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

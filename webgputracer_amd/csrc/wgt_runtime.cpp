@@ -44,6 +44,7 @@ struct wgt_ctx {
   void* scene_mem = nullptr;
   wgt_scene_info info{};
   uint32_t ps_resident = 0;
+  uint32_t rad_resident = 0;  // radiance_resident_waves of the scene, asked at its first radiance query (0: not yet)
   // wgt_update_triangles: the extent of the scene's lights, quads and spheres (they do not move), and
   // what the first refit of a scene prepares (an upload's cost and layout do not change): the level
   // lists of the tree (refit_levels) on the device, then one word for the step exponent
@@ -67,9 +68,12 @@ struct wgt_ctx {
   // queries' rays, prim and dist (closest hits and hit records alike); the occlusion queries'
   // limits and answers; the hit records' pos | norm | col (9 planes) and flags; the G-buffer's rays;
   // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev;
-  // a sampled call's sample map; a rebuild's keys, lists and sort storage (RebuildScratch)
+  // a sampled call's sample map; a rebuild's keys, lists and sort storage (RebuildScratch); a radiance
+  // query's seeds and final seeds (its colours use kHitVec), and the persistent radiance kernel's two
+  // scheduling words (every launch of the context uses them, in launch_on's order)
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
-                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kRebuild, kScratchBufs };
+                 kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kRebuild, kRadSeeds, kRadSeedOut, kRadWs,
+                 kScratchBufs };
   DevBuf buf[kScratchBufs];
   // Scheduling workspaces of the persistent kernel (queues, LPT costs and order),
   // used round-robin by its launches.  A launch waits (on the device) only for the
@@ -427,6 +431,21 @@ int nearest_launch(wgt_ctx* ctx, const float* d_points, const float* d_max_dist,
   return launch_on(ctx, s, "launch_nearest",
                    [&] { return launch_nearest(ctx->sc, d_points, d_max_dist, n, dev, d_counts, s); });
 }
+// The radiance query (behind its checks): the plan (plan_radiance), then one launch of the planned form.
+int radiance_launch(wgt_ctx* ctx, const float* d_rays, const uint32_t* d_seeds, uint32_t seed0, uint32_t samples,
+                    uint32_t n, const wgt_radiance_buffers& dev, unsigned long long* d_counts, hipStream_t s) {
+  if (ctx->sc.n_tris > 0 && ctx->rad_resident == 0)
+    WGT_HIP(ctx, radiance_resident_waves(ctx->sc, ctx->device, ctx->rad_resident));
+  RadianceArgs a;
+  const std::string bad = plan_radiance(ctx->sc, seed0, samples, n, ctx->rad_resident, a);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  uint32_t* d_ws = nullptr;
+  int rc;
+  if (a.persistent && (rc = scratch(ctx, wgt_ctx::kRadWs, 8, d_ws))) return rc;
+  return launch_on(ctx, s, "launch_radiance", [&] {
+    return launch_radiance(ctx->sc, a, d_rays, d_seeds, dev, d_counts, ctx->rad_resident, d_ws, s);
+  });
+}
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                    const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
@@ -499,6 +518,7 @@ void install_scene(wgt_ctx* ctx, const DevScene& sc, const BvhOut& bvh, uint32_t
   ctx->has_snapshot = false;
   ctx->sc = sc;
   ctx->ps_resident = resident;
+  ctx->rad_resident = 0;
   if (env_u32("WGT_DEBUG", 0))
     std::fprintf(stderr, "[wgt] resident: k_render_ps %u waves; LDS stack %u of %u entries, parked %u\n",
                  ctx->ps_resident, sc.ps_cap, sc.stack, sc.ps_park);
@@ -1364,6 +1384,47 @@ int wgt_nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t 
   if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
   if (const char* bad = check_nearest_args(points, out, n)) return fail(nullptr, WGT_E_INVALID, bad);
   nearest_points_spec(tris, n_tris, first_prim, points, max_dist, n, *out);
+  return WGT_OK;
+}
+
+int wgt_trace_radiance_async(wgt_ctx* ctx, const float* d_rays, const uint32_t* d_seeds, uint32_t seed0,
+                             uint32_t samples, uint32_t n, const wgt_radiance_buffers* d_out, void* stream) {
+  WGT_BEGIN(query_begin(ctx, n, check_radiance_args(d_rays, d_out, samples)));
+  return radiance_launch(ctx, d_rays, d_seeds, seed0, samples, n, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_trace_radiance(wgt_ctx* ctx, const float* rays, const uint32_t* seeds, uint32_t seed0, uint32_t samples,
+                       uint32_t n, const wgt_radiance_buffers* out) {
+  WGT_BEGIN(query_begin(ctx, n, check_radiance_args(rays, out, samples)));
+  const RadianceStage st = plan_radiance_stage(*out, seeds != nullptr, n);
+  wgt_radiance_buffers dev{};
+  const float* d_rays;
+  const uint32_t* d_seeds = nullptr;
+  int rc;
+  if (st.rgb && (rc = scratch(ctx, wgt_ctx::kHitVec, st.rgb, dev.rgb))) return rc;
+  if (st.prim && (rc = scratch(ctx, wgt_ctx::kPrim, st.prim, dev.prim))) return rc;
+  if (st.seed_out && (rc = scratch(ctx, wgt_ctx::kRadSeedOut, st.seed_out, dev.seed_out))) return rc;
+  if ((rc = stage(ctx, wgt_ctx::kRays, rays, st.rays, d_rays))) return rc;
+  if (seeds && (rc = stage(ctx, wgt_ctx::kRadSeeds, seeds, st.seeds, d_seeds))) return rc;
+  if ((rc = radiance_launch(ctx, d_rays, d_seeds, seed0, samples, n, dev, nullptr, ctx->stream))) return rc;
+  if (out->rgb && (rc = fetch(ctx, out->rgb, dev.rgb, st.rgb))) return rc;
+  if (out->prim && (rc = fetch(ctx, out->prim, dev.prim, st.prim))) return rc;
+  if (out->seed_out && (rc = fetch(ctx, out->seed_out, dev.seed_out, st.seed_out))) return rc;
+  return sync_stream(ctx);
+}
+
+int wgt_trace_radiance_stats(wgt_ctx* ctx, const float* d_rays, const uint32_t* d_seeds, uint32_t seed0,
+                             uint32_t samples, uint32_t n, const wgt_radiance_buffers* d_out, uint64_t counts[4]) {
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;  // what n == 0 leaves
+  const char* bad = check_radiance_args(d_rays, d_out, samples);
+  WGT_BEGIN(query_begin(ctx, n, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[4], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = radiance_launch(ctx, d_rays, d_seeds, seed0, samples, n, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  for (int k = 0; k < 4; ++k) counts[k] = c[k];
   return WGT_OK;
 }
 

@@ -33,6 +33,11 @@ through wgt_denoise_variance, the filter whose luminance weight follows each pix
 sample map wgt_sample_plan makes of the previous frame's accumulated state, capped at `--budget-spp`
 samples per pixel on average (default: `--spp`); one frame per launch, all on one stream.
 
+`--panorama` writes NNN_pano.png instead: an equirectangular image, width x width/2, seen from the camera's
+origin, a camera the reference's pinhole cannot express.  Pixel (x, y) looks along
+panorama_directions(W, H)[y, x]; its `--spp` paths start from the state x + y*W + frame*W*H and go through
+Context.trace_radiance (wgt_trace_radiance); the colour is stored as the renderer stores it (unorm8).
+
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
       -m webgputracer_amd.frames --frame 1 600 --spp 64 --batch 4 --out out/
@@ -74,6 +79,47 @@ def _cpu_share() -> int:
 
 def batches(frames, batch: int):
     return [frames[i:i + batch] for i in range(0, len(frames), max(batch, 1))]
+
+
+def panorama_directions(W: int, H: int):
+    """(H, W, 3) float32 unit directions of an equirectangular image: pixel (x, y) has longitude
+    (u - 1/2) 2 pi and latitude (1/2 - v) pi at its centre (u, v) = ((x + 1/2) / W, (y + 1/2) / H), and
+    looks along (cos lat sin lon, sin lat, cos lat cos lon): the image's centre looks along +z (the
+    reference camera's view), +x is a quarter to the right, -z the left and right edges, +y the top row."""
+    lon = ((np.arange(W, dtype=np.float64) + 0.5) / W - 0.5) * (2.0 * np.pi)
+    lat = (0.5 - (np.arange(H, dtype=np.float64) + 0.5) / H) * np.pi
+    d = np.empty((H, W, 3), np.float64)
+    d[..., 0] = np.cos(lat)[:, None] * np.sin(lon)[None, :]
+    d[..., 1] = np.sin(lat)[:, None]
+    d[..., 2] = np.cos(lat)[:, None] * np.cos(lon)[None, :]
+    return d.astype(np.float32)
+
+
+def panorama_seeds(W: int, H: int, frame: int):
+    """(H, W) uint32: pixel (x, y) of frame `frame` starts from x + y*W + frame*W*H (32-bit wrap-around),
+    the renderer's per-pixel seed (path_tracer.wgsl:378)."""
+    x, y = np.meshgrid(np.arange(W, dtype=np.uint64), np.arange(H, dtype=np.uint64))
+    return ((x + y * W + np.uint64(frame) * np.uint64(W * H)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def unorm8(x):
+    """The renderer's rgba8unorm store of an fp32 value: floor(min(max(x, 0), 1) * 255 + 0.5) in fp32,
+    a NaN as 0."""
+    x = np.asarray(x, np.float32)
+    c = np.where(x > 0, x, np.float32(0))
+    c = np.where(c < 1, c, np.float32(1))
+    return np.floor(c * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+
+
+def render_panorama(ctx: Context, W: int, spp: int, frame: int, origin=(278.0, 278.0, -800.0)):
+    """(W/2, W, 4) uint8: frame `frame` of the equirectangular camera at `origin` (see --panorama)."""
+    H = W // 2
+    d = panorama_directions(W, H).reshape(-1, 3)
+    o = np.broadcast_to(np.asarray(origin, np.float32), d.shape)
+    rgb = ctx.trace_radiance(o, d, seeds=panorama_seeds(W, H, frame).reshape(-1), samples=spp, want=("rgb",))["rgb"]
+    img = np.full((H, W, 4), 255, np.uint8)
+    img[..., :3] = unorm8(rgb).reshape(H, W, 3)
+    return img
 
 
 class FrameRenderer:
@@ -338,6 +384,10 @@ def main(argv=None):
     ap.add_argument("--budget-spp", type=float, default=None,
                     help="--adaptive: the map's mean samples per pixel may not exceed this (default: --spp, so the "
                          "option never spends more than the plain run)")
+    ap.add_argument("--panorama", action="store_true",
+                    help="write NNN_pano.png instead of NNN.png: an equirectangular image, --width x --width/2, from "
+                         "the camera's origin, --spp paths per pixel through wgt_trace_radiance; without the other "
+                         "outputs")
     ap.add_argument("--max-history", type=int, default=32, help="--accumulate: the history length's cap (1..65536)")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
@@ -359,6 +409,10 @@ def main(argv=None):
     if a.accumulate and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--accumulate needs consecutive frames: frames are dealt round-robin to the ranks, so run it "
                  "in one process (WORLD_SIZE = 1)")
+    if a.panorama and (a.gbuffer or a.denoise or a.accumulate or a.denoise_variance or a.adaptive):
+        ap.error("--panorama runs without --gbuffer, --denoise, --accumulate, --denoise-variance and --adaptive")
+    if a.panorama and not (a.out and a.width >= 2 and 0 <= a.spp <= 65536):
+        ap.error("--panorama needs --out, --width >= 2 and --spp within 0..65536")
     if a.frame[0] < 1 or a.frame[1] < a.frame[0]:
         ap.error("bad frame range")  # the C++ CLI's check (csrc/main.cpp)
     if not 1 <= a.pipeline <= 4:
@@ -396,7 +450,11 @@ def main(argv=None):
     accumulated_denoised = {} if a.accumulate and a.denoise else None
     accumulated_vdenoised = {} if a.accumulate and a.denoise_variance else None
     totals = {}
-    if a.adaptive:
+    if a.panorama:
+        for f in mine:
+            pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_pano.png"),
+                                       render_panorama(ctx, a.width, a.spp, f)))
+    elif a.adaptive:
         for f, img, accum in fr.stream_adaptive(mine, max_history=a.max_history, budget_spp=a.budget_spp, totals=totals):
             pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), img))
             pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_accum.png"), accum))

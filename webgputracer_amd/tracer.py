@@ -8,6 +8,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   sample_hit (path_tracer.wgsl:290-310)     -> Context.trace_rays, Context.occluded (dist < a limit)
   HitInfo (path_tracer.wgsl:27-36)          -> Context.trace_hits, Context.render_gbuffer (whole records)
   (none: the triangle nearest to a point)   -> Context.nearest_points, nearest_points_spec (host brute force)
+  compute_sample's path loop (:386-393)     -> Context.trace_radiance (a path per caller ray and RNG state)
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -17,7 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, NEAREST_FIELDS, WgtNearestBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, NEAREST_FIELDS, RADIANCE_FIELDS, WgtNearestBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
@@ -547,6 +548,47 @@ class Context:
         self._check(self._L.wgt_nearest_points_stats(self.h, ctypes.c_void_p(d_points or None),
                                                      ctypes.c_void_p(d_max_dist or None), n, ctypes.byref(bufs), counts))
         return int(counts[0]), int(counts[1])
+
+    def trace_radiance(self, start, direction, seeds=None, seed0=0, samples=1, want=RADIANCE_FIELDS):
+        """Radiance query (wgt_trace_radiance): `samples` paths of the renderer's raytrace() along each
+        caller ray, a dict of the fields in `want`: rgb (n, 3) the mean of max(path colour, 0), prim (n,)
+        uint32 the primitive the first path's ray hits, seed (n,) uint32 the RNG state after the last
+        path.  Ray i starts from seeds[i], or from seed0 + i (32-bit wrap-around) when seeds is None.
+        Feeding `seed` back as `seeds` chains calls: S one-sample calls summed as col + c / f32(S) in
+        fp32 equal one call with S samples.  A frame at spp = 1 is this query on render_gbuffer's rays
+        from the state two rand() past each pixel's seed."""
+        bad = set(want) - set(RADIANCE_FIELDS)
+        if bad:
+            raise ValueError(f"unknown radiance field(s) {sorted(bad)}; choose from {RADIANCE_FIELDS}")
+        soa, n = _ray_soa(start, direction)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+            if len(seeds) != n:
+                raise ValueError(f"{len(seeds)} seeds for {n} rays")
+        arr = {"rgb": np.zeros((3, n), np.float32), "prim": np.zeros(n, np.uint32), "seed": np.zeros(n, np.uint32)}
+        arr = {k: a for k, a in arr.items() if k in want}
+        bufs = WgtRadianceBuffers(ptr(arr.get("rgb")), ptr(arr.get("prim")), ptr(arr.get("seed")))
+        self._check(self._L.wgt_trace_radiance(self.h, ptr(soa), ptr(seeds), seed0 & 0xFFFFFFFF, samples, n,
+                                               ctypes.byref(bufs)))
+        return {k: np.ascontiguousarray(a.T) if k == "rgb" else a for k, a in arr.items()}
+
+    def trace_radiance_async(self, d_rays, n, d_seeds=0, seed0=0, samples=1, rgb=0, prim=0, seed=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_rays 6 planes of n floats, d_seeds n
+        uint32 or 0 (then seed0 + i); rgb receives 3 planes of n floats, prim and seed n uint32."""
+        bufs = WgtRadianceBuffers(rgb or None, prim or None, seed or None)
+        self._check(self._L.wgt_trace_radiance_async(self.h, ctypes.c_void_p(d_rays or None),
+                                                     ctypes.c_void_p(d_seeds or None), seed0 & 0xFFFFFFFF, samples, n,
+                                                     ctypes.byref(bufs), ctypes.c_void_p(stream or None)))
+
+    def trace_radiance_stats(self, d_rays, n, d_seeds=0, seed0=0, samples=1, rgb=0, prim=0, seed=0):
+        """The same answers from the counting kernel (wgt_trace_radiance_stats; synchronous, device
+        pointers): -> (queries, traced, samples, nan_rays) summed over the n rays, the oracle's counters."""
+        bufs = WgtRadianceBuffers(rgb or None, prim or None, seed or None)
+        counts = (ctypes.c_uint64 * 4)()
+        self._check(self._L.wgt_trace_radiance_stats(self.h, ctypes.c_void_p(d_rays or None),
+                                                     ctypes.c_void_p(d_seeds or None), seed0 & 0xFFFFFFFF, samples, n,
+                                                     ctypes.byref(bufs), counts))
+        return tuple(int(c) for c in counts)
 
     def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False, sample_map=None):
         """First-hit G-buffer (wgt_render_gbuffer): the hit record of sample 0's primary ray of each
