@@ -31,6 +31,7 @@
  *                                                     (a new BVH made on the device, any triangle count)
  *   (none: the triangle nearest to a point)           wgt_nearest_points (closest-point query)
  *   raytrace loop of compute_sample :386-393          wgt_trace_radiance (a path per caller ray and RNG state)
+ *   (none: every surface along a ray)                 wgt_trace_multi_hits (the k nearest hits, the hit count)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -588,6 +589,52 @@ int wgt_trace_radiance_async(wgt_ctx *ctx, const float *d_rays, const uint32_t *
  * over the n rays. */
 int wgt_trace_radiance_stats(wgt_ctx *ctx, const float *d_rays, const uint32_t *d_seeds, uint32_t seed0,
                              uint32_t samples, uint32_t n, const wgt_radiance_buffers *d_out, uint64_t counts[4]);
+
+/* ---- multi-hit queries (no reference counterpart; what lies behind the first surface) ---- */
+#define WGT_MULTI_HIT_TRIS_ONLY 1u /* flags: the scene's triangles only; ids unchanged */
+#define WGT_MULTI_HIT_MAX_K 32u
+/* Any pointer may be NULL (that field is not written), at least one must be set. */
+typedef struct {
+  uint32_t *count; /* n, may be NULL */
+  uint32_t *prim;  /* k planes of n, may be NULL */
+  float *dist;     /* k planes of n, may be NULL */
+} wgt_multi_hit_buffers; /* 24 bytes */
+
+/* The k nearest hits of each ray and the number of all its hits (rays as for wgt_trace_rays: six planes
+ * of n floats).  For ray i = (o, d) and m = max_dist[i] (a NULL max_dist: +inf), lim = min(m, 1e20):
+ * a primitive is HIT when the closest-hit code of wgt_trace_rays accepts it tested alone (no other
+ * primitive present) at a distance dist with dist < lim, an IEEE f32 comparison: a NaN distance is
+ * below nothing, a zero, negative or NaN m gives no hits.  A ray with a NaN or infinite component has
+ * no hits, by definition.  A sphere gives at most the one root the reference accepts.  With S the set of
+ * hit primitives: count[i] = |S|, all of it, not capped at k; prim[j*n + i] and dist[j*n + i], j < k, hold
+ * the j-th element of S by (dist, prim) ascending (dist compared as f32, prim as wgt_trace_rays numbers:
+ * lights, quads, triangles, spheres), and 0xffffffff and +inf for j >= min(|S|, k).
+ * WGT_MULTI_HIT_TRIS_ONLY: S holds triangles only; quads, lights and spheres are not tested.  A scene
+ * without triangles then answers with empty records.
+ * Consequences: count > 0 equals wgt_occluded_rays with the same limit for every ray with finite
+ * components for which no quad or sphere yields a NaN distance.  For a ray that wgt_trace_rays answers
+ * with a non-NaN distance, dist[0*n + i] equals that distance bit for bit, and prim[0*n + i] its
+ * primitive except when two triangles have different t but the same rounded dist (the closest-hit order
+ * among triangles is (t, index), this one (dist, prim)).  Crossing parity (count & 1 of a tris-only
+ * query) tells inside from outside of a closed mesh.
+ * With count asked for, every hit below the limit is visited; without it the search stops looking
+ * beyond the k-th distance: the answers are the same.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
+ * WGT_E_NOSCENE; n == 0 (success, nothing done); NULL rays; NULL out or an out without a field; unknown
+ * flag bits; k outside 1..32 when prim or dist is asked for (with only count asked for k is ignored); in
+ * the stats form NULL counts last.
+ * The synchronous form takes host pointers and stages through the context's scratch; the async form
+ * takes device pointers and a host struct of device pointers, and follows wgt_trace_rays_async's rules:
+ * ordered on `stream` (NULL = the context's) after every earlier query, update and rebuild of the
+ * context, returns once queued. */
+int wgt_trace_multi_hits(wgt_ctx *ctx, const float *rays, const float *max_dist, uint32_t n, uint32_t k,
+                         uint32_t flags, const wgt_multi_hit_buffers *out);
+int wgt_trace_multi_hits_async(wgt_ctx *ctx, const float *d_rays, const float *d_max_dist, uint32_t n, uint32_t k,
+                               uint32_t flags, const wgt_multi_hit_buffers *d_out, void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation;
+ * counts[0] = node visits, counts[1] = triangle tests, summed over the n rays. */
+int wgt_trace_multi_hits_stats(wgt_ctx *ctx, const float *d_rays, const float *d_max_dist, uint32_t n, uint32_t k,
+                               uint32_t flags, const wgt_multi_hit_buffers *d_out, uint64_t counts[2]);
 
 /* ---- denoising (no reference counterpart) --------------------------------- */
 /* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered W x H image, guided

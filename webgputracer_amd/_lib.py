@@ -54,6 +54,16 @@ class WgtRadianceBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("rgb", "prim", "seed_out")]
 
 
+MULTI_HIT_FIELDS = ("count", "prim", "dist")
+WGT_MULTI_HIT_TRIS_ONLY = 1  # wgt_trace_multi_hits' flags
+WGT_MULTI_HIT_MAX_K = 32
+
+
+class WgtMultiHitBuffers(ctypes.Structure):
+    """wgt_multi_hit_buffers (24 bytes): outputs of the multi-hit queries (None / 0 = not written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in MULTI_HIT_FIELDS]
+
+
 WGT_DENOISE_DEMODULATE = 1  # wgt_denoise_params.flags
 
 
@@ -164,6 +174,7 @@ EXPORTS = [
     "wgt_order_info", "wgt_order_read", "wgt_order_reset",
     "wgt_nearest_points", "wgt_nearest_points_async", "wgt_nearest_points_stats", "wgt_nearest_points_spec",
     "wgt_trace_radiance", "wgt_trace_radiance_async", "wgt_trace_radiance_stats",
+    "wgt_trace_multi_hits", "wgt_trace_multi_hits_async", "wgt_trace_multi_hits_stats",
 ]
 
 _lib = None
@@ -290,6 +301,10 @@ def lib():
         "wgt_trace_radiance_async": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtRadianceBuffers), P]),
         "wgt_trace_radiance_stats": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtRadianceBuffers),
                                          ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_trace_multi_hits": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtMultiHitBuffers)]),
+        "wgt_trace_multi_hits_async": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtMultiHitBuffers), P]),
+        "wgt_trace_multi_hits_stats": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtMultiHitBuffers),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -1001,4 +1001,37 @@ std::string plan_radiance(const DevScene& sc, uint32_t seed0, uint32_t samples, 
   return "";
 }
 
+const char* check_multi_hit_args(const void* rays, const wgt_multi_hit_buffers* out, uint64_t k, uint64_t flags) {
+  if (!rays) return "null rays";
+  if (!out) return "null output buffers";
+  if (!out->count && !out->prim && !out->dist) return "no multi-hit field asked for";
+  if (flags & ~(uint64_t)WGT_MULTI_HIT_TRIS_ONLY) return "unknown multi-hit flags";
+  if ((out->prim || out->dist) && (k < 1 || k > WGT_MULTI_HIT_MAX_K)) return "k out of range (1..32)";
+  return nullptr;
+}
+
+MultiHitStage plan_multi_hit_stage(const wgt_multi_hit_buffers& out, bool has_limit, uint32_t n, uint32_t k) {
+  const size_t N = n, planes = (size_t)k * N * 4;
+  return MultiHitStage{N * 24, has_limit ? N * 4 : 0, out.count ? N * 4 : 0, out.prim ? planes : 0,
+                       out.dist ? planes : 0};
+}
+
+std::string plan_multi_hit(const DevScene& sc, const wgt_multi_hit_buffers& out, uint32_t n, uint32_t k,
+                           uint32_t flags, MultiHitPlan& p) {
+  p = MultiHitPlan{};
+  p.n = n;
+  p.k = (out.prim || out.dist) ? k : 0u;
+  p.tris_only = (flags & WGT_MULTI_HIT_TRIS_ONLY) ? 1u : 0u;
+  p.mode = out.count ? kMultiHitCount : kMultiHitCull;
+  // the kernel's list indices rely on it, whoever calls
+  if ((out.prim || out.dist) && (k < 1 || k > WGT_MULTI_HIT_MAX_K)) return "k out of range (1..32)";
+  const size_t lds = multi_hit_lds_bytes(sc.stack, p.k);
+  if (lds > kLdsPerWorkgroup)
+    return "a stack of " + std::to_string(sc.stack) + " entries and a list of " + std::to_string(p.k) +
+           " hits per lane need " + std::to_string(lds) + " bytes of LDS, above a workgroup's " +
+           std::to_string(kLdsPerWorkgroup);
+  p.lds = (uint32_t)lds;
+  return "";
+}
+
 }  // namespace wgt

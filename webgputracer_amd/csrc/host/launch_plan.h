@@ -14,6 +14,7 @@
 #include "../wgt_denoise_variance.h"
 #include "../wgt_internal.h"
 #include "../wgt_motion.h"
+#include "../wgt_multihit.h"
 #include "../wgt_nearest.h"
 #include "../wgt_radiance.h"
 #include "../wgt_rebuild.h"
@@ -318,6 +319,23 @@ RadianceStage plan_radiance_stage(const wgt_radiance_buffers& out, bool has_seed
 // radiance kernel does not have): such a launch is never queued.  Empty when fine.
 std::string plan_radiance(const DevScene& sc, uint32_t seed0, uint32_t samples, uint32_t n, uint32_t resident,
                           RadianceArgs& a);
+
+// The multi-hit queries (wgt_trace_multi_hits and its forms).  Their own checks after
+// the context, the scene and n == 0, in the calls' order: null rays; null out or an out without a field;
+// unknown flag bits; k outside 1..WGT_MULTI_HIT_MAX_K when prim or dist is asked for (with count alone k
+// is ignored).  Returns the refusal's text, null when fine.
+const char* check_multi_hit_args(const void* rays, const wgt_multi_hit_buffers* out, uint64_t k, uint64_t flags);
+// What the synchronous form stages in the context's scratch for the fields `out` asks for, in bytes:
+// the rays, the limits (0 without), count, and prim and dist of k planes each (0: not asked for).
+struct MultiHitStage {
+  size_t rays, limits, count, prim, dist;
+};
+MultiHitStage plan_multi_hit_stage(const wgt_multi_hit_buffers& out, bool has_limit, uint32_t n, uint32_t k);
+// The launch: the count form when out.count is asked for, else the cull form; k = 0 when neither prim nor
+// dist is asked for; the dynamic LDS of the scene's stack and the lists.  Returns a refusal, not a launch, when that LDS exceeds one workgroup's (or k is out of
+// range, which check_multi_hit_args refuses first); empty when fine.
+std::string plan_multi_hit(const DevScene& sc, const wgt_multi_hit_buffers& out, uint32_t n, uint32_t k,
+                           uint32_t flags, MultiHitPlan& p);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

@@ -70,7 +70,8 @@ struct wgt_ctx {
   // a refit's moved triangles; the device check's result (RefitCheck); a reproject's pos_prev | norm_prev;
   // a sampled call's sample map; a rebuild's keys, lists and sort storage (RebuildScratch); a radiance
   // query's seeds and final seeds (its colours use kHitVec), and the persistent radiance kernel's two
-  // scheduling words (every launch of the context uses them, in launch_on's order)
+  // scheduling words (every launch of the context uses them, in launch_on's order); a multi-hit query's
+  // counts (kOut32) and its k planes of prim and dist (kPrim, kDist)
   enum Scratch { kTiles, kOut8, kOut32, kHit, kCounters, kRays, kPrim, kDist, kOccLimit, kOccOut, kHitVec,
                  kHitFlags, kGbRays, kMoved, kCheck, kMotionOut, kSampleMap, kRebuild, kRadSeeds, kRadSeedOut, kRadWs,
                  kScratchBufs };
@@ -445,6 +446,15 @@ int radiance_launch(wgt_ctx* ctx, const float* d_rays, const uint32_t* d_seeds, 
   return launch_on(ctx, s, "launch_radiance", [&] {
     return launch_radiance(ctx->sc, a, d_rays, d_seeds, dev, d_counts, ctx->rad_resident, d_ws, s);
   });
+}
+// The multi-hit query (behind its checks): the plan (plan_multi_hit), then one launch of the planned form.
+int multi_hit_launch(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n, uint32_t k,
+                     uint32_t flags, const wgt_multi_hit_buffers& dev, unsigned long long* d_counts, hipStream_t s) {
+  MultiHitPlan p;
+  const std::string bad = plan_multi_hit(ctx->sc, dev, n, k, flags, p);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  return launch_on(ctx, s, "launch_multi_hit",
+                   [&] { return launch_multi_hit(ctx->sc, p, d_rays, d_max_dist, dev, d_counts, s); });
 }
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
@@ -1425,6 +1435,47 @@ int wgt_trace_radiance_stats(wgt_ctx* ctx, const float* d_rays, const uint32_t* 
   if ((rc = radiance_launch(ctx, d_rays, d_seeds, seed0, samples, n, *d_out, d_c, ctx->stream))) return rc;
   if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
   for (int k = 0; k < 4; ++k) counts[k] = c[k];
+  return WGT_OK;
+}
+
+int wgt_trace_multi_hits_async(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n, uint32_t k,
+                               uint32_t flags, const wgt_multi_hit_buffers* d_out, void* stream) {
+  WGT_BEGIN(query_begin(ctx, n, check_multi_hit_args(d_rays, d_out, k, flags)));
+  return multi_hit_launch(ctx, d_rays, d_max_dist, n, k, flags, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_trace_multi_hits(wgt_ctx* ctx, const float* rays, const float* max_dist, uint32_t n, uint32_t k,
+                         uint32_t flags, const wgt_multi_hit_buffers* out) {
+  WGT_BEGIN(query_begin(ctx, n, check_multi_hit_args(rays, out, k, flags)));
+  const MultiHitStage st = plan_multi_hit_stage(*out, max_dist != nullptr, n, k);
+  wgt_multi_hit_buffers dev{};
+  const float *d_rays, *d_limit = nullptr;
+  int rc;
+  if (st.count && (rc = scratch(ctx, wgt_ctx::kOut32, st.count, dev.count))) return rc;
+  if (st.prim && (rc = scratch(ctx, wgt_ctx::kPrim, st.prim, dev.prim))) return rc;
+  if (st.dist && (rc = scratch(ctx, wgt_ctx::kDist, st.dist, dev.dist))) return rc;
+  if ((rc = stage(ctx, wgt_ctx::kRays, rays, st.rays, d_rays))) return rc;
+  if (max_dist && (rc = stage(ctx, wgt_ctx::kOccLimit, max_dist, st.limits, d_limit))) return rc;
+  if ((rc = multi_hit_launch(ctx, d_rays, d_limit, n, k, flags, dev, nullptr, ctx->stream))) return rc;
+  if (out->count && (rc = fetch(ctx, out->count, dev.count, st.count))) return rc;
+  if (out->prim && (rc = fetch(ctx, out->prim, dev.prim, st.prim))) return rc;
+  if (out->dist && (rc = fetch(ctx, out->dist, dev.dist, st.dist))) return rc;
+  return sync_stream(ctx);
+}
+
+int wgt_trace_multi_hits_stats(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist, uint32_t n, uint32_t k,
+                               uint32_t flags, const wgt_multi_hit_buffers* d_out, uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;  // what n == 0 leaves
+  const char* bad = check_multi_hit_args(d_rays, d_out, k, flags);
+  WGT_BEGIN(query_begin(ctx, n, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[2], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = multi_hit_launch(ctx, d_rays, d_max_dist, n, k, flags, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  counts[0] = c[0];
+  counts[1] = c[1];
   return WGT_OK;
 }
 

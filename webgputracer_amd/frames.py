@@ -37,6 +37,8 @@ samples per pixel on average (default: `--spp`); one frame per launch, all on on
 origin, a camera the reference's pinhole cannot express.  Pixel (x, y) looks along
 panorama_directions(W, H)[y, x]; its `--spp` paths start from the state x + y*W + frame*W*H and go through
 Context.trace_radiance (wgt_trace_radiance); the colour is stored as the renderer stores it (unorm8).
+`--hit-count` writes NNN_hits.png instead: grey, the number of surfaces along each pixel's G-buffer ray
+(Context.trace_multi_hits on the rays render_gbuffer exports, every primitive counted), clipped at 255.
 
   python -m webgputracer_amd.frames --frame 1 600 --spp 64 --scene bunny --batch 4 --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -119,6 +121,17 @@ def render_panorama(ctx: Context, W: int, spp: int, frame: int, origin=(278.0, 2
     rgb = ctx.trace_radiance(o, d, seeds=panorama_seeds(W, H, frame).reshape(-1), samples=spp, want=("rgb",))["rgb"]
     img = np.full((H, W, 4), 255, np.uint8)
     img[..., :3] = unorm8(rgb).reshape(H, W, 3)
+    return img
+
+
+def render_hit_count(ctx: Context, W: int, H: int, spp: int, frame: int):
+    """(H, W, 4) uint8 grey image: the number of surfaces along each pixel's G-buffer ray (sample 0's primary
+    ray of frame `frame`, as render_gbuffer exports it), every primitive the ray hits counted
+    (Context.trace_multi_hits, count only), clipped at 255 (see --hit-count)."""
+    g = ctx.render_gbuffer(camera_param(W / H, spp, frame), W, H, want=("prim",), rays=True)
+    count = ctx.trace_multi_hits(g["origin"].reshape(-1, 3), g["direction"].reshape(-1, 3), 0, want=("count",))["count"]
+    img = np.full((H, W, 4), 255, np.uint8)
+    img[..., :3] = np.minimum(count, 255).astype(np.uint8).reshape(H, W, 1)
     return img
 
 
@@ -388,6 +401,9 @@ def main(argv=None):
                     help="write NNN_pano.png instead of NNN.png: an equirectangular image, --width x --width/2, from "
                          "the camera's origin, --spp paths per pixel through wgt_trace_radiance; without the other "
                          "outputs")
+    ap.add_argument("--hit-count", action="store_true",
+                    help="write NNN_hits.png instead of NNN.png: the number of surfaces along each pixel's G-buffer "
+                         "ray through wgt_trace_multi_hits, clipped at 255; without the other outputs")
     ap.add_argument("--max-history", type=int, default=32, help="--accumulate: the history length's cap (1..65536)")
     a = ap.parse_args(argv)
     if a.gbuffer and not a.out:
@@ -413,6 +429,11 @@ def main(argv=None):
         ap.error("--panorama runs without --gbuffer, --denoise, --accumulate, --denoise-variance and --adaptive")
     if a.panorama and not (a.out and a.width >= 2 and 0 <= a.spp <= 65536):
         ap.error("--panorama needs --out, --width >= 2 and --spp within 0..65536")
+    if a.hit_count and (a.panorama or a.gbuffer or a.denoise or a.accumulate or a.denoise_variance or a.adaptive):
+        ap.error("--hit-count runs without --panorama, --gbuffer, --denoise, --accumulate, --denoise-variance and "
+                 "--adaptive")
+    if a.hit_count and not a.out:
+        ap.error("--hit-count needs --out")
     if a.frame[0] < 1 or a.frame[1] < a.frame[0]:
         ap.error("bad frame range")  # the C++ CLI's check (csrc/main.cpp)
     if not 1 <= a.pipeline <= 4:
@@ -454,6 +475,10 @@ def main(argv=None):
         for f in mine:
             pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_pano.png"),
                                        render_panorama(ctx, a.width, a.spp, f)))
+    elif a.hit_count:
+        for f in mine:
+            pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}_hits.png"),
+                                       render_hit_count(ctx, a.width, a.height, a.spp, f)))
     elif a.adaptive:
         for f, img, accum in fr.stream_adaptive(mine, max_history=a.max_history, budget_spp=a.budget_spp, totals=totals):
             pending.append(pool.submit(write_png, os.path.join(a.out, f"{f:03d}.png"), img))

@@ -9,6 +9,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   HitInfo (path_tracer.wgsl:27-36)          -> Context.trace_hits, Context.render_gbuffer (whole records)
   (none: the triangle nearest to a point)   -> Context.nearest_points, nearest_points_spec (host brute force)
   compute_sample's path loop (:386-393)     -> Context.trace_radiance (a path per caller ray and RNG state)
+  (none: every surface along a ray)         -> Context.trace_multi_hits (k nearest hits, hit count), points_inside
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -18,7 +19,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, NEAREST_FIELDS, RADIANCE_FIELDS, WgtNearestBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, MULTI_HIT_FIELDS, NEAREST_FIELDS, RADIANCE_FIELDS, WGT_MULTI_HIT_TRIS_ONLY, WgtMultiHitBuffers, WgtNearestBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
@@ -589,6 +590,53 @@ class Context:
                                                      ctypes.c_void_p(d_seeds or None), seed0 & 0xFFFFFFFF, samples, n,
                                                      ctypes.byref(bufs), counts))
         return tuple(int(c) for c in counts)
+
+    def trace_multi_hits(self, start, direction, k, max_dist=None, tris_only=False, want=MULTI_HIT_FIELDS):
+        """Multi-hit query (wgt_trace_multi_hits): every primitive ray i hits below max_dist (scene units; a
+        scalar broadcasts; None = no limit), a dict of the fields in `want`: count (n,) uint32 the number of
+        all hits, prim (n, k) uint32 and dist (n, k) the k nearest by (dist, prim), 0xffffffff and inf
+        beyond the ray's hits.  tris_only: the scene's triangles only.  With "count" wanted every hit is
+        visited; without it the search stops looking beyond the k-th distance (the same prim and dist)."""
+        bad = set(want) - set(MULTI_HIT_FIELDS)
+        if bad:
+            raise ValueError(f"unknown multi-hit field(s) {sorted(bad)}; choose from {MULTI_HIT_FIELDS}")
+        soa, n = _ray_soa(start, direction)
+        lim = None if max_dist is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float32), (n,)))
+        kk = max(int(k), 0)
+        arr = {"count": np.zeros(n, np.uint32), "prim": np.zeros((kk, n), np.uint32), "dist": np.zeros((kk, n), np.float32)}
+        arr = {f: a for f, a in arr.items() if f in want}
+        bufs = WgtMultiHitBuffers(**{f: a.ctypes.data for f, a in arr.items()})
+        self._check(self._L.wgt_trace_multi_hits(self.h, ptr(soa), ptr(lim), n, kk,
+                                                 WGT_MULTI_HIT_TRIS_ONLY if tris_only else 0, ctypes.byref(bufs)))
+        return {f: a if f == "count" else np.ascontiguousarray(a.T) for f, a in arr.items()}
+
+    def trace_multi_hits_async(self, d_rays, n, k, d_max_dist=0, tris_only=False, count=0, prim=0, dist=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_rays 6 planes of n floats, d_max_dist n
+        floats or 0; count receives n uint32, prim and dist k planes of n."""
+        bufs = WgtMultiHitBuffers(count or None, prim or None, dist or None)
+        self._check(self._L.wgt_trace_multi_hits_async(self.h, ctypes.c_void_p(d_rays or None),
+                                                       ctypes.c_void_p(d_max_dist or None), n, k,
+                                                       WGT_MULTI_HIT_TRIS_ONLY if tris_only else 0, ctypes.byref(bufs),
+                                                       ctypes.c_void_p(stream or None)))
+
+    def trace_multi_hits_stats(self, d_rays, n, k, d_max_dist=0, tris_only=False, count=0, prim=0, dist=0):
+        """The same answers from the counting kernel (wgt_trace_multi_hits_stats; synchronous, device
+        pointers): -> (node visits, triangle tests) summed over the n rays."""
+        bufs = WgtMultiHitBuffers(count or None, prim or None, dist or None)
+        counts = (ctypes.c_uint64 * 2)()
+        self._check(self._L.wgt_trace_multi_hits_stats(self.h, ctypes.c_void_p(d_rays or None),
+                                                       ctypes.c_void_p(d_max_dist or None), n, k,
+                                                       WGT_MULTI_HIT_TRIS_ONLY if tris_only else 0, ctypes.byref(bufs),
+                                                       counts))
+        return int(counts[0]), int(counts[1])
+
+    def points_inside(self, points, direction=(0.5377, 0.3183, 0.7807)):
+        """bool per point: inside the scene's triangle mesh, by crossing parity: one ray per point along
+        `direction` through the triangles only, count & 1.  Valid for closed meshes; undefined for a point
+        whose ray passes within rounding of an edge or a silhouette (a crossing counted twice or not at all)."""
+        points = np.asarray(points, np.float32).reshape(-1, 3)
+        d = np.broadcast_to(np.asarray(direction, np.float32), points.shape)
+        return (self.trace_multi_hits(points, d, 0, tris_only=True, want=("count",))["count"] & 1).astype(bool)
 
     def render_gbuffer(self, cam, W, H, x0=0, y0=0, tw=None, th=None, want=HIT_FIELDS, rays=False, sample_map=None):
         """First-hit G-buffer (wgt_render_gbuffer): the hit record of sample 0's primary ray of each
