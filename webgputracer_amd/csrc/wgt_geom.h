@@ -100,7 +100,10 @@ WGT_HD f3 slab_offset(f3 o, f3 inv) { return f3{-(o.x * inv.x), -(o.y * inv.y), 
 // |e1| |e2| |d| <= 3 sqrt(3) 2^92 < 2^95 (triangle edge components within 2^30, wgt_runtime.cpp
 // check_scene_limits; primary-direction components within 2^32, scattered ones unit), so the
 // result is the IEEE one; caller-supplied rays (the ray queries) use IEEE.
-template <bool SHORT = false>
+// EXITS: 3 = an early-out after each of u, v and t; 2 = one after u, one after v and t (t is then
+// computed for every lane that passes u; the same operations on the same operands, so the same
+// bits for every lane that reaches the end); 1 = one exit after all three.
+template <bool SHORT = false, int EXITS = 3>
 WGT_HD bool mt_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& tout) {
   f3 pvec = cross(d, e2);
   float det = dot(e1, pvec);
@@ -108,12 +111,15 @@ WGT_HD bool mt_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& tout) {
   float inv_det = SHORT ? div_rn(1.0f, det) : 1.0f / det;
   f3 tvec = o - v0;
   float u = dot(tvec, pvec) * inv_det;
-  if (!det_ok || u < 0.0f || u > 1.0f) return false;
+  const bool u_out = !det_ok || u < 0.0f || u > 1.0f;
+  if (EXITS > 1 && u_out) return false;
   f3 qvec = cross(tvec, e1);
   float v = dot(d, qvec) * inv_det;
-  if (v < 0.0f || u + v > 1.0f) return false;
+  const bool v_out = v < 0.0f || u + v > 1.0f;
+  if (EXITS > 2 && v_out) return false;
   float t = dot(e2, qvec) * inv_det;
-  if (t < kRayMin || kRayMax < t) return false;
+  const bool t_out = t < kRayMin || kRayMax < t;
+  if (EXITS > 2 ? t_out : EXITS > 1 ? (v_out || t_out) : (u_out || v_out || t_out)) return false;
   tout = t;
   return true;
 }
@@ -137,7 +143,6 @@ constexpr uint32_t kTriRecordBytes = 64;
 #define WGT_TRI_PER_STEP 2
 #endif
 static_assert(WGT_TRI_PER_STEP >= 1 && WGT_TRI_PER_STEP <= 4, "1 to 4 triangles per step");
-
 // BVH4 node, 128 B (8 x float4, one L2 cache line), children in SoA order:
 //   N[0] = lo.x of children 0..3   N[1] = hi.x   N[2] = lo.y   N[3] = hi.y
 //   N[4] = lo.z                    N[5] = hi.z   N[6] = child refs (int bits)

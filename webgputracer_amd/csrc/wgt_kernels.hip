@@ -359,7 +359,10 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
       cyc_svc += now - t_phase;
       t_phase = now;
     }
-    if (__ballot(have || !exhausted) == 0ull) break;
+    // the lanes a service pass could serve once they stop traversing: neither flag changes
+    // inside a traversal phase
+    const unsigned long long serviceable = __ballot(have || !exhausted);
+    if (serviceable == 0ull) break;
     // --------------------------------------------------------- traversal phase
     uint32_t to_service = fr.ps_to_service;
     if (fr.ps_svc_frac) {
@@ -380,13 +383,16 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
       t.inv = CN ? sc.cstep * inv : inv;
     }
     bool parked = false;  // PK: the lane left on its LDS stack bound, its state parked as it was
+    // the lanes with a node to visit and with a pending leaf: taken once after each step, for
+    // the phase's exit tests and for the next step's mode
+    unsigned long long b_node = __ballot(t.ref != kNoRef), b_tri = __ballot(t.lf < t.le);
     for (; TRIS;) {
       // one uniform mode per step: triangle steps once enough lanes hold a
       // pending leaf (weighted by the two steps' costs), else node steps
       const bool can_node = t.ref != kNoRef;  // implies trav (invariant above)
       const bool can_tri = t.lf < t.le;  // implies trav
-      const uint32_t nn = (uint32_t)__popcll(__ballot(can_node));
-      const uint32_t nl = (uint32_t)__popcll(__ballot(can_tri));
+      const uint32_t nn = (uint32_t)__popcll(b_node);
+      const uint32_t nl = (uint32_t)__popcll(b_tri);
       const bool tri_mode = nn == 0 || nl * 100u >= nn * fr.tri_ratio;
       if (STATS && (tri_mode ? can_tri : can_node)) simt_count(st.wave_steps, st.lane_steps);
       if (COST && (tri_mode ? can_tri : can_node)) ++work;
@@ -421,13 +427,19 @@ k_render_ps(DevScene sc, DevFrame fr, const wgt_tile* __restrict__ tiles, uchar4
           cs_top += all_top ? dt : 0u;
         }
       }
-      if (trav && trav_done(t)) {
-        trav = false;
-        pending = true;
-      }
-      const uint32_t ntrav = (uint32_t)__popcll(__ballot(trav));
-      if (ntrav == 0) break;
-      if (ntrav <= to_service && __any(!trav && (have || !exhausted))) break;
+      // a lane is traversing exactly while it has a node or a pending leaf (the invariant above:
+      // without either its stack is empty), so the two ballots give the traversing lanes, and a
+      // lane's own flags are settled once, after the phase: per step the tail is four compares
+      // and scalar work on three masks, where it kept trav and pending as masks through every step
+      b_node = __ballot(t.ref != kNoRef);
+      b_tri = __ballot(t.lf < t.le);
+      const unsigned long long b_trav = b_node | b_tri;
+      if (b_trav == 0ull) break;
+      if ((uint32_t)__popcll(b_trav) <= to_service && (serviceable & ~b_trav) != 0ull) break;
+    }
+    if (TRIS && trav && trav_done(t)) {
+      trav = false;
+      pending = true;
     }
     if (PK && TRIS && !parked) park_put(P, t);
     if (STATS) cyc_trav += __builtin_amdgcn_s_memtime() - t_phase;

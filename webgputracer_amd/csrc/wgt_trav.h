@@ -29,13 +29,8 @@ __device__ __forceinline__ void simt_count(uint32_t& wave, uint32_t& lane) {
 // v_med3_f32), rejected when the clamp leaves [kRayMin, kRayMax].  Only then the comparison
 // with (bt, bi).  inv: 1/d.  Returns true with (tt, idx) when the triangle becomes the closest hit.
 // SHORT: mt_test's short reciprocal (render rays only, wgt_geom.h).
-template <bool SHORT>
-__device__ __forceinline__ bool tri_test_rec(float4 A, float4 B, float4 C, float4 D, f3 o, f3 d, f3 ot, f3 inv,
-                                             float bt, uint32_t bi, float& tt, uint32_t& idx) {
-  const f3 v0 = xyz(A), e1 = xyz(B), e2 = xyz(C);
-  idx = __float_as_uint(A.w);
-  const f3 blo = f3{B.w, C.w, D.x}, bhi = f3{D.y, D.z, D.w};
-  if (!mt_test<SHORT>(o, d, v0, e1, e2, tt)) return false;
+// tri_tail is the part after Moller-Trumbore: tt comes in as its t and leaves clamped.
+__device__ __forceinline__ bool tri_tail(f3 blo, f3 bhi, f3 ot, f3 inv, float bt, uint32_t bi, float& tt, uint32_t idx) {
   float bn, bf;
   slab(ot, inv, blo, bhi, bn, bf);
   tt = __builtin_amdgcn_fmed3f(tt, bn, bf);
@@ -44,6 +39,15 @@ __device__ __forceinline__ bool tri_test_rec(float4 A, float4 B, float4 C, float
   // unnoticed: an accepted t is <= bt <= kRayMax (bt starts at kRayMax, or is a quad's t, an
   // earlier triangle's or the occlusion bound).  For an empty interval tt is meaningless and unused.
   return (bn <= bf) & (tt >= kRayMin) & ((tt < bt) | ((tt == bt) & (idx < bi)));
+}
+template <bool SHORT>
+__device__ __forceinline__ bool tri_test_rec(float4 A, float4 B, float4 C, float4 D, f3 o, f3 d, f3 ot, f3 inv,
+                                             float bt, uint32_t bi, float& tt, uint32_t& idx) {
+  const f3 v0 = xyz(A), e1 = xyz(B), e2 = xyz(C);
+  idx = __float_as_uint(A.w);
+  const f3 blo = f3{B.w, C.w, D.x}, bhi = f3{D.y, D.z, D.w};
+  if (!mt_test<SHORT>(o, d, v0, e1, e2, tt)) return false;
+  return tri_tail(blo, bhi, ot, inv, bt, bi, tt, idx);
 }
 // The same for the record at byte offset lf: all four float4 loaded at once (the padded box D,
 // for a candidate closest hit, used to be loaded in the branch, a second dependent round trip).

@@ -209,37 +209,65 @@ __device__ __forceinline__ void tri_step(const DevScene& sc, f3 o, f3 d, Trav& t
   // test's early-out branches, two dependent round trips per step (round 6: sponza +1.5 %,
   // bunny +0.9 %)
   constexpr int K = WGT_TRI_PER_STEP;
-  float tt[K];
-  uint32_t idx[K];
-  bool hit[K];
   uint32_t n = 1;
   float4 R[K][4];
+  // every record's address before any load: the empty asm ties the addresses together, so that
+  // no record's loads can issue before the last address is known and the 4 K loads go out back
+  // to back.  Without it the scheduler put the select of the second address behind the first
+  // record's loads and a multiply of the first record, with the wait for its operand, before
+  // the second record's loads: two round trips per step again (sponza -0.5 %)
+  uint32_t ra[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const uint32_t a = t.lf + uint32_t(j) * kTriRecordBytes;
-    const bool live = j == 0 || a < t.le;
-    const float4* __restrict__ q = (const float4*)((const char*)sc.tris + (live ? a : t.lf));
+    ra[j] = (j == 0 || a < t.le) ? a : t.lf;
+  }
+#pragma unroll
+  for (int j = 1; j < K; ++j) asm("" : "+v"(ra[0]), "+v"(ra[j]));
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const float4* __restrict__ q = (const float4*)((const char*)sc.tris + ra[j]);
     R[j][0] = q[0], R[j][1] = q[1], R[j][2] = q[2], R[j][3] = q[3];
   }
+  // Every slot's Moller-Trumbore first, then one tail (tri_tail) for the slots that passed, lowest
+  // slot first: a lane's slots meet the tail in the order, and against the bounds, that K whole
+  // tests followed by a merge gave them.  Slot 0 is accepted against (bt, bi).  A later slot was
+  // accepted against the same (bt, bi) and then merged by strict (t, index) order against the
+  // bound the earlier slots left, which is never above (bt, bi): the two comparisons are the one
+  // against the updated bound, the tail's own.  The tail's code exists once (the inlined whole
+  // tests carried it K times, each behind its test's exits), and a wave runs it a second time
+  // only when one of its lanes has two passing slots (DESIGN.md §4.2 item 34;
+  // tests/tri_tail_restatement.py states both forms in numpy).
+  float tm[K];
+  uint32_t pass = 0u;  // bit j: slot j is live and passed Moller-Trumbore
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const bool live = j == 0 || t.lf + uint32_t(j) * kTriRecordBytes < t.le;
-    hit[j] = tri_test_rec<true>(R[j][0], R[j][1], R[j][2], R[j][3], o, d, t.ot, inv, t.bt, t.bi, tt[j], idx[j]);
-    if (j > 0) {
-      hit[j] = hit[j] && live;
-      n += live ? 1u : 0u;
-    }
+    // two exits (after u; after v and t): the fewest instructions short of the branch-free form
+    const bool p = mt_test<true, 2>(o, d, xyz(R[j][0]), xyz(R[j][1]), xyz(R[j][2]), tm[j]);
+    pass |= (p && live) ? 1u << j : 0u;
+    if (j > 0) n += live ? 1u : 0u;
   }
-  if (hit[0]) {  // passed tri_test's own (t, index) filter against the same bound
-    t.bt = tt[0];
-    t.bi = idx[0];
-  }
+#pragma nounroll
+  while (pass != 0u) {
+    // the record of the lowest slot that passed
+    float iw = R[K - 1][0].w, lx = R[K - 1][1].w, ly = R[K - 1][2].w;
+    float4 D = R[K - 1][3];
+    float tj = tm[K - 1];
 #pragma unroll
-  for (int j = 1; j < K; ++j)
-    if (hit[j] && (tt[j] < t.bt || (tt[j] == t.bt && idx[j] < t.bi))) {
-      t.bt = tt[j];
-      t.bi = idx[j];
+    for (int j = K - 2; j >= 0; --j) {
+      const bool s = (pass & ((2u << j) - 1u)) == (1u << j);  // slot j is the lowest set
+      iw = s ? R[j][0].w : iw, lx = s ? R[j][1].w : lx, ly = s ? R[j][2].w : ly;
+      D.x = s ? R[j][3].x : D.x, D.y = s ? R[j][3].y : D.y, D.z = s ? R[j][3].z : D.z, D.w = s ? R[j][3].w : D.w;
+      tj = s ? tm[j] : tj;
     }
+    pass &= pass - 1u;
+    const uint32_t idx = __float_as_uint(iw);
+    // selects, not a branch around two moves
+    const bool acc = tri_tail(f3{lx, ly, D.x}, f3{D.y, D.z, D.w}, t.ot, inv, t.bt, t.bi, tj, idx);
+    t.bt = acc ? tj : t.bt;
+    t.bi = acc ? idx : t.bi;
+  }
   if (STATS) st.tris += n;
   t.lf += n * kTriRecordBytes;
 #else
