@@ -32,6 +32,7 @@
  *   (none: the triangle nearest to a point)           wgt_nearest_points (closest-point query)
  *   raytrace loop of compute_sample :386-393          wgt_trace_radiance (a path per caller ray and RNG state)
  *   (none: every surface along a ray)                 wgt_trace_multi_hits (the k nearest hits, the hit count)
+ *   (none: the triangles within a radius of a point)  wgt_nearest_k_points (the k nearest, their number)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -515,7 +516,8 @@ typedef struct {
  * comparison: a NaN, zero or negative limit reports nothing, +inf or a NULL max_dist anything);
  * otherwise, and for a point with a NaN or infinite component or a scene without triangles, it is the
  * miss record: prim = 0xffffffff, dist = +inf, pos = 0, uv = 0.  Only triangles are searched: no quads,
- * lights or spheres; no signed distance; one nearest triangle, not k or all within the radius.
+ * lights or spheres; no signed distance; one nearest triangle: the k nearest and the number within the
+ * radius are wgt_nearest_k_points' answers, below.
  * The answers equal wgt_nearest_points_spec on the resident triangles bit for bit; the BVH and the
  * radius only cull (DESIGN.md §4.13 states for which triangle shapes that is proved).
  * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
@@ -539,6 +541,59 @@ int wgt_nearest_points_stats(wgt_ctx *ctx, const float *d_points, const float *d
  * points, a NULL or empty out (n == 0 succeeds first). */
 int wgt_nearest_points_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *points,
                             const float *max_dist, uint32_t n, const wgt_nearest_buffers *out);
+
+/* ---- k-nearest and within-radius closest-point queries ---------------------- */
+#define WGT_NEAREST_MAX_K 32u
+/* Planar outputs for n points; any pointer may be NULL (that field is not written), at least one must be
+ * set.  prim, dist, pos and uv are the list fields: entry j of point i is at plane j (prim, dist), planes
+ * 3 j + axis (pos) and 2 j + {0: v, 1: w} (uv), element i. */
+typedef struct {
+  uint32_t *count; /* n */
+  uint32_t *prim;  /* k planes of n */
+  float *dist;     /* k planes of n */
+  float *pos;      /* 3k planes of n: plane (3*j + axis) */
+  float *uv;       /* 2k planes of n: plane (2*j + {v,w}) */
+} wgt_nearest_k_buffers; /* 40 bytes */
+
+/* The triangles within a radius of each point: how many, and the k nearest (points and max_dist as for
+ * wgt_nearest_points).  For point i = p and m = max_dist[i] (a NULL max_dist: +inf), with d2_t the fp32
+ * squared distance from p to triangle t's resident record exactly as wgt_nearest_points computes it
+ * (DESIGN.md §4.13): S is the set of triangles with d2_t < +inf and sqrt(d2_t) < m, the root correctly
+ * rounded and the comparison IEEE f32: a NaN d2 is in no set, a NaN, zero or negative m gives the empty
+ * set.  count[i] = |S|, all of it, not capped at k.  Entry j < k of the list is the j-th element of S by
+ * (d2, prim) ascending (d2 compared as f32, prim as wgt_trace_rays numbers triangles): prim, dist =
+ * sqrt(d2), the closest point pos and its weights uv, as wgt_nearest_points reports them; entries
+ * j >= min(|S|, k) hold 0xffffffff, +inf, zeros.  A point with a NaN or infinite component, or a scene
+ * without triangles, gives empty entries and count = 0.  Only triangles are searched.
+ * Consequences: S is a prefix of the (d2, prim) order over all triangles with a finite d2 (the root is
+ * monotone); the list for k is a prefix of the list for any larger k; entry 0 equals wgt_nearest_points'
+ * record bit for bit, in all four fields, for the same point and radius; two triangles with different d2
+ * that round to the same dist are ordered by d2, not by prim.
+ * With count asked for, every triangle within the radius is visited; without it the search stops
+ * looking beyond the k-th distance: the answers are the same.  They equal
+ * wgt_nearest_k_points_spec on the resident triangles bit for bit; the BVH, the radius and the k-th
+ * distance only cull (for the triangle shapes DESIGN.md §4.13 names).
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
+ * WGT_E_NOSCENE; n == 0 (success, nothing done); NULL points; NULL out or an out without a field; k
+ * outside 1..32 when a list field is asked for (with only count asked for k is ignored); in the stats
+ * form NULL counts last.  Pointers are not validated.
+ * The synchronous form takes host pointers and stages through the context's scratch; the async form
+ * takes device pointers and a host struct of device pointers, and follows wgt_trace_rays_async's rules:
+ * ordered on `stream` (NULL = the context's) after every earlier query, update and rebuild of the
+ * context, returns once queued. */
+int wgt_nearest_k_points(wgt_ctx *ctx, const float *points, const float *max_dist, uint32_t n, uint32_t k,
+                         const wgt_nearest_k_buffers *out);
+int wgt_nearest_k_points_async(wgt_ctx *ctx, const float *d_points, const float *d_max_dist, uint32_t n, uint32_t k,
+                               const wgt_nearest_k_buffers *d_out, void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation;
+ * counts[0] = node visits, counts[1] = triangle tests, summed over the n points. */
+int wgt_nearest_k_points_stats(wgt_ctx *ctx, const float *d_points, const float *d_max_dist, uint32_t n, uint32_t k,
+                               const wgt_nearest_k_buffers *d_out, uint64_t counts[2]);
+/* Host only, no device: the definition by brute force over tris[0..n_tris) in index order, primitive
+ * ids first_prim + i.  n_tris == 0 gives empty records.  WGT_E_INVALID for NULL tris with n_tris > 0, NULL
+ * points, a NULL or empty out, k out of range with a list field (n == 0 succeeds first). */
+int wgt_nearest_k_points_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *points,
+                              const float *max_dist, uint32_t n, uint32_t k, const wgt_nearest_k_buffers *out);
 
 /* ---- radiance queries (compute_sample's path loop on the caller's rays) ---- */
 /* Planar outputs for n rays; any pointer may be NULL (that field is not written), at least one must

@@ -46,6 +46,16 @@ class WgtNearestBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in NEAREST_FIELDS]
 
 
+NEAREST_K_FIELDS = ("count", "prim", "dist", "pos", "uv")
+WGT_NEAREST_MAX_K = 32
+
+
+class WgtNearestKBuffers(ctypes.Structure):
+    """wgt_nearest_k_buffers (40 bytes): planar outputs of the k-nearest closest-point queries (None / 0 = not
+    written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in NEAREST_K_FIELDS]
+
+
 RADIANCE_FIELDS = ("rgb", "prim", "seed")  # the Python names; the struct's third field is seed_out
 
 
@@ -175,6 +185,7 @@ EXPORTS = [
     "wgt_nearest_points", "wgt_nearest_points_async", "wgt_nearest_points_stats", "wgt_nearest_points_spec",
     "wgt_trace_radiance", "wgt_trace_radiance_async", "wgt_trace_radiance_stats",
     "wgt_trace_multi_hits", "wgt_trace_multi_hits_async", "wgt_trace_multi_hits_stats",
+    "wgt_nearest_k_points", "wgt_nearest_k_points_async", "wgt_nearest_k_points_stats", "wgt_nearest_k_points_spec",
 ]
 
 _lib = None
@@ -305,6 +316,11 @@ def lib():
         "wgt_trace_multi_hits_async": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtMultiHitBuffers), P]),
         "wgt_trace_multi_hits_stats": (I, [P, P, P, U32, U32, U32, ctypes.POINTER(WgtMultiHitBuffers),
                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_nearest_k_points": (I, [P, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers)]),
+        "wgt_nearest_k_points_async": (I, [P, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers), P]),
+        "wgt_nearest_k_points_stats": (I, [P, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_nearest_k_points_spec": (I, [P, U32, U32, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -16,6 +16,7 @@
 #include "../wgt_motion.h"
 #include "../wgt_multihit.h"
 #include "../wgt_nearest.h"
+#include "../wgt_nearest_k.h"
 #include "../wgt_radiance.h"
 #include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
@@ -336,6 +337,32 @@ MultiHitStage plan_multi_hit_stage(const wgt_multi_hit_buffers& out, bool has_li
 // range, which check_multi_hit_args refuses first); empty when fine.
 std::string plan_multi_hit(const DevScene& sc, const wgt_multi_hit_buffers& out, uint32_t n, uint32_t k,
                            uint32_t flags, MultiHitPlan& p);
+
+// The k-nearest and within-radius closest-point queries (wgt_nearest_k_points and its forms; DESIGN.md
+// §4.16).  Their own checks after the context, the scene and n == 0, in the calls' order: null points;
+// null out or an out without a field; n above kNearestMaxPoints; k outside 1..WGT_NEAREST_MAX_K when a
+// list field (prim, dist, pos, uv) is asked for (with count alone k is ignored).  Returns the refusal's
+// text, null when fine.
+const char* check_nearest_k_args(const void* points, const wgt_nearest_k_buffers* out, uint64_t n, uint64_t k);
+// What the synchronous form stages in the context's scratch for the fields `out` asks for, in bytes: the
+// points, the limits (0 without a radius), count, prim and dist of k planes each, and pos | uv as one
+// buffer of 3k and 2k planes with uv at float offset uv_at (0: not asked for).
+struct NearestKStage {
+  size_t points, limits, count, prim, dist, vec, uv_at;
+};
+NearestKStage plan_nearest_k_stage(const wgt_nearest_k_buffers& out, bool has_radius, uint32_t n, uint32_t k);
+// The launch: the count form when out.count is asked for, else the cull form; k = 0 when no list field is
+// asked for; two list words per entry, three when pos or uv is asked for; the count form's node step sorted
+// when it fills a list (WGT_NEAREST_K_SORT = 0 / 1 forces slot order / nearest first); the dynamic LDS of the scene's
+// stack and the lists, sized for the call's k.  Returns a refusal, not a launch, when that LDS exceeds one
+// workgroup's (or k is out of range, which check_nearest_k_args refuses first); empty when fine.
+std::string plan_nearest_k(const DevScene& sc, const wgt_nearest_k_buffers& out, uint32_t n, uint32_t k,
+                           NearestKPlan& p);
+// wgt_nearest_k_points_spec: the definition by brute force (wgt_nearest_k.h) over tris[0..n_tris) in index
+// order for the n points, ids first_prim + index; writes the fields `out` asks for.  k as plan_nearest_k
+// takes it (ignored without a list field).
+void nearest_k_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
+                           const float* max_dist, uint32_t n, uint32_t k, const wgt_nearest_k_buffers& out);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

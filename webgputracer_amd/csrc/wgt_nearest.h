@@ -12,7 +12,8 @@
 //
 // Only triangles are searched (their primitive ids are the scene's: n_lights + n_quads + index);
 // quads, lights and spheres are out of scope.  So is a signed distance (it needs angle-weighted
-// pseudo-normals at edges and vertices) and so are k-nearest and all-within-radius results.
+// pseudo-normals at edges and vertices).  The k nearest triangles and the number within the radius are
+// wgt_nearest_k_points' answers (wgt_nearest_k.h), built on this per-triangle definition.
 #pragma once
 
 #include "wgt_math.h"

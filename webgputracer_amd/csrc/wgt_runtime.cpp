@@ -456,6 +456,15 @@ int multi_hit_launch(wgt_ctx* ctx, const float* d_rays, const float* d_max_dist,
   return launch_on(ctx, s, "launch_multi_hit",
                    [&] { return launch_multi_hit(ctx->sc, p, d_rays, d_max_dist, dev, d_counts, s); });
 }
+// The k-nearest query (behind its checks): the plan (plan_nearest_k), then one launch of the planned form.
+int nearest_k_launch(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n, uint32_t k,
+                     const wgt_nearest_k_buffers& dev, unsigned long long* d_counts, hipStream_t s) {
+  NearestKPlan p;
+  const std::string bad = plan_nearest_k(ctx->sc, dev, n, k, p);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  return launch_on(ctx, s, "launch_nearest_k",
+                   [&] { return launch_nearest_k(ctx->sc, p, d_points, d_max_dist, dev, d_counts, s); });
+}
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                    const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
@@ -1394,6 +1403,62 @@ int wgt_nearest_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t 
   if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
   if (const char* bad = check_nearest_args(points, out, n)) return fail(nullptr, WGT_E_INVALID, bad);
   nearest_points_spec(tris, n_tris, first_prim, points, max_dist, n, *out);
+  return WGT_OK;
+}
+
+int wgt_nearest_k_points_async(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n, uint32_t k,
+                               const wgt_nearest_k_buffers* d_out, void* stream) {
+  WGT_BEGIN(query_begin(ctx, n, check_nearest_k_args(d_points, d_out, n, k)));
+  return nearest_k_launch(ctx, d_points, d_max_dist, n, k, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_nearest_k_points(wgt_ctx* ctx, const float* points, const float* max_dist, uint32_t n, uint32_t k,
+                         const wgt_nearest_k_buffers* out) {
+  WGT_BEGIN(query_begin(ctx, n, check_nearest_k_args(points, out, n, k)));
+  const NearestKStage st = plan_nearest_k_stage(*out, max_dist != nullptr, n, k);
+  wgt_nearest_k_buffers dev{};
+  const float *d_points, *d_limit = nullptr;
+  float* d_vec = nullptr;
+  int rc;
+  if (st.count && (rc = scratch(ctx, wgt_ctx::kOut32, st.count, dev.count))) return rc;
+  if (st.prim && (rc = scratch(ctx, wgt_ctx::kPrim, st.prim, dev.prim))) return rc;
+  if (st.dist && (rc = scratch(ctx, wgt_ctx::kDist, st.dist, dev.dist))) return rc;
+  if (st.vec && (rc = scratch(ctx, wgt_ctx::kHitVec, st.vec, d_vec))) return rc;
+  if (out->pos) dev.pos = d_vec;
+  if (out->uv) dev.uv = d_vec + st.uv_at;
+  if ((rc = stage(ctx, wgt_ctx::kRays, points, st.points, d_points))) return rc;
+  if (max_dist && (rc = stage(ctx, wgt_ctx::kOccLimit, max_dist, st.limits, d_limit))) return rc;
+  if ((rc = nearest_k_launch(ctx, d_points, d_limit, n, k, dev, nullptr, ctx->stream))) return rc;
+  if (out->count && (rc = fetch(ctx, out->count, dev.count, st.count))) return rc;
+  if (out->prim && (rc = fetch(ctx, out->prim, dev.prim, st.prim))) return rc;
+  if (out->dist && (rc = fetch(ctx, out->dist, dev.dist, st.dist))) return rc;
+  if (out->pos && (rc = fetch(ctx, out->pos, dev.pos, (size_t)n * k * 12))) return rc;
+  if (out->uv && (rc = fetch(ctx, out->uv, dev.uv, (size_t)n * k * 8))) return rc;
+  return sync_stream(ctx);
+}
+
+int wgt_nearest_k_points_stats(wgt_ctx* ctx, const float* d_points, const float* d_max_dist, uint32_t n, uint32_t k,
+                               const wgt_nearest_k_buffers* d_out, uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;  // what n == 0 leaves
+  const char* bad = check_nearest_k_args(d_points, d_out, n, k);
+  WGT_BEGIN(query_begin(ctx, n, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[2], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = nearest_k_launch(ctx, d_points, d_max_dist, n, k, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  counts[0] = c[0];
+  counts[1] = c[1];
+  return WGT_OK;
+}
+
+int wgt_nearest_k_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
+                              const float* max_dist, uint32_t n, uint32_t k, const wgt_nearest_k_buffers* out) {
+  if (n == 0) return WGT_OK;
+  if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
+  if (const char* bad = check_nearest_k_args(points, out, n, k)) return fail(nullptr, WGT_E_INVALID, bad);
+  nearest_k_points_spec(tris, n_tris, first_prim, points, max_dist, n, k, *out);
   return WGT_OK;
 }
 

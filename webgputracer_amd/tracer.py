@@ -10,6 +10,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   (none: the triangle nearest to a point)   -> Context.nearest_points, nearest_points_spec (host brute force)
   compute_sample's path loop (:386-393)     -> Context.trace_radiance (a path per caller ray and RNG state)
   (none: every surface along a ray)         -> Context.trace_multi_hits (k nearest hits, hit count), points_inside
+  (none: the triangles around a point)      -> Context.nearest_k_points (k nearest, count within a radius), nearest_k_points_spec
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -19,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, MULTI_HIT_FIELDS, NEAREST_FIELDS, RADIANCE_FIELDS, WGT_MULTI_HIT_TRIS_ONLY, WgtMultiHitBuffers, WgtNearestBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, MULTI_HIT_FIELDS, NEAREST_FIELDS, NEAREST_K_FIELDS, RADIANCE_FIELDS, WGT_MULTI_HIT_TRIS_ONLY, WgtMultiHitBuffers, WgtNearestBuffers, WgtNearestKBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
@@ -213,6 +214,42 @@ def nearest_points_spec(tris, points, max_dist=None, first_prim=0, want=NEAREST_
     check(lib().wgt_nearest_points_spec(ptr(tris) if len(tris) else None, len(tris), first_prim, ptr(soa), ptr(lim), n,
                                         ctypes.byref(bufs)))
     return _nearest_dict(arr)
+
+
+def _nearest_k_arrays(want, n, k):
+    """Host arrays of the k-nearest fields in `want` (planar: prim (k, n), pos (3k, n), uv (2k, n)), their
+    struct, and k as the call takes it."""
+    bad = set(want) - set(NEAREST_K_FIELDS)
+    if bad:
+        raise ValueError(f"unknown nearest field(s) {sorted(bad)}; choose from {NEAREST_K_FIELDS}")
+    kk = max(int(k), 0)
+    shape = {"count": (n,), "prim": (kk, n), "dist": (kk, n), "pos": (3 * kk, n), "uv": (2 * kk, n)}
+    arr = {f: np.zeros(shape[f], np.uint32 if f in ("count", "prim") else np.float32) for f in NEAREST_K_FIELDS if f in want}
+    return arr, WgtNearestKBuffers(**{f: a.ctypes.data for f, a in arr.items()}), kk
+
+
+def _nearest_k_dict(arr, n, k):
+    """Points first, entries next, vectors last: prim and dist (n, k), pos (n, k, 3), uv (n, k, 2)."""
+    out = {}
+    for f, a in arr.items():
+        if f == "count":
+            out[f] = a
+        elif f in ("prim", "dist"):
+            out[f] = np.ascontiguousarray(a.T)
+        else:
+            out[f] = np.ascontiguousarray(a.reshape(k, 3 if f == "pos" else 2, n).transpose(2, 0, 1))
+    return out
+
+
+def nearest_k_points_spec(tris, points, k, max_dist=None, first_prim=0, want=NEAREST_K_FIELDS):
+    """The k-nearest query's definition by brute force on the host (wgt_nearest_k_points_spec, no device):
+    what Context.nearest_k_points returns for a scene that holds `tris` (TRI_DTYPE, ids first_prim + index)."""
+    tris = np.ascontiguousarray(tris, TRI_DTYPE)
+    soa, lim, n = _nearest_inputs(points, max_dist)
+    arr, bufs, kk = _nearest_k_arrays(want, n, k)
+    check(lib().wgt_nearest_k_points_spec(ptr(tris) if len(tris) else None, len(tris), first_prim, ptr(soa), ptr(lim), n,
+                                          kk, ctypes.byref(bufs)))
+    return _nearest_k_dict(arr, n, kk)
 
 
 def build_id() -> str:
@@ -548,6 +585,38 @@ class Context:
         counts = (ctypes.c_uint64 * 2)()
         self._check(self._L.wgt_nearest_points_stats(self.h, ctypes.c_void_p(d_points or None),
                                                      ctypes.c_void_p(d_max_dist or None), n, ctypes.byref(bufs), counts))
+        return int(counts[0]), int(counts[1])
+
+    def nearest_k_points(self, points, k, max_dist=None, want=NEAREST_K_FIELDS):
+        """k-nearest and within-radius closest-point query (wgt_nearest_k_points): the triangles within
+        max_dist of each point (scene units; a scalar broadcasts; None = no radius), a dict of the fields in
+        `want`: count (n,) uint32 the number of all of them, and of the k nearest by (squared distance, prim)
+        prim (n, k) uint32, dist (n, k), pos (n, k, 3) the closest points, uv (n, k, 2) their weights;
+        0xffffffff, inf and zeros beyond the point's triangles.  Entry 0 is nearest_points' record.  With
+        "count" wanted every triangle within the radius is visited; without it the search stops looking
+        beyond the k-th distance (the same lists).  Equals nearest_k_points_spec on the resident triangles
+        bit for bit."""
+        soa, lim, n = _nearest_inputs(points, max_dist)
+        arr, bufs, kk = _nearest_k_arrays(want, n, k)
+        self._check(self._L.wgt_nearest_k_points(self.h, ptr(soa), ptr(lim), n, kk, ctypes.byref(bufs)))
+        return _nearest_k_dict(arr, n, kk)
+
+    def nearest_k_points_async(self, d_points, n, k, d_max_dist=0, count=0, prim=0, dist=0, pos=0, uv=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_points 3 planes of n floats, d_max_dist
+        n floats or 0; count receives n uint32, prim and dist k planes of n, pos 3k planes (3 j + axis), uv 2k."""
+        bufs = WgtNearestKBuffers(count or None, prim or None, dist or None, pos or None, uv or None)
+        self._check(self._L.wgt_nearest_k_points_async(self.h, ctypes.c_void_p(d_points or None),
+                                                       ctypes.c_void_p(d_max_dist or None), n, k, ctypes.byref(bufs),
+                                                       ctypes.c_void_p(stream or None)))
+
+    def nearest_k_points_stats(self, d_points, n, k, d_max_dist=0, count=0, prim=0, dist=0, pos=0, uv=0):
+        """The same answers from the counting kernel (wgt_nearest_k_points_stats; synchronous, device
+        pointers): -> (node visits, triangle tests) summed over the n points."""
+        bufs = WgtNearestKBuffers(count or None, prim or None, dist or None, pos or None, uv or None)
+        counts = (ctypes.c_uint64 * 2)()
+        self._check(self._L.wgt_nearest_k_points_stats(self.h, ctypes.c_void_p(d_points or None),
+                                                       ctypes.c_void_p(d_max_dist or None), n, k, ctypes.byref(bufs),
+                                                       counts))
         return int(counts[0]), int(counts[1])
 
     def trace_radiance(self, start, direction, seeds=None, seed0=0, samples=1, want=RADIANCE_FIELDS):
