@@ -33,6 +33,7 @@
  *   raytrace loop of compute_sample :386-393          wgt_trace_radiance (a path per caller ray and RNG state)
  *   (none: every surface along a ray)                 wgt_trace_multi_hits (the k nearest hits, the hit count)
  *   (none: the triangles within a radius of a point)  wgt_nearest_k_points (the k nearest, their number)
+ *   (none: the triangles a triangle cuts)             wgt_overlap_triangles (whether, how many, which)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -594,6 +595,65 @@ int wgt_nearest_k_points_stats(wgt_ctx *ctx, const float *d_points, const float 
  * points, a NULL or empty out, k out of range with a list field (n == 0 succeeds first). */
 int wgt_nearest_k_points_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *points,
                               const float *max_dist, uint32_t n, uint32_t k, const wgt_nearest_k_buffers *out);
+
+/* ---- triangle overlap queries: which resident triangles a triangle cuts ------ */
+#define WGT_OVERLAP_MAX_K 32
+/* Planar outputs for n query triangles; any pointer may be NULL (that field is not written), at least one
+ * must be set.  Entry j of query i is at plane j of prim, element i. */
+typedef struct {
+  uint8_t *hit;    /* n: 1 when the query cuts a resident triangle, else 0 */
+  uint32_t *count; /* n */
+  uint32_t *prim;  /* k planes of n */
+} wgt_overlap_buffers; /* 24 bytes */
+
+/* The resident triangles each query triangle cuts.  tris: nine planes of n floats, the corners a0.x a0.y
+ * a0.z a1.x a1.y a1.z a2.x a2.y a2.z (the planar convention of the points and rays).  For query i = A =
+ * (a0, a1, a2) and resident triangle B = (v0, e1, e2) with its padded box [lo, hi], in
+ * IEEE f32 with +, -, * only, no division and no fused operation (DESIGN.md §4.17 has every formula):
+ *   segment o + t d, 0 <= t <= 1, crosses triangle (w0, f1, f2): two-sided Moller-Trumbore with the
+ *     quotients cleared; with det, U, V, T its determinant and numerators and a, U', V', T' their values
+ *     negated when det < 0:  a > 0, U' >= 0, V' >= 0, U' + V' <= a, 0 <= T' <= a.  A NaN or a zero
+ *     determinant says no.
+ *   A and B overlap iff min(a0, a1, a2) <= hi and max(a0, a1, a2) >= lo on each axis (exact; the query gets
+ *     no pad) and one of six segments crosses: A's edges (a0, a1 - a0), (a1, a2 - a1), (a2, a0 - a2)
+ *     against B, or B's edges (v0, e1), (v0, e2), (v0 + e1, e2 - e1) against (a0, a1 - a0, a2 - a0).
+ * A query is valid iff its nine coordinates are finite and within 2^40 and every component of a1 - a0,
+ * a2 - a0 and a2 - a1 is within 2^30 (the scene's own triangle limits); an invalid query, or a scene
+ * without triangles, gives the empty answer.  With S the set of resident triangles that overlap A:
+ * count[i] = |S|, all of it, not capped at k; hit[i] = count > 0; entry j < k of prim is the j-th lowest
+ * primitive id of S (as wgt_trace_rays numbers triangles); entries j >= min(|S|, k) hold 0xffffffff.
+ * Only triangles are searched: no quads, lights or spheres.
+ * Consequences: the box clause removes no real intersection (the pad only enlarges B) and makes the BVH's
+ * cull exact, so the answers equal wgt_overlap_triangles_spec on the resident triangles bit for bit with
+ * no condition on the triangles' shapes.  Coplanar pairs are never reported (all six determinants are
+ * zero); nearly coplanar pairs are decided by rounding.  A triangle wholly inside a closed mesh cuts
+ * nothing: combine with an inside test.  Touching counts (the comparisons admit equality), so neighbours in
+ * one mesh that share a vertex or an edge usually report each other: a self-intersection check filters
+ * those by id.  The list for k is a prefix of the list for any larger k.  No intersection segment, no
+ * swept (continuous) test.
+ * With hit alone asked for the search ends at the first overlapping triangle; otherwise every triangle the
+ * boxes allow is visited.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context;
+ * WGT_E_NOSCENE; n == 0 (success, nothing done); NULL tris; NULL out; an out without a field; k > 32;
+ * k == 0 with prim asked for; k > 0 without prim; in the stats form NULL counts last.  Pointers are not
+ * validated.
+ * The synchronous form takes host pointers and stages through a device allocation of the call's own; the
+ * async form takes device pointers and a host struct of device pointers, and follows
+ * wgt_trace_rays_async's rules: ordered on `stream` (NULL = the context's) after every earlier query,
+ * update and rebuild of the context, returns once queued. */
+int wgt_overlap_triangles(wgt_ctx *ctx, const float *tris, uint32_t n, uint32_t k, const wgt_overlap_buffers *out);
+int wgt_overlap_triangles_async(wgt_ctx *ctx, const float *d_tris, uint32_t n, uint32_t k,
+                                const wgt_overlap_buffers *d_out, void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation;
+ * counts[0] = node visits, counts[1] = triangle tests, summed over the n queries. */
+int wgt_overlap_triangles_stats(wgt_ctx *ctx, const float *d_tris, uint32_t n, uint32_t k,
+                                const wgt_overlap_buffers *d_out, uint64_t counts[2]);
+/* Host only, no device: the definition by brute force over tris[0..n_tris) in index order, primitive ids
+ * first_prim + i, each triangle's padded box computed from its record; it culls nothing.  n_tris == 0
+ * gives empty answers.  WGT_E_INVALID for NULL tris with n_tris > 0, then the checks above from NULL query
+ * on (n == 0 succeeds first). */
+int wgt_overlap_triangles_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *query,
+                               uint32_t n, uint32_t k, const wgt_overlap_buffers *out);
 
 /* ---- radiance queries (compute_sample's path loop on the caller's rays) ---- */
 /* Planar outputs for n rays; any pointer may be NULL (that field is not written), at least one must

@@ -56,6 +56,15 @@ class WgtNearestKBuffers(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in NEAREST_K_FIELDS]
 
 
+OVERLAP_FIELDS = ("hit", "count", "prim")
+WGT_OVERLAP_MAX_K = 32
+
+
+class WgtOverlapBuffers(ctypes.Structure):
+    """wgt_overlap_buffers (24 bytes): planar outputs of the triangle overlap queries (None / 0 = not written)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in OVERLAP_FIELDS]
+
+
 RADIANCE_FIELDS = ("rgb", "prim", "seed")  # the Python names; the struct's third field is seed_out
 
 
@@ -186,6 +195,7 @@ EXPORTS = [
     "wgt_trace_radiance", "wgt_trace_radiance_async", "wgt_trace_radiance_stats",
     "wgt_trace_multi_hits", "wgt_trace_multi_hits_async", "wgt_trace_multi_hits_stats",
     "wgt_nearest_k_points", "wgt_nearest_k_points_async", "wgt_nearest_k_points_stats", "wgt_nearest_k_points_spec",
+    "wgt_overlap_triangles", "wgt_overlap_triangles_async", "wgt_overlap_triangles_stats", "wgt_overlap_triangles_spec",
 ]
 
 _lib = None
@@ -321,6 +331,11 @@ def lib():
         "wgt_nearest_k_points_stats": (I, [P, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers),
                                            ctypes.POINTER(ctypes.c_uint64)]),
         "wgt_nearest_k_points_spec": (I, [P, U32, U32, P, P, U32, U32, ctypes.POINTER(WgtNearestKBuffers)]),
+        "wgt_overlap_triangles": (I, [P, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers)]),
+        "wgt_overlap_triangles_async": (I, [P, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers), P]),
+        "wgt_overlap_triangles_stats": (I, [P, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers),
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_overlap_triangles_spec": (I, [P, U32, U32, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

@@ -1144,4 +1144,64 @@ void nearest_k_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t f
   }
 }
 
+const char* check_overlap_args(const void* query, const wgt_overlap_buffers* out, uint64_t k) {
+  if (!query) return "null query triangles";
+  if (!out) return "null output buffers";
+  if (!out->hit && !out->count && !out->prim) return "no overlap field asked for";
+  if (k > WGT_OVERLAP_MAX_K) return "k out of range (0..32)";
+  if (k == 0 && out->prim) return "prim asked for with k == 0";
+  if (k > 0 && !out->prim) return "k > 0 without prim";
+  return nullptr;
+}
+
+std::string plan_overlap(const DevScene& sc, const void* query, const wgt_overlap_buffers* out, uint32_t n, uint64_t k,
+                         OverlapPlan& p) {
+  p = OverlapPlan{};
+  p.n = n;
+  if (const char* bad = check_overlap_args(query, out, k)) return bad;
+  p.k = (uint32_t)k;
+  p.any = (out->hit && !out->count && !out->prim) ? 1u : 0u;
+  const size_t lds = overlap_lds_bytes(sc.stack, p.k);
+  if (lds > kOverlapLdsPerWorkgroup)
+    return "a stack of " + std::to_string(sc.stack) + " entries and a list of " + std::to_string(p.k) +
+           " triangles per lane need " + std::to_string(lds) + " bytes of LDS, above a workgroup's " +
+           std::to_string(kOverlapLdsPerWorkgroup);
+  p.lds = (uint32_t)lds;
+  return "";
+}
+
+StageLayout stage_overlap(const float* query, const wgt_overlap_buffers& out, uint32_t n, uint32_t k) {
+  const size_t N = n;
+  return stage_of("an overlap query", {{N * 36, query, nullptr}, {out.hit ? N : 0, nullptr, out.hit},
+                                       {out.count ? N * 4 : 0, nullptr, out.count},
+                                       {out.prim ? N * k * 4 : 0, nullptr, out.prim}});
+}
+
+void overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* query,
+                            uint32_t n, uint32_t k, const wgt_overlap_buffers& out) {
+  const size_t N = n;
+  if (!out.prim) k = 0;
+  if (k > WGT_OVERLAP_MAX_K) k = WGT_OVERLAP_MAX_K;  // the entry point refused it
+  for (size_t i = 0; i < N; ++i) {
+    const f3 a0{query[i], query[N + i], query[2 * N + i]};
+    const f3 a1{query[3 * N + i], query[4 * N + i], query[5 * N + i]};
+    const f3 a2{query[6 * N + i], query[7 * N + i], query[8 * N + i]};
+    // triangles come in index order, so the first k of S are its k lowest ids
+    uint32_t cnt = 0;
+    const bool ok = overlap_query_ok(a0, a1, a2);
+    for (uint32_t t = 0; ok && t < n_tris; ++t) {
+      const wgt_triangle& tr = tris[t];
+      const f3 v0{tr.v0[0], tr.v0[1], tr.v0[2]}, e1{tr.e1[0], tr.e1[1], tr.e1[2]}, e2{tr.e2[0], tr.e2[1], tr.e2[2]};
+      f3 lo, hi;
+      tri_box(v0, e1, e2, lo, hi);
+      if (!tri_overlap(a0, a1, a2, v0, e1, e2, lo, hi)) continue;
+      if (cnt < k) out.prim[cnt * N + i] = first_prim + t;
+      ++cnt;
+    }
+    if (out.hit) out.hit[i] = cnt > 0 ? 1 : 0;
+    if (out.count) out.count[i] = cnt;
+    for (size_t j = cnt; j < k; ++j) out.prim[j * N + i] = kNoHit;
+  }
+}
+
 }  // namespace wgt

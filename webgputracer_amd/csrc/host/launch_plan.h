@@ -17,6 +17,7 @@
 #include "../wgt_multihit.h"
 #include "../wgt_nearest.h"
 #include "../wgt_nearest_k.h"
+#include "../wgt_overlap.h"
 #include "../wgt_radiance.h"
 #include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
@@ -363,6 +364,27 @@ std::string plan_nearest_k(const DevScene& sc, const wgt_nearest_k_buffers& out,
 // takes it (ignored without a list field).
 void nearest_k_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* points,
                            const float* max_dist, uint32_t n, uint32_t k, const wgt_nearest_k_buffers& out);
+
+// The triangle overlap queries (wgt_overlap_triangles and its forms).  Their own checks
+// after the context, the scene and n == 0, in the calls' order: null query triangles; null out; an out
+// without a field; k above WGT_OVERLAP_MAX_K; k == 0 with prim asked for; k > 0 without prim.  Returns the
+// refusal's text, null when fine.
+const char* check_overlap_args(const void* query, const wgt_overlap_buffers* out, uint64_t k);
+// The launch, of any arguments: those checks first (the kernel's list indices rely on them, whoever
+// calls), then the form (the any form iff hit is the only field asked for), k, and the dynamic LDS of the
+// scene's stack and the lists, sized for the call's k.  Returns a refusal, not a launch, when a check fails
+// or that LDS exceeds one workgroup's; empty when fine.  p.lds is 0 on a refusal.
+std::string plan_overlap(const DevScene& sc, const void* query, const wgt_overlap_buffers* out, uint32_t n, uint64_t k,
+                         OverlapPlan& p);
+// What the synchronous form stages, as the synchronous image passes do (StageLayout): the nine planes of
+// the query up, the fields `out` asks for down.
+enum OverlapStage { kOvsQuery, kOvsHit, kOvsCount, kOvsPrim, kOvsParts };
+StageLayout stage_overlap(const float* query, const wgt_overlap_buffers& out, uint32_t n, uint32_t k);
+// wgt_overlap_triangles_spec: the definition by brute force (wgt_overlap.h) over tris[0..n_tris) in index
+// order for the n query triangles (nine planes of n floats), ids first_prim + index, each triangle's box
+// from tri_box; it culls nothing.  Writes the fields `out` asks for; k as plan_overlap takes it.
+void overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* query,
+                            uint32_t n, uint32_t k, const wgt_overlap_buffers& out);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

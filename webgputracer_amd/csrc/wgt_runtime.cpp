@@ -465,6 +465,14 @@ int nearest_k_launch(wgt_ctx* ctx, const float* d_points, const float* d_max_dis
   return launch_on(ctx, s, "launch_nearest_k",
                    [&] { return launch_nearest_k(ctx->sc, p, d_points, d_max_dist, dev, d_counts, s); });
 }
+// The overlap query (behind its checks): the plan (plan_overlap), then one launch of the planned form.
+int overlap_launch(wgt_ctx* ctx, const float* d_tris, uint32_t n, uint32_t k, const wgt_overlap_buffers& dev,
+                   unsigned long long* d_counts, hipStream_t s) {
+  OverlapPlan p;
+  const std::string bad = plan_overlap(ctx->sc, d_tris, &dev, n, k, p);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  return launch_on(ctx, s, "launch_overlap", [&] { return launch_overlap(ctx->sc, p, d_tris, dev, d_counts, s); });
+}
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                    const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
@@ -1459,6 +1467,46 @@ int wgt_nearest_k_points_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_
   if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
   if (const char* bad = check_nearest_k_args(points, out, n, k)) return fail(nullptr, WGT_E_INVALID, bad);
   nearest_k_points_spec(tris, n_tris, first_prim, points, max_dist, n, k, *out);
+  return WGT_OK;
+}
+
+int wgt_overlap_triangles_async(wgt_ctx* ctx, const float* d_tris, uint32_t n, uint32_t k,
+                                const wgt_overlap_buffers* d_out, void* stream) {
+  WGT_BEGIN(query_begin(ctx, n, check_overlap_args(d_tris, d_out, k)));
+  return overlap_launch(ctx, d_tris, n, k, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_overlap_triangles(wgt_ctx* ctx, const float* tris, uint32_t n, uint32_t k, const wgt_overlap_buffers* out) {
+  WGT_BEGIN(query_begin(ctx, n, check_overlap_args(tris, out, k)));
+  const StageLayout lay = stage_overlap(tris, *out, n, k);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_overlap_buffers dev{(uint8_t*)at(kOvsHit), (uint32_t*)at(kOvsCount), (uint32_t*)at(kOvsPrim)};
+    return overlap_launch(ctx, (const float*)at(kOvsQuery), n, k, dev, nullptr, ctx->stream);
+  });
+}
+
+int wgt_overlap_triangles_stats(wgt_ctx* ctx, const float* d_tris, uint32_t n, uint32_t k,
+                                const wgt_overlap_buffers* d_out, uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;  // what n == 0 leaves
+  const char* bad = check_overlap_args(d_tris, d_out, k);
+  WGT_BEGIN(query_begin(ctx, n, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[2], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = overlap_launch(ctx, d_tris, n, k, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  counts[0] = c[0];
+  counts[1] = c[1];
+  return WGT_OK;
+}
+
+int wgt_overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* query,
+                               uint32_t n, uint32_t k, const wgt_overlap_buffers* out) {
+  if (n == 0) return WGT_OK;
+  if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
+  if (const char* bad = check_overlap_args(query, out, k)) return fail(nullptr, WGT_E_INVALID, bad);
+  overlap_triangles_spec(tris, n_tris, first_prim, query, n, k, *out);
   return WGT_OK;
 }
 

@@ -11,6 +11,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   compute_sample's path loop (:386-393)     -> Context.trace_radiance (a path per caller ray and RNG state)
   (none: every surface along a ray)         -> Context.trace_multi_hits (k nearest hits, hit count), points_inside
   (none: the triangles around a point)      -> Context.nearest_k_points (k nearest, count within a radius), nearest_k_points_spec
+  (none: the triangles a triangle cuts)     -> Context.overlap_triangles (whether, how many, which), overlap_triangles_spec
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -20,7 +21,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (CAMERA_DTYPE, HIT_FIELDS, MULTI_HIT_FIELDS, NEAREST_FIELDS, NEAREST_K_FIELDS, RADIANCE_FIELDS, WGT_MULTI_HIT_TRIS_ONLY, WgtMultiHitBuffers, WgtNearestBuffers, WgtNearestKBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
+from ._lib import (CAMERA_DTYPE, HIT_FIELDS, MULTI_HIT_FIELDS, NEAREST_FIELDS, NEAREST_K_FIELDS, OVERLAP_FIELDS, RADIANCE_FIELDS, WGT_MULTI_HIT_TRIS_ONLY, WgtMultiHitBuffers, WgtNearestBuffers, WgtNearestKBuffers, WgtOverlapBuffers, WgtRadianceBuffers, QUAD_DTYPE, SPHERE_DTYPE, TILE_DTYPE, TRI_DTYPE, WgtDenoiseParams,
                    WgtDenoiseVarianceParams,
                    WgtHitBuffers, WgtMotionBuffers, WgtSamplePlanParams, WgtOrderStats, WgtSceneInfo, WgtStats, WgtTemporalParams, WgtTemporalState, WGT_E_HIP, WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, WgtError, check, lib, ptr)
 
@@ -250,6 +251,39 @@ def nearest_k_points_spec(tris, points, k, max_dist=None, first_prim=0, want=NEA
     check(lib().wgt_nearest_k_points_spec(ptr(tris) if len(tris) else None, len(tris), first_prim, ptr(soa), ptr(lim), n,
                                           kk, ctypes.byref(bufs)))
     return _nearest_k_dict(arr, n, kk)
+
+
+def _overlap_inputs(tris):
+    """The overlap queries' input: (n, 3, 3) corners as nine planes of n floats (a0.x a0.y a0.z a1.x ... a2.z), n."""
+    tris = np.asarray(tris, np.float32).reshape(-1, 9)
+    return np.ascontiguousarray(tris.T), len(tris)
+
+
+def _overlap_arrays(want, n, k):
+    """Host arrays of the overlap fields in `want` (planar: prim (k, n)), their struct, and k as the call takes it."""
+    bad = set(want) - set(OVERLAP_FIELDS)
+    if bad:
+        raise ValueError(f"unknown overlap field(s) {sorted(bad)}; choose from {OVERLAP_FIELDS}")
+    kk = max(int(k), 0)
+    shape = {"hit": (n,), "count": (n,), "prim": (kk, n)}
+    arr = {f: np.zeros(shape[f], np.uint8 if f == "hit" else np.uint32) for f in OVERLAP_FIELDS if f in want}
+    return arr, WgtOverlapBuffers(**{f: a.ctypes.data for f, a in arr.items()}), kk
+
+
+def _overlap_dict(arr):
+    """Queries first: hit (n,) bool, count (n,), prim (n, k)."""
+    return {f: a.astype(bool) if f == "hit" else (np.ascontiguousarray(a.T) if f == "prim" else a) for f, a in arr.items()}
+
+
+def overlap_triangles_spec(T, tris, k, first_prim=0, want=OVERLAP_FIELDS):
+    """The overlap query's definition by brute force on the host (wgt_overlap_triangles_spec, no device): what
+    Context.overlap_triangles returns for a scene that holds `T` (TRI_DTYPE, ids first_prim + index) and the
+    query triangles `tris` ((n, 3, 3) corners)."""
+    T = np.ascontiguousarray(T, TRI_DTYPE)
+    soa, n = _overlap_inputs(tris)
+    arr, bufs, kk = _overlap_arrays(want, n, k)
+    check(lib().wgt_overlap_triangles_spec(ptr(T) if len(T) else None, len(T), first_prim, ptr(soa), n, kk, ctypes.byref(bufs)))
+    return _overlap_dict(arr)
 
 
 def build_id() -> str:
@@ -617,6 +651,35 @@ class Context:
         self._check(self._L.wgt_nearest_k_points_stats(self.h, ctypes.c_void_p(d_points or None),
                                                        ctypes.c_void_p(d_max_dist or None), n, k, ctypes.byref(bufs),
                                                        counts))
+        return int(counts[0]), int(counts[1])
+
+    def overlap_triangles(self, tris, k, want=OVERLAP_FIELDS):
+        """Triangle overlap query (wgt_overlap_triangles): the resident triangles each of `tris` ((n, 3, 3)
+        corners) cuts, a dict of the fields in `want`: hit (n,) bool whether there is one, count (n,) uint32 the
+        number of all of them, prim (n, k) uint32 the k <= 32 lowest primitive ids of them, 0xffffffff beyond
+        the query's triangles.  k is the list's length: at least 1 with "prim" wanted, 0 without.  Two
+        triangles overlap when an edge of one crosses the other (touching counts, coplanar pairs never do);
+        with "hit" alone the search ends at the first one.  Equals overlap_triangles_spec on the resident
+        triangles bit for bit."""
+        soa, n = _overlap_inputs(tris)
+        arr, bufs, kk = _overlap_arrays(want, n, k)
+        self._check(self._L.wgt_overlap_triangles(self.h, ptr(soa), n, kk, ctypes.byref(bufs)))
+        return _overlap_dict(arr)
+
+    def overlap_triangles_async(self, d_tris, n, k, hit=0, count=0, prim=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_tris 9 planes of n floats; hit receives n
+        bytes, count n uint32, prim k planes of n uint32."""
+        bufs = WgtOverlapBuffers(hit or None, count or None, prim or None)
+        self._check(self._L.wgt_overlap_triangles_async(self.h, ctypes.c_void_p(d_tris or None), n, k, ctypes.byref(bufs),
+                                                        ctypes.c_void_p(stream or None)))
+
+    def overlap_triangles_stats(self, d_tris, n, k, hit=0, count=0, prim=0):
+        """The same answers from the counting kernel (wgt_overlap_triangles_stats; synchronous, device
+        pointers): -> (node visits, triangle tests) summed over the n queries."""
+        bufs = WgtOverlapBuffers(hit or None, count or None, prim or None)
+        counts = (ctypes.c_uint64 * 2)()
+        self._check(self._L.wgt_overlap_triangles_stats(self.h, ctypes.c_void_p(d_tris or None), n, k, ctypes.byref(bufs),
+                                                        counts))
         return int(counts[0]), int(counts[1])
 
     def trace_radiance(self, start, direction, seeds=None, seed0=0, samples=1, want=RADIANCE_FIELDS):
