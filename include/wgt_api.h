@@ -34,6 +34,7 @@
  *   (none: every surface along a ray)                 wgt_trace_multi_hits (the k nearest hits, the hit count)
  *   (none: the triangles within a radius of a point)  wgt_nearest_k_points (the k nearest, their number)
  *   (none: the triangles a triangle cuts)             wgt_overlap_triangles (whether, how many, which)
+ *   (none: the triangles a mesh's own triangles cut)  wgt_overlap_self (the same, neighbours by index excluded)
  *
  * Conventions: every call returns 0 on success or a negative WGT_E_* code; the
  * message is available from wgt_last_error(ctx) (per-context, or thread-local
@@ -654,6 +655,54 @@ int wgt_overlap_triangles_stats(wgt_ctx *ctx, const float *d_tris, uint32_t n, u
  * on (n == 0 succeeds first). */
 int wgt_overlap_triangles_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const float *query,
                                uint32_t n, uint32_t k, const wgt_overlap_buffers *out);
+
+/* ---- self-intersection queries: which resident triangles each resident triangle cuts ---- */
+/* The resident mesh against itself, neighbours excluded.  The queries are the resident records; `indices` (3 *
+ * n_tris labels, triangle i's at 3i .. 3i + 2, by upload index; may be NULL) is the only statement of
+ * adjacency; out is a wgt_overlap_buffers sized by the scene's triangle count n_tris and indexed by upload
+ * index (prim: k planes of n_tris).  For resident triangles s and t with records (v0, e1, e2) and padded boxes
+ * (DESIGN.md §3.4), in IEEE f32 with +, -, * only, no division and no fused operation:
+ *   corners(x) = (v0, v0 + e1, v0 + e2), each sum rounded once
+ *   adjacent(s, t): with indices, any of s's three labels equals any of t's.  Labels are compared for
+ *     equality only: they are never addresses and need no range.  With NULL indices nothing is adjacent.
+ *   self_overlap(s, t), lo = min(s, t), hi = max(s, t): s != t, not adjacent(s, t), the two padded boxes
+ *     overlap on each axis (comparisons with equality), and one of wgt_overlap_triangles' six segments
+ *     crosses with corners(lo) as the query A and record hi as the resident B.
+ * The lower id is always the query, so the decision is one function of the unordered pair: t is reported for
+ * s iff s is reported for t, bit for bit.  With S_s the set of t that overlap s: count[s] = |S_s|, all of it,
+ * not capped at k; hit[s] = count > 0; entry j < k of prim is the j-th lowest primitive id of S_s (as
+ * wgt_trace_rays numbers triangles); entries j >= min(|S_s|, k) hold 0xffffffff.  For s < t not adjacent,
+ * whatever wgt_overlap_triangles reports for corners(s) against t is reported here.
+ * Consequences: the box clause removes no real intersection (a corner box nests in its padded box) and makes
+ * the BVH's cull exact (a node box is the exact union of the padded boxes below it), so the answers equal
+ * wgt_overlap_self_spec on the resident triangles bit for bit.  Limits: two triangles that share a label and
+ * still cut each other (a fold through a shared vertex) are not reported; coplanar pairs are never reported;
+ * only triangles are searched.  With hit alone asked for the search ends at the first member.
+ * The answers follow wgt_update_* and wgt_rebuild_*; ids are upload indices throughout.
+ * Order of checks, each WGT_E_INVALID naming the argument, nothing launched: NULL context; WGT_E_NOSCENE; a
+ * scene without triangles (success, nothing done, as wgt_overlap_triangles with n == 0); NULL out; an out
+ * without a field; k > 32; k == 0 with prim asked for; k > 0 without prim; in the stats form NULL counts
+ * last.  Pointers are not validated.
+ * The synchronous form takes host pointers and stages through a device allocation of the call's own; the
+ * async form takes device pointers and a host struct of device pointers and follows wgt_trace_rays_async's
+ * rules.  The return types stand on lines of their own: tests/test_overlap_abi.py counts every one-line
+ * `int wgt_overlap_...(` as one of wgt_overlap_triangles' four forms. */
+int
+wgt_overlap_self(wgt_ctx *ctx, const uint32_t *indices, uint32_t k, const wgt_overlap_buffers *out);
+int
+wgt_overlap_self_async(wgt_ctx *ctx, const uint32_t *d_indices, uint32_t k, const wgt_overlap_buffers *d_out,
+                       void *stream);
+/* Diagnostic, synchronous, device pointers: the same answers from an instrumented instantiation;
+ * counts[0] = node visits, counts[1] = triangle tests, summed over the n_tris lanes. */
+int
+wgt_overlap_self_stats(wgt_ctx *ctx, const uint32_t *d_indices, uint32_t k, const wgt_overlap_buffers *d_out,
+                       uint64_t counts[2]);
+/* Host only, no device: the definition by brute force over every ordered pair of tris[0..n_tris), primitive
+ * ids first_prim + i, each triangle's padded box computed from its record; it culls nothing.  n_tris == 0
+ * succeeds and does nothing; then WGT_E_INVALID for NULL tris, then the checks above from NULL out on. */
+int
+wgt_overlap_self_spec(const wgt_triangle *tris, uint32_t n_tris, uint32_t first_prim, const uint32_t *indices,
+                      uint32_t k, const wgt_overlap_buffers *out);
 
 /* ---- radiance queries (compute_sample's path loop on the caller's rays) ---- */
 /* Planar outputs for n rays; any pointer may be NULL (that field is not written), at least one must

@@ -7,11 +7,11 @@ triangle extension, tile sharding over GPUs and an RCCL gather (webgputracer_amd
 from .tracer import (WGT_HIT_EMISSIVE, WGT_HIT_FRONT_FACE, Context, build_id, bvh_build, bvh_build_compact, bvh_build_morton, bvh_refit, camera_param,
                      cornell_scene, denoise_defaults, denoise_variance_defaults, denoise_variance_workspace_bytes,
                      denoise_workspace_bytes, device_count, load_obj, make_triangles,
-                     mesh_scene, nearest_k_points_spec, nearest_points_spec, overlap_triangles_spec, procedural_mesh, sample_plan_defaults, sample_plan_workspace_bytes, temporal_defaults,
+                     mesh_scene, nearest_k_points_spec, nearest_points_spec, overlap_self_spec, overlap_triangles_spec, procedural_mesh, sample_plan_defaults, sample_plan_workspace_bytes, temporal_defaults,
                      tile_grid, write_obj, write_png)
 
 __all__ = ["WGT_HIT_EMISSIVE", "WGT_HIT_FRONT_FACE", "Context", "build_id", "bvh_build", "bvh_build_compact", "bvh_build_morton", "bvh_refit", "camera_param",
            "cornell_scene", "denoise_defaults", "denoise_variance_defaults", "denoise_variance_workspace_bytes",
            "denoise_workspace_bytes", "device_count", "load_obj", "make_triangles",
-           "mesh_scene", "nearest_k_points_spec", "nearest_points_spec", "overlap_triangles_spec", "procedural_mesh", "sample_plan_defaults", "sample_plan_workspace_bytes", "temporal_defaults",
+           "mesh_scene", "nearest_k_points_spec", "nearest_points_spec", "overlap_self_spec", "overlap_triangles_spec", "procedural_mesh", "sample_plan_defaults", "sample_plan_workspace_bytes", "temporal_defaults",
            "tile_grid", "write_obj", "write_png"]

@@ -196,6 +196,7 @@ EXPORTS = [
     "wgt_trace_multi_hits", "wgt_trace_multi_hits_async", "wgt_trace_multi_hits_stats",
     "wgt_nearest_k_points", "wgt_nearest_k_points_async", "wgt_nearest_k_points_stats", "wgt_nearest_k_points_spec",
     "wgt_overlap_triangles", "wgt_overlap_triangles_async", "wgt_overlap_triangles_stats", "wgt_overlap_triangles_spec",
+    "wgt_overlap_self", "wgt_overlap_self_async", "wgt_overlap_self_stats", "wgt_overlap_self_spec",
 ]
 
 _lib = None
@@ -336,6 +337,10 @@ def lib():
         "wgt_overlap_triangles_stats": (I, [P, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers),
                                             ctypes.POINTER(ctypes.c_uint64)]),
         "wgt_overlap_triangles_spec": (I, [P, U32, U32, P, U32, U32, ctypes.POINTER(WgtOverlapBuffers)]),
+        "wgt_overlap_self": (I, [P, P, U32, ctypes.POINTER(WgtOverlapBuffers)]),
+        "wgt_overlap_self_async": (I, [P, P, U32, ctypes.POINTER(WgtOverlapBuffers), P]),
+        "wgt_overlap_self_stats": (I, [P, P, U32, ctypes.POINTER(WgtOverlapBuffers), ctypes.POINTER(ctypes.c_uint64)]),
+        "wgt_overlap_self_spec": (I, [P, U32, U32, P, U32, ctypes.POINTER(WgtOverlapBuffers)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("WGT_LIB_PATH") and not hasattr(L, name):

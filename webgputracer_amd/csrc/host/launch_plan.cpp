@@ -1204,4 +1204,69 @@ void overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t 
   }
 }
 
+const char* check_overlap_self_args(const wgt_overlap_buffers* out, uint64_t k) {
+  if (!out) return "null output buffers";
+  if (!out->hit && !out->count && !out->prim) return "no overlap field asked for";
+  if (k > WGT_OVERLAP_MAX_K) return "k out of range (0..32)";
+  if (k == 0 && out->prim) return "prim asked for with k == 0";
+  if (k > 0 && !out->prim) return "k > 0 without prim";
+  return nullptr;
+}
+
+std::string plan_overlap_self(const DevScene& sc, const wgt_overlap_buffers* out, uint64_t k, OverlapSelfPlan& p) {
+  p = OverlapSelfPlan{};
+  p.n = sc.n_tris;
+  if (const char* bad = check_overlap_self_args(out, k)) return bad;
+  p.k = (uint32_t)k;
+  p.any = (out->hit && !out->count && !out->prim) ? 1u : 0u;
+  const size_t lds = overlap_lds_bytes(sc.stack, p.k);
+  if (lds > kOverlapLdsPerWorkgroup)
+    return "a stack of " + std::to_string(sc.stack) + " entries and a list of " + std::to_string(p.k) +
+           " triangles per lane need " + std::to_string(lds) + " bytes of LDS, above a workgroup's " +
+           std::to_string(kOverlapLdsPerWorkgroup);
+  p.lds = (uint32_t)lds;
+  return "";
+}
+
+StageLayout stage_overlap_self(const uint32_t* indices, const wgt_overlap_buffers& out, uint32_t n_tris, uint32_t k) {
+  const size_t N = n_tris;
+  return stage_of("a self-intersection query", {{indices ? N * 12 : 0, indices, nullptr}, {out.hit ? N : 0, nullptr, out.hit},
+                                                {out.count ? N * 4 : 0, nullptr, out.count},
+                                                {out.prim ? N * k * 4 : 0, nullptr, out.prim}});
+}
+
+void overlap_self_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const uint32_t* indices,
+                       uint32_t k, const wgt_overlap_buffers& out) {
+  const size_t N = n_tris;
+  if (!out.prim) k = 0;
+  if (k > WGT_OVERLAP_MAX_K) k = WGT_OVERLAP_MAX_K;  // the entry point refused it
+  const auto rec = [&](uint32_t x, f3& v0, f3& e1, f3& e2) {
+    const wgt_triangle& tr = tris[x];
+    v0 = f3{tr.v0[0], tr.v0[1], tr.v0[2]}, e1 = f3{tr.e1[0], tr.e1[1], tr.e1[2]}, e2 = f3{tr.e2[0], tr.e2[1], tr.e2[2]};
+  };
+  for (uint32_t s = 0; s < n_tris; ++s) {
+    f3 sv0, se1, se2, slo, shi;
+    rec(s, sv0, se1, se2);
+    tri_box(sv0, se1, se2, slo, shi);
+    // triangles come in index order, so the first k of S_s are its k lowest ids
+    uint32_t cnt = 0;
+    for (uint32_t t = 0; t < n_tris; ++t) {
+      if (t == s) continue;
+      if (indices && self_adjacent(indices[3 * (size_t)s], indices[3 * (size_t)s + 1], indices[3 * (size_t)s + 2],
+                                   indices[3 * (size_t)t], indices[3 * (size_t)t + 1], indices[3 * (size_t)t + 2]))
+        continue;
+      f3 tv0, te1, te2, tlo, thi;
+      rec(t, tv0, te1, te2);
+      tri_box(tv0, te1, te2, tlo, thi);
+      if (!overlap_boxes(slo, shi, tlo.x, thi.x, tlo.y, thi.y, tlo.z, thi.z)) continue;
+      if (!(s < t ? self_segments(sv0, se1, se2, tv0, te1, te2) : self_segments(tv0, te1, te2, sv0, se1, se2))) continue;
+      if (cnt < k) out.prim[cnt * N + s] = first_prim + t;
+      ++cnt;
+    }
+    if (out.hit) out.hit[s] = cnt > 0 ? 1 : 0;
+    if (out.count) out.count[s] = cnt;
+    for (size_t j = cnt; j < k; ++j) out.prim[j * N + s] = kNoHit;
+  }
+}
+
 }  // namespace wgt

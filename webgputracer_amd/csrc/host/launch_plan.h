@@ -18,6 +18,7 @@
 #include "../wgt_nearest.h"
 #include "../wgt_nearest_k.h"
 #include "../wgt_overlap.h"
+#include "../wgt_overlap_self.h"
 #include "../wgt_radiance.h"
 #include "../wgt_rebuild.h"
 #include "../wgt_sample_plan.h"
@@ -385,6 +386,27 @@ StageLayout stage_overlap(const float* query, const wgt_overlap_buffers& out, ui
 // from tri_box; it culls nothing.  Writes the fields `out` asks for; k as plan_overlap takes it.
 void overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const float* query,
                             uint32_t n, uint32_t k, const wgt_overlap_buffers& out);
+
+// The self-intersection queries (wgt_overlap_self and its forms).  Their own checks after the
+// context, the scene and a scene without triangles, in the calls' order: null out; an out without a field; k
+// above WGT_OVERLAP_MAX_K; k == 0 with prim asked for; k > 0 without prim.  A null index buffer is an answer
+// (nothing is adjacent), not a fault.  Returns the refusal's text, null when fine.
+const char* check_overlap_self_args(const wgt_overlap_buffers* out, uint64_t k);
+// The launch, of any arguments: those checks first (the kernel's list indices rely on them, whoever calls),
+// then one lane per resident triangle (n = sc.n_tris: the kernel reads record i < n and writes at ids below
+// n), the form (the any form iff hit is the only field asked for), k, and the dynamic LDS of the scene's
+// stack and the lists (overlap_lds_bytes).  Returns a refusal, not a launch, when a check fails or that LDS
+// exceeds one workgroup's; empty when fine.  p.lds is 0 on a refusal.
+std::string plan_overlap_self(const DevScene& sc, const wgt_overlap_buffers* out, uint64_t k, OverlapSelfPlan& p);
+// What the synchronous form stages (StageLayout): the index buffer up (no part without one), the fields `out`
+// asks for down, each sized by the scene's triangle count.
+enum OverlapSelfStage { kOssIndex, kOssHit, kOssCount, kOssPrim, kOssParts };
+StageLayout stage_overlap_self(const uint32_t* indices, const wgt_overlap_buffers& out, uint32_t n_tris, uint32_t k);
+// wgt_overlap_self_spec: the definition by brute force (wgt_overlap_self.h) over every ordered pair of
+// tris[0..n_tris), ids first_prim + index, each triangle's box from tri_box; it culls nothing.  indices: 3 *
+// n_tris labels or null.  Writes the fields `out` asks for; k as plan_overlap_self takes it.
+void overlap_self_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const uint32_t* indices,
+                       uint32_t k, const wgt_overlap_buffers& out);
 
 // The pixel queue's order across launches of one view.  The LPT order of
 // a launch depends on its view (scene, camera, frame and tile geometry, knobs), not on its seeds, and

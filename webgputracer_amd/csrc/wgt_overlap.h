@@ -143,6 +143,27 @@ constexpr size_t kOverlapLdsPerWorkgroup = 64 * 1024;
 static_assert(overlap_lds_bytes(kStackMax + 1, WGT_OVERLAP_MAX_K) <= kOverlapLdsPerWorkgroup,
               "the deepest stack and the longest list fit one workgroup's LDS");
 
+// The lane's list in LDS (k_overlap, k_overlap_self): entry j's id at list[j * kBlock], j < len <= k,
+// ascending.  Inserts id if it belongs among the k lowest; every index written is at most k - 1.  A query
+// meets each id once.
+__device__ __forceinline__ void ov_insert(int* __restrict__ list, uint32_t k, uint32_t& len, uint32_t id) {
+  if (k == 0) return;
+  uint32_t j = len;
+  if (len == k) {
+    j = k - 1;
+    if (!(id < (uint32_t)list[j * kBlock])) return;
+  } else {
+    ++len;
+  }
+  while (j > 0) {
+    const int I = list[(j - 1) * kBlock];
+    if (!(id < (uint32_t)I)) break;
+    list[j * kBlock] = I;
+    --j;
+  }
+  list[j * kBlock] = (int)id;
+}
+
 // Launcher implemented in wgt_overlap.hip
 // d_tris: nine planes of p.n floats (a0.x a0.y a0.z a1.x ... a2.z); out: device pointers, a null field is
 // not written.  d_counts (may be null) selects the counting instantiations: += node visits, triangle tests.

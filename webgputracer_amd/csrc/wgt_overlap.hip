@@ -23,26 +23,6 @@ namespace wgt {
 
 namespace {
 
-// The lane's list: entry j's id at list[j * kBlock], j < len <= k, ascending.  Inserts id if it belongs
-// among the k lowest; every index written is at most k - 1.  A query meets each id once.
-__device__ __forceinline__ void ov_insert(int* __restrict__ list, uint32_t k, uint32_t& len, uint32_t id) {
-  if (k == 0) return;
-  uint32_t j = len;
-  if (len == k) {
-    j = k - 1;
-    if (!(id < (uint32_t)list[j * kBlock])) return;
-  } else {
-    ++len;
-  }
-  while (j > 0) {
-    const int I = list[(j - 1) * kBlock];
-    if (!(id < (uint32_t)I)) break;
-    list[j * kBlock] = I;
-    --j;
-  }
-  list[j * kBlock] = (int)id;
-}
-
 // TRIS: the scene has triangles.  ANY: only hit is asked for, the traversal ends at the first overlapping
 // triangle.  STATS: the counting instantiation (wgt_overlap_triangles_stats) adds its lanes' node visits
 // and triangle tests to counts[0] and counts[1].

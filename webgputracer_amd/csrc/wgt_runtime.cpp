@@ -473,6 +473,20 @@ int overlap_launch(wgt_ctx* ctx, const float* d_tris, uint32_t n, uint32_t k, co
   if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
   return launch_on(ctx, s, "launch_overlap", [&] { return launch_overlap(ctx->sc, p, d_tris, dev, d_counts, s); });
 }
+// The self-intersection query (behind its checks): the plan (plan_overlap_self), then one launch of the planned form.
+int overlap_self_launch(wgt_ctx* ctx, const uint32_t* d_indices, uint32_t k, const wgt_overlap_buffers& dev,
+                        unsigned long long* d_counts, hipStream_t s) {
+  OverlapSelfPlan p;
+  const std::string bad = plan_overlap_self(ctx->sc, &dev, k, p);
+  if (!bad.empty()) return fail(ctx, WGT_E_INVALID, bad);
+  return launch_on(ctx, s, "launch_overlap_self",
+                   [&] { return launch_overlap_self(ctx->sc, p, d_indices, dev, d_counts, s); });
+}
+// The self-intersection calls' preamble: query_begin with the scene's triangle count as n, so a scene without
+// triangles is answered as the overlap query answers n == 0.
+int overlap_self_begin(wgt_ctx* ctx, const char* bad) {
+  return query_begin(ctx, ctx && ctx->has_scene ? ctx->sc.n_tris : 1u, bad);
+}
 // The G-buffer launch of a tile list (behind check_render_args, the render calls' preamble).
 int gbuffer_launch(wgt_ctx* ctx, const DevFrame& fr, const SampleArgs& sm, const wgt_tile* d_tiles,
                    const wgt_hit_buffers& dev, float* d_rays, hipStream_t s) {
@@ -1507,6 +1521,46 @@ int wgt_overlap_triangles_spec(const wgt_triangle* tris, uint32_t n_tris, uint32
   if (n_tris > 0 && !tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
   if (const char* bad = check_overlap_args(query, out, k)) return fail(nullptr, WGT_E_INVALID, bad);
   overlap_triangles_spec(tris, n_tris, first_prim, query, n, k, *out);
+  return WGT_OK;
+}
+
+int wgt_overlap_self_async(wgt_ctx* ctx, const uint32_t* d_indices, uint32_t k, const wgt_overlap_buffers* d_out,
+                           void* stream) {
+  WGT_BEGIN(overlap_self_begin(ctx, check_overlap_self_args(d_out, k)));
+  return overlap_self_launch(ctx, d_indices, k, *d_out, nullptr, stream_or_own(ctx, stream));
+}
+
+int wgt_overlap_self(wgt_ctx* ctx, const uint32_t* indices, uint32_t k, const wgt_overlap_buffers* out) {
+  WGT_BEGIN(overlap_self_begin(ctx, check_overlap_self_args(out, k)));
+  const StageLayout lay = stage_overlap_self(indices, *out, ctx->sc.n_tris, k);
+  return run_staged(ctx, lay, [&](auto at) {
+    const wgt_overlap_buffers dev{(uint8_t*)at(kOssHit), (uint32_t*)at(kOssCount), (uint32_t*)at(kOssPrim)};
+    return overlap_self_launch(ctx, (const uint32_t*)at(kOssIndex), k, dev, nullptr, ctx->stream);
+  });
+}
+
+int wgt_overlap_self_stats(wgt_ctx* ctx, const uint32_t* d_indices, uint32_t k, const wgt_overlap_buffers* d_out,
+                           uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;  // what a scene without triangles leaves
+  const char* bad = check_overlap_self_args(d_out, k);
+  WGT_BEGIN(overlap_self_begin(ctx, bad ? bad : (counts ? nullptr : "null counts")));
+  unsigned long long c[2], *d_c;
+  int rc;
+  if ((rc = scratch(ctx, wgt_ctx::kCounters, sizeof c, d_c))) return rc;
+  WGT_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof c, ctx->stream));
+  if ((rc = overlap_self_launch(ctx, d_indices, k, *d_out, d_c, ctx->stream))) return rc;
+  if ((rc = fetch(ctx, c, d_c, sizeof c)) || (rc = sync_stream(ctx))) return rc;
+  counts[0] = c[0];
+  counts[1] = c[1];
+  return WGT_OK;
+}
+
+int wgt_overlap_self_spec(const wgt_triangle* tris, uint32_t n_tris, uint32_t first_prim, const uint32_t* indices,
+                          uint32_t k, const wgt_overlap_buffers* out) {
+  if (n_tris == 0) return WGT_OK;
+  if (!tris) return fail(nullptr, WGT_E_INVALID, "null triangles");
+  if (const char* bad = check_overlap_self_args(out, k)) return fail(nullptr, WGT_E_INVALID, bad);
+  overlap_self_spec(tris, n_tris, first_prim, indices, k, *out);
   return WGT_OK;
 }
 

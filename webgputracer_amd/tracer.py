@@ -12,6 +12,7 @@ Mirrors the reference's host objects for the path-tracing hot path:
   (none: every surface along a ray)         -> Context.trace_multi_hits (k nearest hits, hit count), points_inside
   (none: the triangles around a point)      -> Context.nearest_k_points (k nearest, count within a radius), nearest_k_points_spec
   (none: the triangles a triangle cuts)     -> Context.overlap_triangles (whether, how many, which), overlap_triangles_spec
+  (none: the triangles a mesh's own cut)    -> Context.overlap_self, self_intersections (neighbours by index excluded), overlap_self_spec
 The C++ mirror (include/wgt/{scene,camera,renderer}.h) is the same API for C++ callers.
 """
 from __future__ import annotations
@@ -283,6 +284,27 @@ def overlap_triangles_spec(T, tris, k, first_prim=0, want=OVERLAP_FIELDS):
     soa, n = _overlap_inputs(tris)
     arr, bufs, kk = _overlap_arrays(want, n, k)
     check(lib().wgt_overlap_triangles_spec(ptr(T) if len(T) else None, len(T), first_prim, ptr(soa), n, kk, ctypes.byref(bufs)))
+    return _overlap_dict(arr)
+
+
+def _self_indices(indices, n_tris):
+    """The self-intersection queries' index buffer: (n_tris, 3) labels as 3 * n_tris uint32, or None."""
+    if indices is None:
+        return None
+    idx = np.ascontiguousarray(np.asarray(indices, np.uint32).reshape(-1))
+    if len(idx) != 3 * n_tris:
+        raise ValueError(f"indices hold {len(idx)} labels, the mesh has {n_tris} triangles: 3 per triangle are needed")
+    return idx
+
+
+def overlap_self_spec(T, indices=None, k=0, first_prim=0, want=OVERLAP_FIELDS):
+    """The self-intersection query's definition by brute force on the host (wgt_overlap_self_spec, no device):
+    what Context.overlap_self returns for a scene that holds `T` (TRI_DTYPE, ids first_prim + index) and the
+    index buffer `indices` ((n_tris, 3) labels, or None: nothing is adjacent)."""
+    T = np.ascontiguousarray(T, TRI_DTYPE)
+    idx = _self_indices(indices, len(T))
+    arr, bufs, kk = _overlap_arrays(want, len(T), k)
+    check(lib().wgt_overlap_self_spec(ptr(T) if len(T) else None, len(T), first_prim, ptr(idx), kk, ctypes.byref(bufs)))
     return _overlap_dict(arr)
 
 
@@ -681,6 +703,48 @@ class Context:
         self._check(self._L.wgt_overlap_triangles_stats(self.h, ctypes.c_void_p(d_tris or None), n, k, ctypes.byref(bufs),
                                                         counts))
         return int(counts[0]), int(counts[1])
+
+    def overlap_self(self, indices=None, k=0, want=OVERLAP_FIELDS):
+        """Self-intersection query (wgt_overlap_self): the resident triangles each resident triangle cuts, a dict
+        of the fields in `want`, indexed by upload index: hit (n_tris,) bool, count (n_tris,) uint32 the number
+        of all of them, prim (n_tris, k) uint32 the k <= 32 lowest primitive ids of them, 0xffffffff beyond.
+        `indices` ((n_tris, 3) vertex labels) is the only statement of adjacency: two triangles that share a
+        label never report each other; with None nothing is adjacent.  k is the list's length: at least 1 with
+        "prim" wanted, 0 without.  The decision is symmetric (t in s's set iff s in t's); with "hit" alone the
+        search ends at the first member.  Equals overlap_self_spec on the resident triangles bit for bit."""
+        n = self.scene_info()["n_tris"]
+        idx = _self_indices(indices, n)
+        arr, bufs, kk = _overlap_arrays(want, n, k)
+        self._check(self._L.wgt_overlap_self(self.h, ptr(idx), kk, ctypes.byref(bufs)))
+        return _overlap_dict(arr)
+
+    def overlap_self_async(self, d_indices, k, hit=0, count=0, prim=0, stream=0):
+        """Device-pointer launch (raw device addresses, 0 = NULL): d_indices 3 * n_tris uint32 labels or 0; hit
+        receives n_tris bytes, count n_tris uint32, prim k planes of n_tris uint32."""
+        bufs = WgtOverlapBuffers(hit or None, count or None, prim or None)
+        self._check(self._L.wgt_overlap_self_async(self.h, ctypes.c_void_p(d_indices or None), k, ctypes.byref(bufs),
+                                                   ctypes.c_void_p(stream or None)))
+
+    def overlap_self_stats(self, d_indices, k, hit=0, count=0, prim=0):
+        """The same answers from the counting kernel (wgt_overlap_self_stats; synchronous, device pointers):
+        -> (node visits, triangle tests) summed over the resident triangles."""
+        bufs = WgtOverlapBuffers(hit or None, count or None, prim or None)
+        counts = (ctypes.c_uint64 * 2)()
+        self._check(self._L.wgt_overlap_self_stats(self.h, ctypes.c_void_p(d_indices or None), k, ctypes.byref(bufs),
+                                                   counts))
+        return int(counts[0]), int(counts[1])
+
+    def self_intersections(self, indices, k=32):
+        """The mesh's self-intersections as pairs: (pairs, truncated).  pairs is (m, 2) int64, the unique pairs
+        (s, t) of upload indices with s < t that overlap_self(indices, k) lists, in lexicographic order;
+        truncated is True when a triangle cuts more than k others, so that its list (and, if every partner's
+        list is cut short too, the pairs) may be incomplete.  Python over the query: no kernel of its own."""
+        r = self.overlap_self(indices, k, want=("count", "prim"))
+        info = self.scene_info()
+        s, j = np.nonzero(r["prim"] != 0xFFFFFFFF)
+        t = r["prim"][s, j].astype(np.int64) - (info["n_lights"] + info["n_quads"])
+        pairs = np.unique(np.stack([np.minimum(s, t), np.maximum(s, t)], 1), axis=0) if len(s) else np.zeros((0, 2), np.int64)
+        return pairs.astype(np.int64), bool((r["count"] > k).any())
 
     def trace_radiance(self, start, direction, seeds=None, seed0=0, samples=1, want=RADIANCE_FIELDS):
         """Radiance query (wgt_trace_radiance): `samples` paths of the renderer's raytrace() along each
